@@ -14,10 +14,16 @@ ResNet-101 + ASPP seg step, bs 4, 1024x512), ``deeplab-da`` (configs[4] per GPU:
 iteration, 2 + 2 images at 1280x720).  Unit: source images/s (one DA unit = a source image
 with its paired target image).
 
-Extra fields: inference FPS (eval forward, bs 8 and bs 1), the live conv roofline
-(HIP events around every implicit-GEMM launch over one extra step after the timed
-region), and the CPU baseline (the oracle's restatement of the reference step on the host
-cores, bounded sample, rank 0 at N=1 only).
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line.
+``--dump-outputs DIR`` also writes what the last timed step returned and left behind
+(``loss.npy``, ``correct.npy``, ``params.npy``; inputs and weights are seeded, so two builds
+can be compared output for output).
+
+``--full`` adds the extra fields, each measured in a run of its own after the timed region:
+inference FPS (eval forward, bs 8 and bs 1), the live conv roofline (HIP events around every
+implicit-GEMM launch over one extra step), and the CPU baseline (the oracle's restatement of
+the reference step on the host cores, bounded sample, rank 0 at N=1 only).  ``--no-infer``,
+``--no-conv-profile`` and ``--no-cpu-baseline`` drop single legs of a ``--full`` run.
 """
 import argparse
 import json
@@ -65,18 +71,28 @@ def parse():
     ap.add_argument("--allreduce-dtype", default="fp32", choices=["fp32", "fp16", "bf16"],
                     help="gradient all-reduce wire dtype (N>1)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-infer", action="store_true")
-    ap.add_argument("--conv-report", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure inference FPS, the event-timed conv roofline "
+                         "and the CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-infer", action="store_true", help="with --full: skip the inference FPS runs")
+    ap.add_argument("--conv-report", action="store_true", help="with --full: per-conv table on stderr")
     ap.add_argument("--da-unfused", action="store_true",
                     help="A/B: discriminator input through interpolate + softmax (no fused upsample_softmax)")
-    ap.add_argument("--no-conv-profile", action="store_true", help="skip the event-timed roofline step")
+    ap.add_argument("--no-conv-profile", action="store_true", help="with --full: skip the event-timed roofline step")
     ap.add_argument("--submit", default="auto", choices=["auto", "branches", "serial", "split"],
                     help="graph submission variant (runtime.GraphedStep; auto = time both captures, keep the faster)")
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                     help="replay the iteration as hipGraph segments (auto = on; under data parallelism "
                          "the RCCL collectives run between the segments, runtime.GraphedStep)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.conv_report and not args.full:
+        ap.error("--conv-report reads the event-timed conv step: run it with --full")
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def synthetic_batch(n, seed, device, h=H, w=W):
@@ -156,6 +172,26 @@ def conv_traffic(args, dtype):
         return None
     with open(paths[-1]) as f:
         return json.load(f)["conv_gemm_kernel_bytes_per_step"]
+
+
+DUMP_PARAM_ELEMS = 8 * 1024 * 1024  # params.npy holds at most this many float32 values (32 MiB)
+
+
+def dump_outputs(path, loss, corr, net):
+    """``--dump-outputs``: what the caller of the last timed step holds afterwards, as float32
+    ``.npy`` files -- the step's returned loss and correct-pixel count (float64), and the
+    generator's updated parameters (float32, flat, named_parameters order; above
+    DUMP_PARAM_ELEMS values a fixed, seeded sample of positions, the same in every run and
+    build)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat = torch.cat([p.detach().float().reshape(-1) for _, p in net.named_parameters()])
+    if flat.numel() > DUMP_PARAM_ELEMS:
+        g = torch.Generator().manual_seed(1234)
+        idx = torch.randperm(flat.numel(), generator=g)[:DUMP_PARAM_ELEMS].sort().values
+        flat = flat[idx.to(flat.device)]
+    for name, t in (("loss", loss.detach().double()), ("correct", corr.detach().double()), ("params", flat)):
+        np.save(os.path.join(path, name + ".npy"), t.reshape(-1).cpu().numpy())
 
 
 def build(args, dev, rank):
@@ -297,10 +333,13 @@ def main():
     ms = 1000.0 * elapsed / args.steps
     imgs = args.batch * world * args.steps / elapsed
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, corr, net)
 
     # ---- live conv roofline: one more step with HIP events around each implicit-GEMM launch
     recs = []
-    if not args.no_conv_profile:
+    profiled = args.full and not args.no_conv_profile
+    if profiled:
         # a GPU-bound spacer ahead of the profiled step lets the host run ahead, so the step's
         # launches queue back to back and each conv's events bracket GPU time rather than the
         # host launch gaps of an eager step (~40 ms of bf16 GEMMs vs ~8 ms of host enqueue)
@@ -338,7 +377,7 @@ def main():
     # Eval-mode forward (BN folded into the conv epilogues), replayed as one hipGraph per batch
     # size (runtime.GraphedForward); each replay copies the batch into the captured input.
     infer = {}
-    if not args.no_infer and args.workload == "bisenet-seg":
+    if args.full and not args.no_infer and args.workload == "bisenet-seg":
         from rtsds_amd.runtime import GraphedForward
         net.eval()
         with torch.no_grad():
@@ -407,14 +446,16 @@ def main():
                    **({"discriminator": "TinyDomainDiscriminator", "target_batch_per_gpu": args.batch} if wl[1] else {}),
                    **({"grad_allreduce_dtype": args.allreduce_dtype} if world > 1 else {})},
         **infer,
-        "roofline": {"bound": "mfma", "kernel": "conv_gemm_kernel (implicit-GEMM conv fwd/dgrad/wgrad, "
-                                                "incl. dgrad repack + wgrad split-reduce launches)",
-                     "achieved": round(achieved, 2), "peak": MFMA_BF16_PEAK_TFLOPS if dtype == torch.bfloat16 else 157.3,
-                     "unit": "TFLOP/s", "frac": round(achieved / (MFMA_BF16_PEAK_TFLOPS if dtype == torch.bfloat16 else 157.3), 4),
-                     "traffic": conv_traffic(args, dtype), "traffic_unit": "HBM bytes per step, all conv launches",
-                     "launches_per_step": len(recs),
-                     "conv_ms_per_step": round(conv_ms, 3),
-                     "conv_gflop_per_step": round(conv_flop / 1e9, 1)},
+        # the event-timed conv step is a --full leg; a plain run reports no roofline
+        **({"roofline": {"bound": "mfma", "kernel": "conv_gemm_kernel (implicit-GEMM conv fwd/dgrad/wgrad, "
+                                                    "incl. dgrad repack + wgrad split-reduce launches)",
+                         "achieved": round(achieved, 2), "peak": MFMA_BF16_PEAK_TFLOPS if dtype == torch.bfloat16 else 157.3,
+                         "unit": "TFLOP/s",
+                         "frac": round(achieved / (MFMA_BF16_PEAK_TFLOPS if dtype == torch.bfloat16 else 157.3), 4),
+                         "traffic": conv_traffic(args, dtype), "traffic_unit": "HBM bytes per step, all conv launches",
+                         "launches_per_step": len(recs),
+                         "conv_ms_per_step": round(conv_ms, 3),
+                         "conv_gflop_per_step": round(conv_flop / 1e9, 1)}} if args.full else {}),
         "whole_step_conv_flop_rate_tflops": round(wl[5] * args.batch / ms, 2),
         "final_loss": round(final_loss, 4),
         # host time submitting the iteration (graph segment launches + collectives), and the
@@ -427,7 +468,7 @@ def main():
         "timed_s": round(elapsed, 3),
         **({"ranks": world, "backend": backend} if backend else {}),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "bisenet-seg":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "bisenet-seg":
         out["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(out), flush=True)

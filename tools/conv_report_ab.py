@@ -1,4 +1,4 @@
-"""Same-box A/B of bench.py --conv-report tables: conv_report_ab.py PREFIX_A PREFIX_B
+"""Same-box A/B of bench.py --full --conv-report tables: conv_report_ab.py PREFIX_A PREFIX_B
 (glob prefixes of the report files, e.g. gpurun_out/r5h_report_base_ gpurun_out/r5h_report_old2_).
 Sums the event-timed us of every (op, geometry) row per report (both tables: train step and eval
 forward), averages over the repeated reports of a variant, prints the rows that moved by >= 2 %

@@ -1,4 +1,4 @@
-"""Per-layer conv table (markdown) from a `bench.py --conv-report` stderr capture: one row per
+"""Per-layer conv table (markdown) from a `bench.py --full --conv-report` stderr capture: one row per
 conv geometry, fwd / dgrad / wgrad microseconds and TF/s, summed over the layers sharing it.
 usage: python tools/conv_table.py REPORT.txt [rows]"""
 import collections
