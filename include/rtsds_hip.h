@@ -415,6 +415,20 @@ int rtsds_upsoftmax_bwd(const void* dy, int dy_ld, const void* y, int y_ld, void
                         int wi, int c, int ho, int wo, float scale_h, float scale_w, int dtype,
                         void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- multi-scale / flip evaluation
+ * One pass of the summed-probability evaluation protocol: p = softmax(interpolate_bilinear(x))
+ * exactly as rtsds_upsoftmax_fwd forms it (same geometries, c <= 32), kept in fp32 (fp32 mode:
+ * bit-identical to rtsds_upsoftmax_fwd's output; bf16 mode: its value before the bf16 rounding),
+ * stored into (accumulate == 0) or added onto (accumulate != 0: one fp32 add of the rounded
+ * product, never an FMA) acc, fp32 NHWC [n][ho][wo][c] with dense pitch c.  flip != 0 stores
+ * the pixel computed at output column ow at column wo - 1 - ow (un-mirrors the prediction of a
+ * mirrored image).  pred (int64 [n][ho][wo], may be NULL) receives the argmax over classes of
+ * the updated acc row, first maximum wins, at the same column.  One owner per output pixel:
+ * no atomics, no host synchronisation (graph-capture safe).                                 */
+int rtsds_upsoftmax_acc(const void* x, float* acc, int64_t* pred, int n, int hi, int wi, int c,
+                        int ho, int wo, float scale_h, float scale_w, int flip, int accumulate,
+                        int dtype, void* stream);
+
 /* ---------------------------------------------------------------- input pipeline
  * The reference's per-sample torchvision transforms (main.py:60-108; datasets/cityscapes.py:
  * 56-68, datasets/gta5.py:69-118) on a decoded HWC image in device memory.
@@ -478,7 +492,7 @@ int rtsds_pooled_mlp_fwd(const void* p, const void* w1, const float* b1, const v
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 10
+#define RTSDS_ABI_VERSION 11
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

@@ -1577,15 +1577,55 @@ RT_DEV void stage_out(T* __restrict__ g, const T* s, int nel) {
 static const int kUpsmMaxC = 32;
 static const int kUpsmPix = 256;
 static const int kUpsmLds = 48 * 1024;
-// one output pixel of upsoftmax_fwd_kernel: blend, softmax, padded row into the LDS tile
+// one tile of the fused resize + softmax kernels (blockIdx.x = row * tiles + tile): up to 256
+// output pixels [ow0, ow0 + np) of output row `row`, the two source rows r0 / r1 with their
+// weights and, STAGED, their columns [wlo, wlo + n1 / c) copied to src as fp32 [2][n1] (the
+// caller places the barrier)
+template <typename T>
+struct UpsmTile {
+  long row;  // img * ho + oh
+  int ow0, np, wlo, n1;
+  float lh0, lh1;
+  const T *r0, *r1;
+};
+template <typename T, bool STAGED>
+RT_DEV UpsmTile<T> upsm_tile(const T* __restrict__ x, float* src, int hi, int wi, int c, int ho, int wo, float sh, float sw,
+                             int tiles) {
+  UpsmTile<T> t;
+  const int tile = blockIdx.x % tiles;
+  t.row = blockIdx.x / tiles;
+  const int oh = (int)(t.row % ho), img = (int)(t.row / ho);
+  t.ow0 = tile * kUpsmPix;
+  t.np = min(kUpsmPix, wo - t.ow0);
+  int h0, h1;
+  bil_src(oh, sh, hi, h0, h1, t.lh0, t.lh1);
+  t.r0 = x + ((long)img * hi + h0) * wi * c;
+  t.r1 = x + ((long)img * hi + h1) * wi * c;
+  t.wlo = 0;
+  t.n1 = 0;
+  if (STAGED) {  // taps are monotone in ow: columns [w0(ow0), w1(last)] cover the tile
+    int a0, a1, b0, b1;
+    float t0, t1;
+    bil_src(t.ow0, sw, wi, a0, a1, t0, t1);
+    bil_src(t.ow0 + t.np - 1, sw, wi, b0, b1, t0, t1);
+    t.wlo = a0;
+    t.n1 = (b1 - a0 + 1) * c;
+    for (int e = threadIdx.x; e < t.n1; e += 256) {
+      src[e] = to_f(t.r0[(long)t.wlo * c + e]);
+      src[t.n1 + e] = to_f(t.r1[(long)t.wlo * c + e]);
+    }
+  }
+  return t;
+}
+// one output pixel's blend + softmax, shared by upsoftmax_fwd_kernel and upsoftmax_acc_kernel:
+// on return the probability of class k is the fp32 product z[k] * iz
 template <typename T, bool STAGED, int CC>
-RT_DEV void upsm_pixel(const T* __restrict__ r0, const T* __restrict__ r1, const float* src, T* o, int wlo, int n1, int c_, int ow,
-                       float sw, int wi, float lh0, float lh1, int yld) {
+RT_DEV void upsm_probs(const T* __restrict__ r0, const T* __restrict__ r1, const float* src, int wlo, int n1, int c_, int ow,
+                       float sw, int wi, float lh0, float lh1, float (&z)[kUpsmMaxC], float& iz) {
   const int c = CC > 0 ? CC : c_;
   int w0, w1;
   float lw0, lw1;
   bil_src(ow, sw, wi, w0, w1, lw0, lw1);
-  float z[kUpsmMaxC];
   float m = -INFINITY;
 #pragma unroll
   for (int k = 0; k < kUpsmMaxC; ++k) {
@@ -1614,7 +1654,16 @@ RT_DEV void upsm_pixel(const T* __restrict__ r0, const T* __restrict__ r1, const
       z[k] = expf(z[k] - m);
       sum += z[k];
     }
-  const float iz = 1.f / sum;
+  iz = 1.f / sum;
+}
+// one output pixel of upsoftmax_fwd_kernel: blend, softmax, padded row into the LDS tile
+template <typename T, bool STAGED, int CC>
+RT_DEV void upsm_pixel(const T* __restrict__ r0, const T* __restrict__ r1, const float* src, T* o, int wlo, int n1, int c_, int ow,
+                       float sw, int wi, float lh0, float lh1, int yld) {
+  const int c = CC > 0 ? CC : c_;
+  float z[kUpsmMaxC];
+  float iz;
+  upsm_probs<T, STAGED, CC>(r0, r1, src, wlo, n1, c_, ow, sw, wi, lh0, lh1, z, iz);
   // the padded row goes through LDS so the tile leaves as lane-consecutive 16-B chunks (the
   // tile's rows are contiguous in y): full-line writes instead of 64-B-strided partial ones
   if (sizeof(T) == 2 && yld == 32) {  // 4 x 16-B LDS writes, chunk q at slot q ^ (pixel & 3)
@@ -1638,34 +1687,15 @@ __global__ void __launch_bounds__(256) upsoftmax_fwd_kernel(const T* __restrict_
                                                             int ho, int wo, float sh, float sw, int yld, int tiles) {
   const int c = CC > 0 ? CC : c_;
   extern __shared__ __attribute__((aligned(16))) float src[];  // STAGED: [2][ncols][c]
-  const int tile = blockIdx.x % tiles;
-  const long row = blockIdx.x / tiles;  // img * ho + oh
-  const int oh = (int)(row % ho), img = (int)(row / ho);
-  const int ow0 = tile * kUpsmPix, np = min(kUpsmPix, wo - ow0);
   const int tid = threadIdx.x;
-  int h0, h1;
-  float lh0, lh1;
-  bil_src(oh, sh, hi, h0, h1, lh0, lh1);
-  const T* r0 = x + ((long)img * hi + h0) * wi * c;
-  const T* r1 = x + ((long)img * hi + h1) * wi * c;
-  int wlo = 0, n1 = 0;
-  if (STAGED) {  // taps are monotone in ow: columns [w0(ow0), w1(last)] cover the tile
-    int a0, a1, b0, b1;
-    float t0, t1;
-    bil_src(ow0, sw, wi, a0, a1, t0, t1);
-    bil_src(ow0 + np - 1, sw, wi, b0, b1, t0, t1);
-    wlo = a0;
-    n1 = (b1 - a0 + 1) * c;
-    for (int e = tid; e < n1; e += 256) {
-      src[e] = to_f(r0[(long)wlo * c + e]);
-      src[n1 + e] = to_f(r1[(long)wlo * c + e]);
-    }
-    __syncthreads();
-  }
-  T* outbuf = (T*)(src + ((2 * n1 + 3) & ~3));  // [256][yld], 16-B aligned
-  if (tid < np) upsm_pixel<T, STAGED, CC>(r0, r1, src, outbuf + tid * yld, wlo, n1, c, ow0 + tid, sw, wi, lh0, lh1, yld);
+  const UpsmTile<T> tl = upsm_tile<T, STAGED>(x, src, hi, wi, c, ho, wo, sh, sw, tiles);
+  const int ow0 = tl.ow0, np = tl.np;
+  if (STAGED) __syncthreads();
+  T* outbuf = (T*)(src + ((2 * tl.n1 + 3) & ~3));  // [256][yld], 16-B aligned
+  if (tid < np)
+    upsm_pixel<T, STAGED, CC>(tl.r0, tl.r1, src, outbuf + tid * yld, tl.wlo, tl.n1, c, ow0 + tid, sw, wi, tl.lh0, tl.lh1, yld);
   __syncthreads();  // every lane reaches the same barrier (no early exit)
-  T* dst = y + (row * wo + ow0) * yld;
+  T* dst = y + (tl.row * wo + ow0) * yld;
   if (sizeof(T) == 2 && yld == 32) {  // un-swizzle: LDS read linear, global chunk q = slot ^ (pixel & 3)
     typedef typename VecT<T>::v16 V16;
     for (int i = tid; i < np * 4; i += 256) {
@@ -1675,6 +1705,75 @@ __global__ void __launch_bounds__(256) upsoftmax_fwd_kernel(const T* __restrict_
   } else {
     stage_out(dst, outbuf, np * yld);
   }
+}
+// ------------------------------------------------------------------ multi-scale / flip evaluation
+// One pass of the summed-probability protocol (validation.predict_multiscale): the
+// upsoftmax_fwd_kernel tile (same staging, same upsm_probs arithmetic), but the probabilities stay
+// fp32 and are stored into / added onto the fp32 sum acc [n][ho][wo][c]; with flip the tile lands
+// on the mirrored column range, which is still contiguous, so the pixel order is reversed inside
+// LDS and the tile leaves (and, when accumulating, the old sums arrive) as lane-consecutive 16-B
+// chunks.  The LDS tile sits at the destination's offset inside its 16-B chunk (a 19-class row
+// is 76 B, so tiles start at any 4-B phase): head / tail floats move singly, the rest as float4.
+// The add is one fp32 add of the rounded product (never an FMA), so acc equals the unfused
+// softmax -> flip -> add chain bit for bit.  pred = first-max argmax of the updated row.
+template <bool IN>  // IN: global -> LDS, else LDS -> global; s and g share the phase `(4 - head) & 3`
+RT_DEV void upsm_tile_copy(float* __restrict__ g, float* s, int nel, int head) {
+  const int tid = threadIdx.x;
+  const int nv = (nel - head) >> 2, rest = nel - head - (nv << 2);
+  float4* gv = (float4*)(g + head);
+  float4* sv = (float4*)(s + head);
+  for (int i = tid; i < nv; i += 256) {
+    if (IN) sv[i] = gv[i];
+    else gv[i] = sv[i];
+  }
+  int e = -1;  // head (< 4 floats) on lanes 0.., tail (< 4 floats) on the second wave
+  if (tid < head) e = tid;
+  else if (tid >= 64 && tid - 64 < rest) e = head + (nv << 2) + tid - 64;
+  if (e >= 0) {
+    if (IN) s[e] = g[e];
+    else g[e] = s[e];
+  }
+}
+template <typename T, bool STAGED, int CC>  // CC > 0: compile-time class count (19), 0: runtime c
+__global__ void __launch_bounds__(256) upsoftmax_acc_kernel(const T* __restrict__ x, float* __restrict__ acc,
+                                                            int64_t* __restrict__ pred, int hi, int wi, int c_, int ho, int wo,
+                                                            float sh, float sw, int flip, int accumulate, int tiles) {
+  const int c = CC > 0 ? CC : c_;
+  extern __shared__ __attribute__((aligned(16))) float src[];  // STAGED: [2][ncols][c]
+  const int tid = threadIdx.x;
+  const UpsmTile<T> tl = upsm_tile<T, STAGED>(x, src, hi, wi, c, ho, wo, sh, sw, tiles);
+  const int ow0 = tl.ow0, np = tl.np;
+  // destination: output columns [ow0, ow0 + np), mirrored to [wo - ow0 - np, wo - ow0) with flip
+  const int d0 = flip ? wo - ow0 - np : ow0;
+  float* dst = acc + (tl.row * wo + d0) * c;
+  const int nel = np * c;
+  const int mis = (int)(((uintptr_t)dst >> 2) & 3), head = min(nel, (4 - mis) & 3);
+  float* tbuf = src + ((2 * tl.n1 + 3) & ~3) + mis;  // [np][c] at dst's phase inside a 16-B chunk
+  if (accumulate) upsm_tile_copy<true>(dst, tbuf, nel, head);
+  __syncthreads();
+  if (tid < np) {
+    float z[kUpsmMaxC];
+    float iz;
+    upsm_probs<T, STAGED, CC>(tl.r0, tl.r1, src, tl.wlo, tl.n1, c, ow0 + tid, sw, wi, tl.lh0, tl.lh1, z, iz);
+    const int lp = flip ? np - 1 - tid : tid;
+    float* o = tbuf + lp * c;
+    float best = 0.f;
+    int bi = 0;
+#pragma unroll
+    for (int k = 0; k < kUpsmMaxC; ++k)
+      if (k < c) {
+        float v = __fmul_rn(z[k], iz);
+        if (accumulate) v = __fadd_rn(o[k], v);
+        o[k] = v;
+        if (k == 0 || v > best) {
+          best = v;
+          bi = k;
+        }
+      }
+    if (pred != nullptr) pred[tl.row * wo + d0 + lp] = bi;
+  }
+  __syncthreads();  // every lane reaches the same barrier (no early exit)
+  upsm_tile_copy<false>(dst, tbuf, nel, head);
 }
 // exact output-pixel span [lo, hi] read by input columns [iw0, iw1] (bil_wsum_range bounds)
 __host__ __device__ inline void upsm_span(int iw0, int iw1, float sw, int wi, int wo, int& lo, int& hi) {
@@ -1797,6 +1896,33 @@ extern "C" int rtsds_upsoftmax_fwd(const void* x, void* y, int n, int hi, int wi
     else
       hipLaunchKernelGGL((upsoftmax_fwd_kernel<T, false, 0>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)x, (T*)y, hi,
                          wi, c, ho, wo, scale_h, scale_w, y_ld, tiles);
+  });
+  RET_LAUNCH();
+}
+extern "C" int rtsds_upsoftmax_acc(const void* x, float* acc, int64_t* pred, int n, int hi, int wi, int c, int ho, int wo,
+                                   float scale_h, float scale_w, int flip, int accumulate, int dtype, void* stream) {
+  if (n <= 0 || ho <= 0 || wo <= 0 || hi <= 0 || wi <= 0 || c <= 0 || c > kUpsmMaxC) return RTSDS_ERR_SHAPE;
+  if (dtype != RTSDS_F32 && dtype != RTSDS_BF16) return RTSDS_ERR_UNSUPPORTED;
+  if (x == nullptr || acc == nullptr || ((uintptr_t)acc & 3)) return RTSDS_ERR_UNSUPPORTED;
+  const int tiles = rt_cdiv(wo, kUpsmPix);
+  const long blocks = (long)n * ho * tiles;
+  if (blocks > INT_MAX) return RTSDS_ERR_UNSUPPORTED;
+  const size_t taps = (size_t)2 * upsm_fwd_cols(wi, wo, scale_w) * c * sizeof(float);
+  // the fp32 tile + up to 3 floats of phase behind the (16-B rounded) staged rows
+  const size_t tileb = 16 + (size_t)kUpsmPix * c * sizeof(float);
+  const bool staged = taps + 16 + tileb <= (size_t)64 * 1024;
+  const size_t lds = (staged ? taps + 16 : 0) + tileb;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_T(dtype, {
+    if (staged && c == 19)
+      hipLaunchKernelGGL((upsoftmax_acc_kernel<T, true, 19>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)x, acc, pred,
+                         hi, wi, c, ho, wo, scale_h, scale_w, flip, accumulate, tiles);
+    else if (staged)
+      hipLaunchKernelGGL((upsoftmax_acc_kernel<T, true, 0>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)x, acc, pred,
+                         hi, wi, c, ho, wo, scale_h, scale_w, flip, accumulate, tiles);
+    else
+      hipLaunchKernelGGL((upsoftmax_acc_kernel<T, false, 0>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)x, acc, pred,
+                         hi, wi, c, ho, wo, scale_h, scale_w, flip, accumulate, tiles);
   });
   RET_LAUNCH();
 }

@@ -1488,6 +1488,30 @@ def upsample_softmax(x, geo):
     return y
 
 
+def upsample_softmax_accumulate(x, geo, acc, flip=False, accumulate=True, pred=None):
+    """One pass of multi-scale / flip evaluation (rtsds_upsoftmax_acc): the fp32 probabilities
+    softmax(interpolate_bilinear(x, geo), dim=1) are stored into (``accumulate=False``) or added
+    onto the fp32 NHWC sum ``acc`` [n, ho, wo, c]; ``flip`` stores them mirrored along W (the
+    prediction of a mirrored image, un-mirrored).  ``pred`` (int64 [n, ho, wo]) receives the
+    argmax of the updated sum.  Inference only (no autograd node).  Returns ``acc``."""
+    require_hip(x)
+    x = nhwc(x.detach())
+    n, c, hi, wi = x.shape
+    ho, wo, sh, sw = geo
+    if not acc.is_cuda or acc.device != x.device:
+        raise RuntimeError("rtsds_amd: upsample_softmax_accumulate: acc must be on the input's HIP device")
+    if acc.dtype != torch.float32 or tuple(acc.shape) != (n, ho, wo, c) or not acc.is_contiguous():
+        raise RuntimeError(f"rtsds_amd: upsample_softmax_accumulate: acc must be contiguous fp32 {(n, ho, wo, c)}, "
+                           f"got {acc.dtype} {tuple(acc.shape)}")
+    if pred is not None and (pred.dtype != torch.int64 or tuple(pred.shape) != (n, ho, wo) or not pred.is_contiguous()
+                             or pred.device != x.device):
+        raise RuntimeError(f"rtsds_amd: upsample_softmax_accumulate: pred must be contiguous int64 {(n, ho, wo)} "
+                           f"on the input's device, got {pred.dtype} {tuple(pred.shape)}")
+    lib.rtsds_upsoftmax_acc(_P(x), _P(acc), _P(pred), n, hi, wi, c, ho, wo, sh, sw, int(bool(flip)),
+                            int(bool(accumulate)), dcode(x), stream())
+    return acc
+
+
 class BCEWithLogitsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, target):

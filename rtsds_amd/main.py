@@ -212,7 +212,7 @@ def main(argv=None):
                   max_iter=max_iter, callbacks=callbacks, device=config.device)
             val(epoch=epoch, model=model, val_loader=val_dl, num_classes=t["num_classes"],
                 class_names=config.meta["class_names"], detailed_report=True, device=config.device,
-                callbacks=callbacks)
+                callbacks=callbacks, scales=t.get("eval_scales"), flip=bool(t.get("eval_flip", False)))
 
 
 if __name__ == "__main__":
