@@ -936,7 +936,7 @@ extern "C" int rtsds_bn_fwd_ld(const void* x, const void* res, void* y, long ldy
     if (c % 4 == 0) bn_fwd_launch<float, 4>(x, res, y, rows, c, gamma, beta, running_mean, running_var, save_mean, save_invstd, momentum, eps, training, act, stats_part, stats_nrb, nbt, w, st, ldy);
     else bn_fwd_launch<float, 1>(x, res, y, rows, c, gamma, beta, running_mean, running_var, save_mean, save_invstd, momentum, eps, training, act, stats_part, stats_nrb, nbt, w, st, ldy);
   } else return RTSDS_ERR_UNSUPPORTED;
-  return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH;
+  RET_LAUNCH();
 }
 
 extern "C" int rtsds_bn_fwd(const void* x, const void* res, void* y, long rows, int c, const float* gamma, const float* beta,
@@ -1037,7 +1037,7 @@ extern "C" int rtsds_bn_bwd_part(const void* dy, const void* x, void* dx, float*
   if (!(act == RTSDS_ACT_NONE || act == RTSDS_ACT_RELU || act == RTSDS_ACT_LEAKY)) return RTSDS_ERR_UNSUPPORTED;
   bn_bwd_launch<bf16, 8>(dy, x, nullptr, dx, nullptr, dgamma, dbeta, rows, c, gamma, beta, save_mean, save_invstd, training, act,
                          accumulate_params, bn_ws(ws, rows, c), (hipStream_t)stream, part, nrb);
-  return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH;
+  RET_LAUNCH();
 }
 
 extern "C" int rtsds_bn_bwd_ld(const void* dy, long ldy, const void* x, const void* y, void* dx, void* dres, float* dgamma,
@@ -1058,7 +1058,7 @@ extern "C" int rtsds_bn_bwd_ld(const void* dy, long ldy, const void* x, const vo
     if (c % 4 == 0) bn_bwd_launch<float, 4>(dy, x, y, dx, dres, dgamma, dbeta, rows, c, gamma, beta, save_mean, save_invstd, training, act, accumulate_params, w, st, nullptr, 0, ldy);
     else bn_bwd_launch<float, 1>(dy, x, y, dx, dres, dgamma, dbeta, rows, c, gamma, beta, save_mean, save_invstd, training, act, accumulate_params, w, st, nullptr, 0, ldy);
   } else return RTSDS_ERR_UNSUPPORTED;
-  return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH;
+  RET_LAUNCH();
 }
 extern "C" int rtsds_bn_bwd(const void* dy, const void* x, const void* y, void* dx, void* dres, float* dgamma, float* dbeta,
                             long rows, int c, const float* gamma, const float* beta, const float* save_mean,
@@ -1163,7 +1163,7 @@ extern "C" int rtsds_bn_relu_maxpool_fwd(const void* x, void* y, uint8_t* idx, i
   hipLaunchKernelGGL(bn_relu_pool_fwd_kernel<bf16>, dim3(blocks), dim3(256), 0, st, (const bf16*)x, (const float*)scale,
                      (const float*)shift, (bf16*)y, idx, h, w, c, ho, wo, p, total, fastdiv_make(c / 8), fastdiv_make(wo),
                      fastdiv_make(ho));
-  return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH;
+  RET_LAUNCH();
 }
 extern "C" int rtsds_bn_relu_maxpool_bwd(const void* dy_pool, const uint8_t* idx, const void* x, void* dx, float* dgamma,
                                          float* dbeta, int n, int h, int w, int c, int ho, int wo, int p, const float* gamma,
@@ -1175,7 +1175,7 @@ extern "C" int rtsds_bn_relu_maxpool_bwd(const void* dy_pool, const uint8_t* idx
   const GradPool<bf16> gs{(const bf16*)dy_pool, idx, c, h, w, ho, wo, p, fastdiv_make(w), fastdiv_make(h)};
   bn_bwd_launch<bf16, 8, GradPool<bf16>>(gs, x, nullptr, dx, nullptr, dgamma, dbeta, rows, c, gamma, beta, save_mean, save_invstd,
                                          training, RTSDS_ACT_RELU, accumulate_params, bn_ws(ws, rows, c), (hipStream_t)stream);
-  return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH;
+  RET_LAUNCH();
 }
 
 // Eval-mode BatchNorm folded into the producing conv (rtsds_conv2d_fwd_bn):
@@ -1198,5 +1198,5 @@ extern "C" int rtsds_bn_fold(const float* gamma, const float* beta, const float*
   if (!running_mean || !running_var || !scale || !shift) return RTSDS_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(bn_fold_kernel, dim3(rt_cdiv(c, 256)), dim3(256), 0, (hipStream_t)stream, gamma, beta, running_mean,
                      running_var, conv_bias, eps, c, scale, shift);
-  return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH;
+  RET_LAUNCH();
 }

@@ -1,0 +1,724 @@
+// Channel-vector kernels (gfx950): global average pool and the ARM / FFM channel attention
+// (chan_* reductions, ffm_head_eval), then the per-pixel class-vector ops -- channel softmax,
+// cross-entropy with ignore_index, BCE-with-logits, argmax / pixel accuracy, confusion.
+#include "ew_common.h"
+
+// ------------------------------------------------------------------ global average pool
+// y[img][c] = mean_hw x[img][hw][c]   (AdaptiveAvgPool2d(1) / torch.mean over H,W:
+// build_bisenet.py:46,75, build_contextpath.py:27-28, model.py:63,82).
+//
+// Shared per-image channel reduction: out[img][c] = scale * sum_hw a (* b if DOT), in two
+// deterministic stages.  Stage 1: grid (S row slices, img, channel chunk) of 256-thread blocks
+// laid out [row group][16-B channel vector] (VEC = 8 bf16 / 4 f32 when c allows, else 1) ->
+// part[img][s][c] fp32.  Stage 2 sums the S slices in order.  (One block per image would
+// leave all but n CUs idle: the ARM / FFM / tail pools have n = 8 images.)
+static int chan_slices(int n, long hw) {
+  return (int)std::max<long>(1, std::min<long>(hw / 32, std::max(1, 1024 / std::max(1, n))));
+}
+template <typename T, int VEC, bool DOT>
+__global__ void __launch_bounds__(256) chan_part_kernel(const T* __restrict__ a, const T* __restrict__ b, float* __restrict__ part,
+                                                        long hw, int c) {
+  __shared__ float red[256 * VEC];
+  const int s = blockIdx.x, S = gridDim.x, img = blockIdx.y;
+  const int cbase = blockIdx.z * 256 * VEC;
+  const int cl = min(c - cbase, 256 * VEC);
+  const int tpr = (cl + VEC - 1) / VEC, rpi = 256 / tpr;
+  const int tid = threadIdx.x, cv = tid % tpr, rg = tid / tpr;
+  const int ch0 = cbase + cv * VEC;
+  const long per = (hw + S - 1) / S, r0 = s * per, r1 = min(hw, r0 + per);
+  float acc[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
+  if (rg < rpi) {
+    const long base = (long)img * hw * c + ch0;
+    long r = r0 + rg;
+    for (; r + rpi < r1; r += 2 * rpi) {  // two rows in flight
+      const long o0 = base + r * c, o1 = o0 + (long)rpi * c;
+      if (VEC > 1) {
+        typedef typename VecT<T>::v16 V16;
+        const V16 a0 = *(const V16*)(a + o0), a1 = *(const V16*)(a + o1);
+        if (DOT) {
+          const V16 b0 = *(const V16*)(b + o0), b1 = *(const V16*)(b + o1);
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) acc[j] = fmaf(to_f(a1[j]), to_f(b1[j]), fmaf(to_f(a0[j]), to_f(b0[j]), acc[j]));
+        } else {
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) acc[j] += to_f(a0[j]) + to_f(a1[j]);
+        }
+      } else {
+        acc[0] = DOT ? fmaf(to_f(a[o1]), to_f(b[o1]), fmaf(to_f(a[o0]), to_f(b[o0]), acc[0])) : acc[0] + (to_f(a[o0]) + to_f(a[o1]));
+      }
+    }
+    for (; r < r1; r += rpi) {
+      const long o = base + r * c;
+      if (VEC > 1) {
+        typedef typename VecT<T>::v16 V16;
+        const V16 va = *(const V16*)(a + o);
+        if (DOT) {
+          const V16 vb = *(const V16*)(b + o);
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) acc[j] = fmaf(to_f(va[j]), to_f(vb[j]), acc[j]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) acc[j] += to_f(va[j]);
+        }
+      } else {
+        acc[0] = DOT ? fmaf(to_f(a[o]), to_f(b[o]), acc[0]) : acc[0] + to_f(a[o]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) red[tid * VEC + j] = acc[j];
+  __syncthreads();
+  if (rg == 0 && cv * VEC < cl) {
+    for (int g = 1; g < rpi; ++g)
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) acc[j] += red[(g * tpr + cv) * VEC + j];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+      if (ch0 + j < c) part[((long)img * S + s) * c + ch0 + j] = acc[j];
+  }
+}
+template <typename T>
+__global__ void __launch_bounds__(256) chan_final_kernel(const float* __restrict__ part, T* __restrict__ out, int S, int c, float scale) {
+  const int img = blockIdx.y, ch = blockIdx.x * 256 + threadIdx.x;
+  if (ch >= c) return;
+  const float* p = part + (long)img * S * c + ch;
+  float s = 0.f;
+  int q = 0;
+  for (; q + 8 <= S; q += 8) {  // 8 slices in flight, summed in order
+    float t[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t[u] = p[(long)(q + u) * c];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += t[u];
+  }
+  for (; q < S; ++q) s += p[(long)q * c];
+  out[(long)img * c + ch] = from_f<T>(s * scale);
+}
+extern "C" size_t rtsds_gap_workspace(int n, long hw, int c) {
+  if (n <= 0 || hw <= 0 || c <= 0) return 256;
+  return (size_t)n * chan_slices(n, hw) * c * 4 + 256;
+}
+template <typename T, bool DOT>
+static void chan_reduce(const T* a, const T* b, T* out, int n, long hw, int c, float scale, float* part, hipStream_t st) {
+  constexpr int V = VecT<T>::N;
+  const int S = chan_slices(n, hw);
+  if (c % V == 0)
+    hipLaunchKernelGGL((chan_part_kernel<T, V, DOT>), dim3(S, n, rt_cdiv(c, 256 * V)), dim3(256), 0, st, a, b, part, hw, c);
+  else
+    hipLaunchKernelGGL((chan_part_kernel<T, 1, DOT>), dim3(S, n, rt_cdiv(c, 256)), dim3(256), 0, st, a, b, part, hw, c);
+  hipLaunchKernelGGL(chan_final_kernel<T>, dim3(rt_cdiv(c, 256), n), dim3(256), 0, st, (const float*)part, out, S, c, scale);
+}
+// accum: dx += the (rounded) gradient -- the other reader's contribution already in dx
+// (functional.GradJoin), the same two roundings as autograd's separate elementwise add
+template <typename T>
+__global__ void gap_bwd_kernel(const T* __restrict__ dy, T* __restrict__ dx, int n, long hw, int c, int accum) {
+  const long total = (long)n * hw * c;
+  const float inv = 1.f / (float)hw;
+  GRID_STRIDE(i, total) {
+    const int ch = (int)(i % c);
+    const long img = i / c / hw;
+    const T g = from_f<T>(to_f(dy[img * c + ch]) * inv);
+    dx[i] = accum ? from_f<T>(to_f(dx[i]) + to_f(g)) : g;
+  }
+}
+extern "C" int rtsds_gap_fwd(const void* x, void* y, int n, long hw, int c, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  if (n <= 0 || hw <= 0 || c <= 0) return RTSDS_ERR_SHAPE;
+  if (ws_bytes < rtsds_gap_workspace(n, hw, c)) return RTSDS_ERR_WORKSPACE;
+  DISPATCH_T(dtype, (chan_reduce<T, false>((const T*)x, nullptr, (T*)y, n, hw, c, 1.f / (float)hw, (float*)ws, (hipStream_t)stream)));
+  RET_LAUNCH();
+}
+// 16-B channel vectors (c % 8 == 0, bf16): one division per 8 elements instead of two per element
+__global__ void gap_bwd_vec_kernel(const bf16* __restrict__ dy, bf16* __restrict__ dx, long pixels, long hw, int cv, int accum,
+                                   float inv) {
+  const long total = pixels * cv;
+  GRID_STRIDE(i, total) {
+    const long p = i / cv;
+    const int q = (int)(i - p * cv);
+    const long img = p / hw;
+    const bf16x8 g = *(const bf16x8*)(dy + (img * cv + q) * 8);
+    bf16x8 o;
+    if (accum) o = *(const bf16x8*)(dx + i * 8);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bf16 v = from_f<bf16>(to_f(g[j]) * inv);
+      o[j] = accum ? from_f<bf16>(to_f(o[j]) + to_f(v)) : v;
+    }
+    *(bf16x8*)(dx + i * 8) = o;
+  }
+}
+extern "C" int rtsds_gap_bwd(const void* dy, void* dx, int n, long hw, int c, int accumulate, int dtype, void* stream) {
+  if (n <= 0 || hw <= 0 || c <= 0) return RTSDS_ERR_SHAPE;
+  if (dtype == RTSDS_BF16 && c % 8 == 0) {
+    const long pixels = (long)n * hw;
+    hipLaunchKernelGGL(gap_bwd_vec_kernel, dim3(ew_blocks(pixels * (c / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16*)dy,
+                       (bf16*)dx, pixels, hw, c / 8, accumulate ? 1 : 0, 1.f / (float)hw);
+    RET_LAUNCH();
+  }
+  DISPATCH_T(dtype, hipLaunchKernelGGL(gap_bwd_kernel<T>, dim3(ew_blocks((long)n * hw * c)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (T*)dx, n, hw, c, accumulate ? 1 : 0));
+  RET_LAUNCH();
+}
+
+// ------------------------------------------------------------------ channel attention scale
+// mode 0: y = x * a[img][c]           (ARM x*sigmoid, cx2*tail: build_bisenet.py:52,149)
+// mode 1: y = x * a[img][c] + x       (FFM: build_bisenet.py:79-80)
+template <typename T>
+__global__ void chscale_fwd_kernel(const T* __restrict__ x, const T* __restrict__ a, T* __restrict__ y, int n, long hw, int c, int mode) {
+  const long total = (long)n * hw * c;
+  GRID_STRIDE(i, total) {
+    const int ch = (int)(i % c);
+    const long img = i / c / hw;
+    const float xv = to_f(x[i]), av = to_f(a[img * c + ch]);
+    y[i] = from_f<T>(mode ? fmaf(xv, av, xv) : xv * av);
+  }
+}
+template <typename T>
+__global__ void chscale_bwd_dx_kernel(const T* __restrict__ dy, const T* __restrict__ a, T* __restrict__ dx, int n, long hw, int c, int mode) {
+  const long total = (long)n * hw * c;
+  GRID_STRIDE(i, total) {
+    const int ch = (int)(i % c);
+    const long img = i / c / hw;
+    const float av = to_f(a[img * c + ch]) + (mode ? 1.f : 0.f);
+    dx[i] = from_f<T>(to_f(dy[i]) * av);
+  }
+}
+extern "C" int rtsds_chscale_fwd(const void* x, const void* a, void* y, int n, long hw, int c, int mode, int dtype, void* stream) {
+  const long total = (long)n * hw * c;
+  if (total <= 0) return RTSDS_ERR_SHAPE;
+  DISPATCH_T(dtype, hipLaunchKernelGGL(chscale_fwd_kernel<T>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)a, (T*)y, n, hw, c, mode));
+  RET_LAUNCH();
+}
+// Inference tail of the FeatureFusionModule plus BiSeNet's final 1x1 conv (build_bisenet.py:75-80,
+// 167): a = sigmoid(conv2(relu(conv1(GAP(f))))), r = f * a + f, out = conv(r) + bias, for a
+// narrow class map f [N][hw][C] (C <= 32).  Unfused these are 8 launches (two-stage GAP, two
+// pooled 1x1 convs, the channel scale, two channel pads and the padded GEMM: ~54 us at bs 8,
+// all launch-bound).  Two launches here: (1) chan_part_kernel's GAP partials over FFM_CHUNK-pixel
+// slices of each image; (2) grid (slices, N): every workgroup sums its image's partials in slice
+// order, evaluates the two pooled convs in LDS, stages its slice of pixels in LDS (coalesced 16-B
+// loads), maps each pixel in place (one pixel per thread, the C x C head weights in LDS) and writes
+// the slice back with 16-B stores.  (One launch whose 64 workgroups each re-read their whole image
+// for the GAP ran one wave per CU through the 19 x 19 per-pixel maps: 21.7 us.)  Each intermediate
+// is rounded to T where the unfused chain stores it.
+static constexpr int kFfmChunk = 256;  // pixels per slice / workgroup
+template <typename T, int C>
+__global__ void __launch_bounds__(256) ffm_head_apply_kernel(const float* __restrict__ part, const T* __restrict__ f,
+                                                             const T* __restrict__ w1, const float* __restrict__ b1,
+                                                             const T* __restrict__ w2, const float* __restrict__ b2,
+                                                             const T* __restrict__ w3, const float* __restrict__ b3,
+                                                             T* __restrict__ out, int hw) {
+  typedef typename VecT<T>::v16 V16;
+  constexpr int V = VecT<T>::N;
+  __shared__ float wl[3][C][C + 1];
+  __shared__ float gap[C], hid[C], att[C], bias3[C];
+  __shared__ __attribute__((aligned(16))) T stage[kFfmChunk * C];
+  const int tid = threadIdx.x, img = blockIdx.y, S = gridDim.x;
+  const T* fi = f + (long)img * hw * C;
+  for (int e = tid; e < C * C; e += 256) {
+    const int o = e / C, i = e - o * C;
+    wl[0][o][i] = to_f(w1[e]);
+    wl[1][o][i] = to_f(w2[e]);
+    wl[2][o][i] = to_f(w3[e]);
+  }
+  // this slice's pixels, in flight while the attention vector is formed
+  const int p0 = blockIdx.x * kFfmChunk, np = min(kFfmChunk, hw - p0);  // np % V == 0 (host: hw % V == 0)
+  const int nvec = np * C / V;
+  const V16* src = (const V16*)(fi + (long)p0 * C);
+  for (int e = tid; e < nvec; e += 256) ((V16*)stage)[e] = src[e];
+  if (tid < C) {  // GAP: the slices' partials summed in order (chan_final_kernel's order)
+    const float* pp = part + (long)img * S * C + tid;
+    float t = 0.f;
+    int q = 0;
+    for (; q + 8 <= S; q += 8) {
+      float u[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) u[k] = pp[(long)(q + k) * C];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) t += u[k];
+    }
+    for (; q < S; ++q) t += pp[(long)q * C];
+    gap[tid] = to_f(from_f<T>(t * (1.f / (float)hw)));
+    bias3[tid] = b3 ? b3[tid] : 0.f;
+  }
+  __syncthreads();
+  if (tid < C) {
+    float v = b1 ? b1[tid] : 0.f;
+    for (int i = 0; i < C; ++i) v = fmaf(wl[0][tid][i], gap[i], v);
+    hid[tid] = to_f(from_f<T>(fmaxf(v, 0.f)));
+  }
+  __syncthreads();
+  if (tid < C) {
+    float v = b2 ? b2[tid] : 0.f;
+    for (int i = 0; i < C; ++i) v = fmaf(wl[1][tid][i], hid[i], v);
+    att[tid] = to_f(from_f<T>(1.f / (1.f + expf(-v))));
+  }
+  __syncthreads();
+  for (int p = tid; p < np; p += 256) {
+    T* q = stage + p * C;
+    float r[C];
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+      const float x = to_f(q[i]);
+      r[i] = to_f(from_f<T>(fmaf(x, att[i], x)));
+    }
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+      float v = bias3[k];
+#pragma unroll
+      for (int i = 0; i < C; ++i) v = fmaf(wl[2][k][i], r[i], v);
+      q[k] = from_f<T>(v);
+    }
+  }
+  __syncthreads();
+  V16* dst = (V16*)(out + ((long)img * hw + p0) * C);
+  for (int e = tid; e < nvec; e += 256) dst[e] = ((const V16*)stage)[e];
+}
+extern "C" size_t rtsds_ffm_head_eval_workspace(int n, long hw, int c) {
+  if (n <= 0 || hw <= 0 || c <= 0) return 256;
+  return (size_t)n * ((hw + kFfmChunk - 1) / kFfmChunk) * c * 4 + 256;
+}
+extern "C" int rtsds_ffm_head_eval(const void* f, const void* w1, const float* b1, const void* w2, const float* b2,
+                                   const void* w3, const float* b3, void* out, int n, long hw, int c, int dtype, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  if (n <= 0 || n > 65535 || hw <= 0 || hw >= (1L << 31)) return RTSDS_ERR_SHAPE;
+  if (c != 19) return RTSDS_ERR_UNSUPPORTED;  // instantiated for the 19-class maps
+  const int V = dtype == RTSDS_BF16 ? 8 : 4;
+  if (hw % V) return RTSDS_ERR_UNSUPPORTED;
+  if (ws_bytes < rtsds_ffm_head_eval_workspace(n, hw, c)) return RTSDS_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int S = (int)((hw + kFfmChunk - 1) / kFfmChunk);
+  float* part = (float*)ws;
+  DISPATCH_T(dtype, {
+    hipLaunchKernelGGL((chan_part_kernel<T, 1, false>), dim3(S, n, 1), dim3(256), 0, st, (const T*)f, (const T*)nullptr, part,
+                       hw, c);
+    hipLaunchKernelGGL((ffm_head_apply_kernel<T, 19>), dim3(S, n), dim3(256), 0, st, (const float*)part, (const T*)f, (const T*)w1,
+                       b1, (const T*)w2, b2, (const T*)w3, b3, (T*)out, (int)hw);
+  });
+  RET_LAUNCH();
+}
+extern "C" int rtsds_chscale_bwd(const void* dy, const void* x, const void* a, void* dx, void* da, int n, long hw, int c, int mode,
+                                 int dtype, void* ws, size_t ws_bytes, void* stream) {
+  const long total = (long)n * hw * c;
+  if (total <= 0) return RTSDS_ERR_SHAPE;
+  if (da && ws_bytes < rtsds_gap_workspace(n, hw, c)) return RTSDS_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_T(dtype, {
+    if (dx) hipLaunchKernelGGL(chscale_bwd_dx_kernel<T>, dim3(ew_blocks(total)), dim3(256), 0, st, (const T*)dy, (const T*)a, (T*)dx, n, hw, c, mode);
+    if (da) chan_reduce<T, true>((const T*)dy, (const T*)x, (T*)da, n, hw, c, 1.f, (float*)ws, st);
+  });
+  RET_LAUNCH();
+}
+
+// Staged variants need NHWC-contiguous logits with c <= kStageMaxC.
+static const int kStageMaxC = 64;
+static inline bool stage_ok(long sn, long sc, long shw, long hw, int c) {
+  return sc == 1 && shw == c && sn == hw * c && c <= kStageMaxC;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) softmax_fwd_staged(const T* __restrict__ x, T* __restrict__ y, long total, int c) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  T* buf = (T*)smem_raw;
+  for (long p0 = (long)blockIdx.x * kStagePix; p0 < total; p0 += (long)gridDim.x * kStagePix) {
+    const int np = (int)min<long>(kStagePix, total - p0);
+    __syncthreads();
+    stage_in(x + p0 * c, buf, np * c);
+    __syncthreads();
+    if ((int)threadIdx.x < np) {
+      T* r = buf + threadIdx.x * c;
+      float m = -INFINITY;
+      for (int k = 0; k < c; ++k) m = fmaxf(m, to_f(r[k]));
+      float z = 0.f;
+      for (int k = 0; k < c; ++k) z += expf(to_f(r[k]) - m);
+      const float iz = 1.f / z;
+      for (int k = 0; k < c; ++k) r[k] = from_f<T>(expf(to_f(r[k]) - m) * iz);
+    }
+    __syncthreads();
+    stage_out(y + p0 * c, buf, np * c);
+  }
+}
+template <typename T>
+__global__ void __launch_bounds__(256) softmax_bwd_staged(const T* __restrict__ dy, const T* __restrict__ y, T* __restrict__ dx, long total, int c) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  T* bg = (T*)smem_raw;
+  T* by = bg + kStagePix * c;
+  for (long p0 = (long)blockIdx.x * kStagePix; p0 < total; p0 += (long)gridDim.x * kStagePix) {
+    const int np = (int)min<long>(kStagePix, total - p0);
+    __syncthreads();
+    stage_in(dy + p0 * c, bg, np * c);
+    stage_in(y + p0 * c, by, np * c);
+    __syncthreads();
+    if ((int)threadIdx.x < np) {
+      T* g = bg + threadIdx.x * c;
+      const T* yy = by + threadIdx.x * c;
+      float dot = 0.f;
+      for (int k = 0; k < c; ++k) dot = fmaf(to_f(g[k]), to_f(yy[k]), dot);
+      for (int k = 0; k < c; ++k) g[k] = from_f<T>(to_f(yy[k]) * (to_f(g[k]) - dot));
+    }
+    __syncthreads();
+    stage_out(dx + p0 * c, bg, np * c);
+  }
+}
+
+// ------------------------------------------------------------------ channel softmax (dim=1)
+// train.py:225,245,256.  One thread per pixel; logits addressed by (sn, sc, shw) strides so
+// NHWC and NCHW tensors both work.  Output NHWC contiguous with row pitch yld (zero-padded
+// channels c..yld-1 so a padded discriminator input can be produced directly).
+template <typename T, typename O>
+__global__ void softmax_fwd_kernel(const T* __restrict__ x, O* __restrict__ y, int n, long hw, int c, long sn, long sc, long shw, int yld) {
+  const long total = (long)n * hw;
+  GRID_STRIDE(p, total) {
+    const long img = p / hw, s = p - img * hw;
+    const T* b = x + img * sn + s * shw;
+    float m = -INFINITY;
+    for (int k = 0; k < c; ++k) m = fmaxf(m, to_f(b[k * sc]));
+    float z = 0.f;
+    for (int k = 0; k < c; ++k) z += expf(to_f(b[k * sc]) - m);
+    const float iz = 1.f / z;
+    O* o = y + p * yld;
+    for (int k = 0; k < c; ++k) o[k] = from_f<O>(expf(to_f(b[k * sc]) - m) * iz);
+    for (int k = c; k < yld; ++k) o[k] = from_f<O>(0.f);
+  }
+}
+// dx = y * (dy - sum_k dy_k y_k); dy/y have row pitch ld (>= c), dx strided like the logits.
+template <typename T, typename O>
+__global__ void softmax_bwd_kernel(const O* __restrict__ dy, const O* __restrict__ y, T* __restrict__ dx, int n, long hw, int c, int ld,
+                                   long sn, long sc, long shw) {
+  const long total = (long)n * hw;
+  GRID_STRIDE(p, total) {
+    const long img = p / hw, s = p - img * hw;
+    const O* g = dy + p * ld;
+    const O* yy = y + p * ld;
+    float dot = 0.f;
+    for (int k = 0; k < c; ++k) dot = fmaf(to_f(g[k]), to_f(yy[k]), dot);
+    T* o = dx + img * sn + s * shw;
+    for (int k = 0; k < c; ++k) o[k * sc] = from_f<T>(to_f(yy[k]) * (to_f(g[k]) - dot));
+  }
+}
+extern "C" int rtsds_softmax_fwd(const void* x, long sn, long sc, long shw, void* y, int y_ld, int n, long hw, int c, int dtype,
+                                 void* stream) {
+  if (n <= 0 || hw <= 0 || c <= 0 || y_ld < c) return RTSDS_ERR_SHAPE;
+  DISPATCH_T(dtype, {
+    if (y_ld == c && stage_ok(sn, sc, shw, hw, c))
+      hipLaunchKernelGGL(softmax_fwd_staged<T>, dim3(ew_blocks((long)n * hw, kStagePix, 4096)), dim3(256), kStagePix * c * sizeof(T),
+                         (hipStream_t)stream, (const T*)x, (T*)y, (long)n * hw, c);
+    else
+      hipLaunchKernelGGL((softmax_fwd_kernel<T, T>), dim3(ew_blocks((long)n * hw)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, hw, c, sn, sc, shw, y_ld);
+  });
+  RET_LAUNCH();
+}
+extern "C" int rtsds_softmax_bwd(const void* dy, const void* y, int ld, void* dx, long sn, long sc, long shw, int n, long hw, int c,
+                                 int dtype, void* stream) {
+  if (n <= 0 || hw <= 0 || c <= 0 || ld < c) return RTSDS_ERR_SHAPE;
+  DISPATCH_T(dtype, {
+    if (ld == c && stage_ok(sn, sc, shw, hw, c))
+      hipLaunchKernelGGL(softmax_bwd_staged<T>, dim3(ew_blocks((long)n * hw, kStagePix, 4096)), dim3(256), 2 * kStagePix * c * sizeof(T),
+                         (hipStream_t)stream, (const T*)dy, (const T*)y, (T*)dx, (long)n * hw, c);
+    else
+      hipLaunchKernelGGL((softmax_bwd_kernel<T, T>), dim3(ew_blocks((long)n * hw)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)y, (T*)dx, n, hw, c, ld, sn, sc, shw);
+  });
+  RET_LAUNCH();
+}
+
+// ------------------------------------------------------------------ cross entropy (ignore_index)
+// nn.CrossEntropyLoss(ignore_index=19) (main.py:124-130, train.py:86-92,202-204): mean over
+// non-ignored pixels of logsumexp(x) - x[t].  Two passes for the forward (per-block partial
+// (sum, count) -> final), one fused pass for the backward.
+// ws layout: [0, RB) partial sums, [RB, 2RB) partial counts, [2RB] total count.
+static const int kCeRB = 1024;
+template <typename T>
+__global__ void ce_fwd_part_kernel(const T* __restrict__ x, const int64_t* __restrict__ tgt, float* __restrict__ part, int n, long hw, int c,
+                                   long sn, long sc, long shw, int ignore) {
+  __shared__ float rs[4], rc[4];
+  const long total = (long)n * hw;
+  float ls = 0.f, lc = 0.f;
+  GRID_STRIDE(p, total) {
+    const long t = tgt[p];
+    if (t == ignore) continue;
+    const long img = p / hw, s = p - img * hw;
+    const T* b = x + img * sn + s * shw;
+    float m = -INFINITY;
+    for (int k = 0; k < c; ++k) m = fmaxf(m, to_f(b[k * sc]));
+    float z = 0.f;
+    for (int k = 0; k < c; ++k) z += expf(to_f(b[k * sc]) - m);
+    const float xt = (t >= 0 && t < c) ? to_f(b[t * sc]) : NAN;
+    ls += logf(z) + m - xt;
+    lc += 1.f;
+  }
+  ls = wave_sum(ls);
+  lc = wave_sum(lc);
+  if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = ls; rc[threadIdx.x >> 6] = lc; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = rs[0] + rs[1] + rs[2] + rs[3];
+    part[kCeRB + blockIdx.x] = rc[0] + rc[1] + rc[2] + rc[3];
+  }
+}
+__global__ void ce_fwd_final_kernel(float* __restrict__ part, int nb, float* __restrict__ loss) {
+  __shared__ float rs[4], rc[4];
+  float s = 0.f, cn = 0.f;
+  for (int i = threadIdx.x; i < nb; i += blockDim.x) { s += part[i]; cn += part[kCeRB + i]; }
+  s = wave_sum(s);
+  cn = wave_sum(cn);
+  if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = s; rc[threadIdx.x >> 6] = cn; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float S = rs[0] + rs[1] + rs[2] + rs[3], C = rc[0] + rc[1] + rc[2] + rc[3];
+    part[2 * kCeRB] = C;
+    part[2 * kCeRB + 1] = S;
+    loss[0] = S / C;
+  }
+}
+__global__ void ce_finish_kernel(const float* __restrict__ part, float* __restrict__ loss) {
+  if (threadIdx.x == 0) loss[0] = part[2 * kCeRB + 1] / part[2 * kCeRB];
+}
+template <typename T>
+__global__ void ce_bwd_kernel(const T* __restrict__ x, const int64_t* __restrict__ tgt, const float* __restrict__ gout,
+                              const float* __restrict__ count, T* __restrict__ dx, int n, long hw, int c, long sn, long sc, long shw,
+                              int ignore) {
+  const long total = (long)n * hw;
+  const float g = gout[0] / count[0];
+  GRID_STRIDE(p, total) {
+    const long t = tgt[p];
+    const long img = p / hw, s = p - img * hw;
+    const T* b = x + img * sn + s * shw;
+    T* o = dx + img * sn + s * shw;
+    if (t == ignore) {
+      for (int k = 0; k < c; ++k) o[k * sc] = from_f<T>(0.f);
+      continue;
+    }
+    float m = -INFINITY;
+    for (int k = 0; k < c; ++k) m = fmaxf(m, to_f(b[k * sc]));
+    float z = 0.f;
+    for (int k = 0; k < c; ++k) z += expf(to_f(b[k * sc]) - m);
+    const float iz = 1.f / z;
+    for (int k = 0; k < c; ++k) {
+      const float pr = expf(to_f(b[k * sc]) - m) * iz;
+      o[k * sc] = from_f<T>(g * (pr - (k == t ? 1.f : 0.f)));
+    }
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) ce_fwd_part_staged(const T* __restrict__ x, const int64_t* __restrict__ tgt, float* __restrict__ part,
+                                                          long total, int c, int ignore) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  T* buf = (T*)smem_raw;
+  __shared__ float rs[4], rc[4];
+  float ls = 0.f, lc = 0.f;
+  for (long p0 = (long)blockIdx.x * kStagePix; p0 < total; p0 += (long)gridDim.x * kStagePix) {
+    const int np = (int)min<long>(kStagePix, total - p0);
+    __syncthreads();
+    stage_in(x + p0 * c, buf, np * c);
+    __syncthreads();
+    if ((int)threadIdx.x < np) {
+      const long t = tgt[p0 + threadIdx.x];
+      if (t != ignore) {
+        const T* r = buf + threadIdx.x * c;
+        float m = -INFINITY;
+        for (int k = 0; k < c; ++k) m = fmaxf(m, to_f(r[k]));
+        float z = 0.f;
+        for (int k = 0; k < c; ++k) z += expf(to_f(r[k]) - m);
+        const float xt = (t >= 0 && t < c) ? to_f(r[t]) : NAN;
+        ls += logf(z) + m - xt;
+        lc += 1.f;
+      }
+    }
+  }
+  ls = wave_sum(ls);
+  lc = wave_sum(lc);
+  if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = ls; rc[threadIdx.x >> 6] = lc; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = rs[0] + rs[1] + rs[2] + rs[3];
+    part[kCeRB + blockIdx.x] = rc[0] + rc[1] + rc[2] + rc[3];
+  }
+}
+template <typename T>
+__global__ void __launch_bounds__(256) ce_bwd_staged(const T* __restrict__ x, const int64_t* __restrict__ tgt, const float* __restrict__ gout,
+                                                     const float* __restrict__ count, T* __restrict__ dx, long total, int c, int ignore) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  T* buf = (T*)smem_raw;
+  const float g = gout[0] / count[0];
+  for (long p0 = (long)blockIdx.x * kStagePix; p0 < total; p0 += (long)gridDim.x * kStagePix) {
+    const int np = (int)min<long>(kStagePix, total - p0);
+    __syncthreads();
+    stage_in(x + p0 * c, buf, np * c);
+    __syncthreads();
+    if ((int)threadIdx.x < np) {
+      const long t = tgt[p0 + threadIdx.x];
+      T* r = buf + threadIdx.x * c;
+      if (t == ignore) {
+        for (int k = 0; k < c; ++k) r[k] = from_f<T>(0.f);
+      } else {
+        float m = -INFINITY;
+        for (int k = 0; k < c; ++k) m = fmaxf(m, to_f(r[k]));
+        float z = 0.f;
+        for (int k = 0; k < c; ++k) z += expf(to_f(r[k]) - m);
+        const float gz = g / z;
+        for (int k = 0; k < c; ++k) r[k] = from_f<T>(gz * expf(to_f(r[k]) - m) - (k == t ? g : 0.f));
+      }
+    }
+    __syncthreads();
+    stage_out(dx + p0 * c, buf, np * c);
+  }
+}
+
+extern "C" size_t rtsds_ce_workspace(void) { return (2 * kCeRB + 64) * sizeof(float); }
+extern "C" int rtsds_ce_fwd(const void* x, long sn, long sc, long shw, const int64_t* tgt, float* loss, int n, long hw, int c,
+                            int ignore_index, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  if (n <= 0 || hw <= 0 || c <= 0) return RTSDS_ERR_SHAPE;
+  if (ws_bytes < rtsds_ce_workspace()) return RTSDS_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = std::min<int>(kCeRB, ew_blocks((long)n * hw, kStagePix, kCeRB));
+  DISPATCH_T(dtype, {
+    if (stage_ok(sn, sc, shw, hw, c))
+      hipLaunchKernelGGL(ce_fwd_part_staged<T>, dim3(nb), dim3(256), kStagePix * c * sizeof(T), st, (const T*)x, tgt, (float*)ws,
+                         (long)n * hw, c, ignore_index);
+    else
+      hipLaunchKernelGGL(ce_fwd_part_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)x, tgt, (float*)ws, n, hw, c, sn, sc, shw, ignore_index);
+  });
+  hipLaunchKernelGGL(ce_fwd_final_kernel, dim3(1), dim3(256), 0, st, (float*)ws, nb, loss);
+  RET_LAUNCH();
+}
+// loss = S / C with C summed by the caller over data-parallel ranks (ws + 2*1024 floats: C, S).
+extern "C" int rtsds_ce_finish(const void* ws, float* loss, void* stream) {
+  hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float*)ws, loss);
+  RET_LAUNCH();
+}
+// count = the valid-pixel count written by rtsds_ce_fwd into its workspace (ws + 2*1024 floats).
+extern "C" int rtsds_ce_bwd(const void* x, long sn, long sc, long shw, const int64_t* tgt, const float* grad_loss, const float* count,
+                            void* dx, int n, long hw, int c, int ignore_index, int dtype, void* stream) {
+  if (n <= 0 || hw <= 0 || c <= 0) return RTSDS_ERR_SHAPE;
+  DISPATCH_T(dtype, {
+    if (stage_ok(sn, sc, shw, hw, c))
+      hipLaunchKernelGGL(ce_bwd_staged<T>, dim3(ew_blocks((long)n * hw, kStagePix, 4096)), dim3(256), kStagePix * c * sizeof(T),
+                         (hipStream_t)stream, (const T*)x, tgt, grad_loss, count, (T*)dx, (long)n * hw, c, ignore_index);
+    else
+      hipLaunchKernelGGL(ce_bwd_kernel<T>, dim3(ew_blocks((long)n * hw)), dim3(256), 0, (hipStream_t)stream, (const T*)x, tgt, grad_loss, count, (T*)dx, n, hw, c, sn, sc, shw, ignore_index);
+  });
+  RET_LAUNCH();
+}
+
+// ------------------------------------------------------------------ BCE with logits
+// nn.BCEWithLogitsLoss() (main.py:131-132, train.py:229,247,258): mean of
+// max(x,0) - x*t + log1p(exp(-|x|)).  Tiny (one logit per image): one block.
+__global__ void bce_fwd_kernel(const float* __restrict__ x, const float* __restrict__ t, float* __restrict__ loss, int n) {
+  __shared__ float r[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const float v = x[i];
+    s += fmaxf(v, 0.f) - v * t[i] + log1pf(expf(-fabsf(v)));
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) r[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) loss[0] = (r[0] + r[1] + r[2] + r[3]) / (float)n;
+}
+__global__ void bce_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ gout, float* __restrict__ dx, int n) {
+  const float g = gout[0] / (float)n;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float s = 1.f / (1.f + expf(-x[i]));
+    dx[i] = g * (s - t[i]);
+  }
+}
+extern "C" int rtsds_bce_fwd(const float* x, const float* target, float* loss, int n, void* stream) {
+  if (n <= 0) return RTSDS_ERR_SHAPE;
+  hipLaunchKernelGGL(bce_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x, target, loss, n);
+  RET_LAUNCH();
+}
+extern "C" int rtsds_bce_bwd(const float* x, const float* target, const float* grad_loss, float* dx, int n, void* stream) {
+  if (n <= 0) return RTSDS_ERR_SHAPE;
+  hipLaunchKernelGGL(bce_bwd_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, target, grad_loss, dx, n);
+  RET_LAUNCH();
+}
+
+// ------------------------------------------------------------------ argmax / pixel accuracy
+// argmax over channels, first maximum wins (torch.argmax / max(1), train.py:102-106,272-275,
+// validation.py:51).  out_idx may be NULL; correct += #(argmax == target) (ignored pixels
+// count as wrong, exactly like the reference).
+template <typename T>
+__global__ void argmax_kernel(const T* __restrict__ x, int64_t* __restrict__ out, const int64_t* __restrict__ tgt,
+                              unsigned long long* __restrict__ correct, int n, long hw, int c, long sn, long sc, long shw) {
+  const long total = (long)n * hw;
+  unsigned long long cnt = 0;
+  GRID_STRIDE(p, total) {
+    const long img = p / hw, s = p - img * hw;
+    const T* b = x + img * sn + s * shw;
+    float best = to_f(b[0]);
+    int bi = 0;
+    for (int k = 1; k < c; ++k) {
+      const float v = to_f(b[k * sc]);
+      if (v > best || (v != v && best == best)) { best = v; bi = k; }
+    }
+    if (out) out[p] = bi;
+    if (tgt && tgt[p] == bi) ++cnt;
+  }
+  if (correct) {
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(correct, cnt);
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) argmax_staged(const T* __restrict__ x, int64_t* __restrict__ out, const int64_t* __restrict__ tgt,
+                                                     unsigned long long* __restrict__ correct, long total, int c) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  T* buf = (T*)smem_raw;
+  unsigned long long cnt = 0;
+  for (long p0 = (long)blockIdx.x * kStagePix; p0 < total; p0 += (long)gridDim.x * kStagePix) {
+    const int np = (int)min<long>(kStagePix, total - p0);
+    __syncthreads();
+    stage_in(x + p0 * c, buf, np * c);
+    __syncthreads();
+    if ((int)threadIdx.x < np) {
+      const T* r = buf + threadIdx.x * c;
+      float best = to_f(r[0]);
+      int bi = 0;
+      for (int k = 1; k < c; ++k) {
+        const float v = to_f(r[k]);
+        if (v > best || (v != v && best == best)) { best = v; bi = k; }
+      }
+      const long p = p0 + threadIdx.x;
+      if (out) out[p] = bi;
+      if (tgt && tgt[p] == bi) ++cnt;
+    }
+  }
+  if (correct) {
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(correct, cnt);
+  }
+}
+
+extern "C" int rtsds_argmax(const void* x, long sn, long sc, long shw, int64_t* out, const int64_t* target, unsigned long long* correct,
+                            int n, long hw, int c, int dtype, void* stream) {
+  if (n <= 0 || hw <= 0 || c <= 0) return RTSDS_ERR_SHAPE;
+  DISPATCH_T(dtype, {
+    if (stage_ok(sn, sc, shw, hw, c))
+      hipLaunchKernelGGL(argmax_staged<T>, dim3(ew_blocks((long)n * hw, kStagePix, 4096)), dim3(256), kStagePix * c * sizeof(T),
+                         (hipStream_t)stream, (const T*)x, out, target, correct, (long)n * hw, c);
+    else
+      hipLaunchKernelGGL(argmax_kernel<T>, dim3(ew_blocks((long)n * hw, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const T*)x, out, target, correct, n, hw, c, sn, sc, shw);
+  });
+  RET_LAUNCH();
+}
+
+// 19x19 confusion histogram (utils.fast_hist, utils.py:52-58): labels outside [0, nc) dropped.
+__global__ void confusion_kernel(const int64_t* __restrict__ label, const int64_t* __restrict__ pred, unsigned long long* __restrict__ hist,
+                                 long total, int nc) {
+  extern __shared__ unsigned int lh[];
+  for (int i = threadIdx.x; i < nc * nc; i += blockDim.x) lh[i] = 0;
+  __syncthreads();
+  GRID_STRIDE(p, total) {
+    const long a = label[p];
+    if (a >= 0 && a < nc) atomicAdd(&lh[a * nc + pred[p]], 1u);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nc * nc; i += blockDim.x)
+    if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
+}
+extern "C" int rtsds_confusion(const int64_t* label, const int64_t* pred, unsigned long long* hist, long total, int nc, void* stream) {
+  if (total <= 0 || nc <= 0 || nc > 64) return RTSDS_ERR_SHAPE;
+  hipLaunchKernelGGL(confusion_kernel, dim3(ew_blocks(total, 256, 1024)), dim3(256), nc * nc * 4, (hipStream_t)stream, label, pred, hist, total, nc);
+  RET_LAUNCH();
+}

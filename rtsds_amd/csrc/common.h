@@ -125,5 +125,13 @@ RT_DEV void buf_lds16(rsrc_t, void*, int, int) {}
   do {                                                          \
     if (hipPeekAtLastError() != hipSuccess) return RTSDS_ERR_LAUNCH; \
   } while (0)
+// End of an entry point: unlike RT_CHECK_LAUNCH this clears the runtime's last error.
+#define RET_LAUNCH() return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH
+#define DISPATCH_T(dtype, ...)                                \
+  do {                                                        \
+    if ((dtype) == RTSDS_BF16) { typedef bf16 T; __VA_ARGS__; } \
+    else if ((dtype) == RTSDS_F32) { typedef float T; __VA_ARGS__; } \
+    else return RTSDS_ERR_UNSUPPORTED;                        \
+  } while (0)
 
 static inline int rt_cdiv(long a, long b) { return (int)((a + b - 1) / b); }

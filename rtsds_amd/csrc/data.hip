@@ -152,7 +152,7 @@ extern "C" int rtsds_resize_aa(const void* src, int src_u8, int c, int h, int w,
                        wx, flip);
   hipLaunchKernelGGL(aa_v_kernel, dim3(bv), dim3(256), 0, st, tmp, dst, h, wo, c, ho, ky, ymin, ysz, wy, kind, mean, stdv,
                      clamp_lo, clamp_hi);
-  return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH;
+  RET_LAUNCH();
 }
 
 // ---- GaussianBlur: dst = conv2d(reflect_pad(src), outer(ky, kx)) per channel, HWC fp32 ----
@@ -207,7 +207,7 @@ extern "C" int rtsds_gaussian_blur(const void* src, int src_u8, float* dst, int 
   const long n = (long)h * w * c;
   hipLaunchKernelGGL(gblur_kernel, dim3((int)std::min<long>(8192, (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src,
                      src_u8, dst, h, w, c, kx, ky, sigma_x, sigma_y);
-  return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH;
+  RET_LAUNCH();
 }
 
 // ---- GTA5 RGB label -> train id (gta5.py:111-118), HWC uint8 -> int64 ----
@@ -229,5 +229,5 @@ extern "C" int rtsds_gta5_decode(const uint8_t* rgb, int64_t* out, int h, int w,
   const long n = (long)h * w;
   hipLaunchKernelGGL(gta5_decode_kernel, dim3((int)std::min<long>(8192, (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      rgb, out, n);
-  return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH;
+  RET_LAUNCH();
 }

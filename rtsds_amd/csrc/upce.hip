@@ -637,14 +637,13 @@ extern "C" int rtsds_upce_fwd(int nheads, const void* const* logits, const int64
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = upce_lds(g, nheads);
   const dim3 blk(64 * (nheads + (upce_aux(g, nheads) ? 1 : 0)));
-  if (dtype != RTSDS_BF16 && dtype != RTSDS_F32) return RTSDS_ERR_UNSUPPORTED;
   switch (upce_cp(c)) {
 #define UPCE_CASE(CPV)                                                                                      \
   case CPV:                                                                                                 \
-    if (dtype == RTSDS_BF16 && a.gcorr) hipLaunchKernelGGL((upce_fwd_kernel<bf16, CPV, true>), dim3(g.nblocks), blk, lds, st, a); \
-    else if (dtype == RTSDS_BF16) hipLaunchKernelGGL((upce_fwd_kernel<bf16, CPV, false>), dim3(g.nblocks), blk, lds, st, a);    \
-    else if (a.gcorr) hipLaunchKernelGGL((upce_fwd_kernel<float, CPV, true>), dim3(g.nblocks), blk, lds, st, a);              \
-    else hipLaunchKernelGGL((upce_fwd_kernel<float, CPV, false>), dim3(g.nblocks), blk, lds, st, a);                          \
+    DISPATCH_T(dtype, {                                                                                     \
+      if (a.gcorr) hipLaunchKernelGGL((upce_fwd_kernel<T, CPV, true>), dim3(g.nblocks), blk, lds, st, a);   \
+      else hipLaunchKernelGGL((upce_fwd_kernel<T, CPV, false>), dim3(g.nblocks), blk, lds, st, a);          \
+    });                                                                                                     \
     break;
     UPCE_CASE(4) UPCE_CASE(8) UPCE_CASE(12) UPCE_CASE(16) UPCE_CASE(20) UPCE_CASE(24) UPCE_CASE(28) UPCE_CASE(32)
 #undef UPCE_CASE
@@ -652,7 +651,7 @@ extern "C" int rtsds_upce_fwd(int nheads, const void* const* logits, const int64
   }
   hipLaunchKernelGGL(upce_final_kernel, dim3(1), dim3(256), 0, st, a.lpart, a.cpart, g.nblocks, nheads, loss, loss_sum, stat,
                      a.kpart, correct, (want_grad & RTSDS_UPCE_SET_CORRECT) ? 1 : 0);
-  return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH;
+  RET_LAUNCH();
 }
 
 extern "C" int rtsds_upce_bwd(int nheads, const float* grad_loss, int grad_stride, void* const* dlogits, int n, int hl, int wl, int c, int H, int W,
@@ -677,14 +676,12 @@ extern "C" int rtsds_upce_bwd(int nheads, const float* grad_loss, int grad_strid
   const long total = (long)nheads * n * hl * wl * c;
   const int blocks = (int)std::min<long>(8192, (total + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == RTSDS_BF16) hipLaunchKernelGGL(upce_bwd_kernel<bf16>, dim3(blocks), dim3(256), 0, st, a);
-  else if (dtype == RTSDS_F32) hipLaunchKernelGGL(upce_bwd_kernel<float>, dim3(blocks), dim3(256), 0, st, a);
-  else return RTSDS_ERR_UNSUPPORTED;
-  return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH;
+  DISPATCH_T(dtype, hipLaunchKernelGGL(upce_bwd_kernel<T>, dim3(blocks), dim3(256), 0, st, a));
+  RET_LAUNCH();
 }
 
 extern "C" int rtsds_upce_finish(int nheads, const void* ws, float* loss, float* loss_sum, void* stream) {
   if (nheads <= 0 || nheads > kUpceMaxHeads || !ws) return RTSDS_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(upce_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float*)ws, nheads, loss, loss_sum);
-  return hipGetLastError() == hipSuccess ? RTSDS_OK : RTSDS_ERR_LAUNCH;
+  RET_LAUNCH();
 }

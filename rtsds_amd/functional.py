@@ -425,8 +425,7 @@ def conv_bn_eval(x, weight, bias, wq, stride, padding, dilation, gamma, beta, ru
     ws = workspace(lib.rtsds_conv2d_fwd_workspace(ctypes.byref(d)), x.device)
     if out is not None and residual is None:
         buf, off = out
-        if tuple(buf.shape[2:]) == (d.ho, d.wo) and buf.shape[0] == d.n and buf.dtype == x.dtype and \
-                0 <= off and off + k <= buf.shape[1] and buf.stride(1) == 1 and buf.stride(3) == buf.shape[1]:
+        if _slice_target(buf, off, (d.n, k, d.ho, d.wo), x.dtype):  # the kernel route checks the 16-B chunks
             try:
                 with _Timed(d, "fwd"):
                     lib.rtsds_conv2d_fwd_bn_ld(ctypes.byref(d), _P(x), _P(wq), _P(ss), ss.data_ptr() + 4 * k,
@@ -571,7 +570,8 @@ class BatchNormFn(torch.autograd.Function):
         rows = n * h * w
         keep_y = res is not None or act == ACT_SIGMOID
         ld = c
-        if out is not None and not keep_y and x.dtype == torch.bfloat16 and c % 8 == 0 and out[0].shape[1] % 8 == 0:
+        if out is not None and not keep_y and x.dtype == torch.bfloat16 and \
+                _slice_target(out[0], out[1], x.shape, x.dtype, vec16=True):
             # y written straight into channels [off, off + c) of out's NHWC buffer (a view)
             buf, off = out
             ld = buf.shape[1]
@@ -637,15 +637,41 @@ class BatchNormFn(torch.autograd.Function):
         return dx, dg, db, dres, None, None, None, None, None, None, None, None, None, None, None, None
 
 
+def _nhwc_pitch(t):
+    """Channel pitch of a 4-D [N, C, H, W] tensor or view stored NHWC with dense rows and images
+    (its C channels may be a slice of a wider pixel), else 0."""
+    n, c, h, w = t.shape
+    ld = t.stride(3)
+    if t.stride(1) != 1 or ld < c or (h > 1 and t.stride(2) != w * ld) or (n > 1 and t.stride(0) != h * w * ld):
+        return 0
+    return ld
+
+
+def _slice_target(buf, off, shape, dtype, vec16=False):
+    """Whether channels [off, off + c) of ``buf`` can take an [n, c, h, w] = ``shape`` result of
+    ``dtype`` through a pitched NHWC store: same n, h, w and dtype, the slice inside buf's
+    channels, buf dense NHWC.  ``vec16``: the kernel stores 16-byte vectors, so off, c and the
+    pitch are multiples of the vector and the slice starts 16-byte aligned."""
+    n, c, h, w = shape
+    if buf.dim() != 4 or buf.dtype != dtype or (buf.shape[0], buf.shape[2], buf.shape[3]) != (n, h, w):
+        return False
+    ld = buf.shape[1]
+    if off < 0 or off + c > ld or _nhwc_pitch(buf) != ld:
+        return False
+    if vec16:
+        vec = 16 // buf.element_size()
+        if off % vec or c % vec or ld % vec or (buf.data_ptr() + off * buf.element_size()) % 16:
+            return False
+    return True
+
+
 def _channel_slice_pitch(t):
     """Row pitch of a bf16 [N, C, H, W] view that is a channel slice of a wider NHWC buffer
     (C % 8 == 0, pitch % 8 == 0, pitch > C), else 0."""
     if t.dim() != 4 or t.dtype != torch.bfloat16:
         return 0
-    n, c, h, w = t.shape
-    ld = t.stride(3)
-    if c % 8 or ld % 8 or ld <= c or t.stride(1) != 1 or t.stride(2) != w * ld or (n > 1 and t.stride(0) != h * w * ld) \
-            or t.data_ptr() % 16:
+    ld = _nhwc_pitch(t)
+    if ld <= t.shape[1] or t.shape[1] % 8 or ld % 8 or t.data_ptr() % 16:
         return 0
     return ld
 
@@ -848,9 +874,6 @@ def concat_resized_scaled_eval(x0, parts, size, into=None):
     geometry is outside the fused kernel (the caller then runs the separate ops).  ``into``: the
     preallocated output; x0 is not copied when it already is its leading channel slice (the
     spatial path's conv wrote it there, conv_bn_eval(out=...))."""
-    in_place = into is not None and x0.data_ptr() == into.data_ptr() and x0.stride() == into.stride()
-    if not in_place:
-        x0 = nhwc(x0)
     n, c0, h, w = x0.shape
     ps = []
     for x, scales in parts:
@@ -860,10 +883,13 @@ def concat_resized_scaled_eval(x0, parts, size, into=None):
         ss = [(s if s.dtype == x.dtype else cast(s, x.dtype)).contiguous() for s in scales]
         ps.append((x, ss + [None] * (2 - len(ss))))
     ct = c0 + sum(x.shape[1] for x, _ in ps)
-    if into is not None and tuple(into.shape) == (n, ct, h, w) and into.dtype == x0.dtype:
+    if into is not None and _slice_target(into, 0, (n, ct, h, w), x0.dtype) and into.shape[1] == ct:
         y = into
+        in_place = x0.data_ptr() == into.data_ptr() and x0.stride() == into.stride()
     else:
         y, in_place = empty_nhwc(n, ct, h, w, x0.dtype, x0.device), False
+    if not in_place:
+        x0 = nhwc(x0)
     off = c0
     for x, (s1, s2) in ps:
         _, c, hi, wi = x.shape

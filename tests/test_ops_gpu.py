@@ -345,6 +345,123 @@ def test_batchnorm_channel_slice_bit_identical(shape, ld, off):
         assert torch.equal(a, b_), what
 
 
+_SENTINEL = 7.0
+BAD_TARGETS = ("fp32", "h_plus_1", "off_4", "off_past_end", "nchw")
+
+
+def _carved_target(kind, shape, ct, off):
+    """(arena, buf, off) for a result of bf16 ``shape``: ``buf`` -- a [n, ct, h, w] NHWC view unless
+    ``kind`` says otherwise -- lies inside ``arena``, a larger sentinel-filled allocation, so a
+    store through a target the guard should have refused lands in memory the test owns."""
+    n, c, h, w = shape
+    dt = torch.float32 if kind == "fp32" else torch.bfloat16
+    hb = h + 1 if kind == "h_plus_1" else h
+    numel, lead = n * ct * hb * w, 256  # lead: the view stays 16-byte aligned
+    arena = torch.full((lead + numel + 4096,), _SENTINEL, device=DEV, dtype=dt)
+    flat = arena[lead:lead + numel]
+    buf = flat.view(n, ct, hb, w) if kind == "nchw" else flat.view(n, hb, w, ct).permute(0, 3, 1, 2)
+    return arena, buf, {"off_4": 4, "off_past_end": ct}.get(kind, off)
+
+
+def _inside(t, arena):
+    return arena.data_ptr() <= t.data_ptr() < arena.data_ptr() + arena.numel() * arena.element_size()
+
+
+def test_batchnorm_out_guard():
+    """batch_norm(out=(buf, off)) stores 16-byte vectors through the slice, so a target of the
+    wrong dtype, spatial size, offset or layout must fall back to a plain y: nothing of the
+    allocation around ``buf`` is written, y and the running statistics are bit-identical to the
+    call without out=.  The valid target takes the in-place route."""
+    shape, ct, off = (1, 8, 3, 5), 24, 8
+    c = shape[1]
+    g = torch.Generator().manual_seed(3)
+    x = _dev(torch.randn(shape, generator=g) * 2 + 3, torch.bfloat16)
+    gam, bet = (1 + 0.1 * torch.randn(c, generator=g)).to(DEV), (0.1 * torch.randn(c, generator=g)).to(DEV)
+
+    def run(out):
+        rm, rv = torch.zeros(c, device=DEV), torch.ones(c, device=DEV)
+        with torch.no_grad():
+            y = F.batch_norm(x, gam, bet, rm, rv, True, 0.1, 1e-5, 1, None, out=out)
+        torch.cuda.synchronize()
+        return y, rm, rv
+
+    y0, rm0, rv0 = run(None)
+    for kind in BAD_TARGETS:
+        arena, buf, o = _carved_target(kind, shape, ct, off)
+        y, rm, rv = run((buf, o))
+        assert not _inside(y, arena), kind
+        assert torch.equal(arena, torch.full_like(arena, _SENTINEL)), kind
+        assert torch.equal(y, y0) and torch.equal(rm, rm0) and torch.equal(rv, rv0), kind
+    arena, buf, o = _carved_target("valid", shape, ct, off)
+    y, rm, rv = run((buf, o))
+    assert y.data_ptr() == buf.data_ptr() + 2 * off and y.stride(3) == ct and y.shape == y0.shape
+    assert torch.equal(y, y0) and torch.equal(rm, rm0) and torch.equal(rv, rv0)
+    keep = torch.ones(ct, dtype=torch.bool, device=DEV)
+    keep[off:off + c] = False
+    assert torch.equal(buf[:, keep], torch.full_like(buf[:, keep], _SENTINEL))
+    buf[:, off:off + c] = _SENTINEL
+    assert torch.equal(arena, torch.full_like(arena, _SENTINEL))
+
+
+@pytest.mark.parametrize("kind", BAD_TARGETS)
+def test_conv_bn_eval_out_guard(kind):
+    """conv_bn_eval(out=(buf, off)) refuses the targets batch_norm(out=) refuses (the smallest
+    geometry of test_conv_bn_eval_into_slice, bf16): a plain y equal to the call without out=,
+    the allocation around ``buf`` untouched."""
+    n, c, h, w, k, kh, s, p, ct, off = (1, 32, 9, 13, 32, 3, 2, 1, 40, 8)
+    g = torch.Generator().manual_seed(12)
+    x = _dev(torch.randn(n, c, h, w, generator=g), torch.bfloat16)
+    wt = (torch.randn(k, c, kh, kh, generator=g) / (c * kh * kh) ** 0.5).to(DEV).contiguous(memory_format=CL)
+    rm, rv = torch.randn(k, generator=g).to(DEV), (0.5 + torch.rand(k, generator=g)).to(DEV)
+    gam, bet = torch.randn(k, generator=g).to(DEV), torch.randn(k, generator=g).to(DEV)
+    args = (wt, None, _shadow(wt, torch.bfloat16), (s, s), (p, p), (1, 1), gam, bet, rm, rv, 1e-5, 1)
+    with torch.no_grad():
+        ref = F.conv_bn_eval(x, *args)
+        arena, buf, o = _carved_target(kind, tuple(ref.shape), ct, off)
+        got = F.conv_bn_eval(x, *args, out=(buf, o))
+    torch.cuda.synchronize()
+    assert not _inside(got, arena)
+    assert torch.equal(arena, torch.full_like(arena, _SENTINEL))
+    assert torch.equal(got, ref)
+
+
+@pytest.mark.parametrize("mode,dt", [("train", torch.bfloat16), ("eval", torch.bfloat16), ("eval", torch.float32)])
+def test_bisenet_spatial_path_in_concat(mode, dt, monkeypatch):
+    """BiSeNet's spatial path writes its result straight into the leading channels of the
+    fusion module's concatenated input (batch_norm out= in training, conv_bn_eval out= in
+    inference), and the concat takes that buffer without a copy."""
+    import rtsds_amd
+    from rtsds_amd.models.bisenet import build_bisenet as bb
+    seen = []
+
+    def spy(name):
+        real = getattr(F, name)
+
+        def f(x0, *a, **kw):
+            y = real(x0, *a, **kw)
+            seen.append((x0, kw.get("into"), y))
+            return y
+        monkeypatch.setattr(bb.F, name, f)
+
+    spy("concat_resized")
+    spy("concat_resized_scaled_eval")
+    torch.manual_seed(0)
+    with rtsds_amd.precision(dt):
+        net = bb.BiSeNet(19, "resnet18").to(DEV)
+        x = torch.randn(2, 3, 64, 128, device=DEV)
+        if mode == "train":
+            net.train()(x)
+        else:
+            with torch.no_grad():
+                net.eval()(x)
+    torch.cuda.synchronize()
+    assert len(seen) == 1
+    x0, into, cat = seen[0]
+    assert into is not None and cat is not None
+    assert x0.data_ptr() == into.data_ptr() == cat.data_ptr()
+    assert x0.stride() == into.stride() and x0.shape[1] < into.shape[1] and cat.shape == into.shape
+
+
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 def test_batchnorm_eval(dt):
     g = torch.Generator().manual_seed(5)

@@ -28,6 +28,10 @@ for unit in "$@"; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-variable -c $src/$unit.hip -o $out/$unit.o &
 done
 wait
-for f in rtsds_amd/csrc/build/*.o; do [ -e $out/$(basename $f) ] || cp $f $out/; done
+# a revision's ew unit is today's layout + pool + chan + resize + optim
+[[ "$units" == *" ew "* ]] && split=" layout pool chan resize optim " || split=""
+for f in rtsds_amd/csrc/build/*.o; do
+  b=$(basename $f .o); [ -e $out/$b.o ] || [[ "$split" == *" $b "* ]] || cp $f $out/
+done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o rtsds_amd/var_$name.so $out/*.o
 echo built rtsds_amd/var_$name.so: "$@" from $rev

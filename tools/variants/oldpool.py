@@ -4,5 +4,5 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from textvariant import build  # noqa: E402
 
-build("oldpool", {"ew.hip": [("if (c % VecT<T>::N == 0 && k == 3 && s == 2 && (p == 0 || p == 1) && total < (1L << 31)) {",
-                              "if (false) {")]}, ["ew"])
+build("oldpool", {"pool.hip": [("if (c % VecT<T>::N == 0 && k == 3 && s == 2 && (p == 0 || p == 1) && total < (1L << 31)) {",
+                                "if (false) {")]}, ["pool"])

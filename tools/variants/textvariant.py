@@ -3,7 +3,7 @@ scratch directory, apply exact-match edits, recompile the named units and link t
 main build's other objects into rtsds_amd/var_NAME.so (same ABI revision as the tree).
 
     from textvariant import build
-    build("u2", {"ew.hip": [(old, new), ...]}, units=["ew"])
+    build("u2", {"resize.hip": [(old, new), ...]}, units=["resize"])
 """
 import os
 import shutil
