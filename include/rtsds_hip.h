@@ -429,6 +429,29 @@ int rtsds_upsoftmax_acc(const void* x, float* acc, int64_t* pred, int n, int hi,
                         int ho, int wo, float scale_h, float scale_w, int flip, int accumulate,
                         int dtype, void* stream);
 
+/* ---------------------------------------------------------------- pseudo-labels (self-training)
+ * No counterpart in the reference (it never trains on target pixels).  Class-balanced
+ * self-training keeps, per class, the most confident share of the pixels predicted as that
+ * class; the two entries below turn the fp32 probability sum rtsds_upsoftmax_acc leaves into
+ * such labels without a host round trip per pixel.
+ * rtsds_conf_hist: acc = total pixels x c contiguous fp32.  Per pixel k = argmax over classes
+ *   (first maximum wins, NaN handled as rtsds_argmax does), conf = acc[k] * inv (one fp32
+ *   multiply; inv = 1 / number of summed passes), b = floor(conf * bins) clamped to
+ *   [0, bins - 1] (a conf that is not > 0: bin 0).  hist[k * bins + b] += 1 -- hist (uint64
+ *   [c][bins]) is ADDED to, never cleared, so it accumulates over batches; pred[p] = k (uint8)
+ *   and cbin[p] = b (uint16), each may be NULL.  2 <= c <= 32; bins a power of two in
+ *   [16, 1024] (conf * bins is then exact: the bin is reproducible on the host bit for bit) with
+ *   c * (bins + 512) * 4 <= 160 KiB (the workgroup-private histogram plus a 512-pixel tile in
+ *   LDS; RTSDS_ERR_UNSUPPORTED otherwise, e.g. c = 32 with bins = 1024).  Integer atomics only:
+ *   deterministic.
+ * rtsds_pseudo_select: out[p] (int64) = pred[p] if cbin[p] >= tbin[pred[p]] else ignore_index;
+ *   tbin = c device ints (a value >= bins keeps nothing of that class).
+ * Neither synchronises, allocates or touches the host (graph-capture safe).               */
+int rtsds_conf_hist(const float* acc, unsigned long long* hist, uint8_t* pred, uint16_t* cbin,
+                    long total, int c, int bins, float inv, void* stream);
+int rtsds_pseudo_select(const uint8_t* pred, const uint16_t* cbin, const int* tbin, int64_t* out,
+                        long total, int c, int ignore_index, void* stream);
+
 /* ---------------------------------------------------------------- input pipeline
  * The reference's per-sample torchvision transforms (main.py:60-108; datasets/cityscapes.py:
  * 56-68, datasets/gta5.py:69-118) on a decoded HWC image in device memory.
@@ -492,7 +515,7 @@ int rtsds_pooled_mlp_fwd(const void* p, const void* w1, const float* b1, const v
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 11
+#define RTSDS_ABI_VERSION 12
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

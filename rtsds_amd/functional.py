@@ -1538,6 +1538,70 @@ def upsample_softmax_accumulate(x, geo, acc, flip=False, accumulate=True, pred=N
     return acc
 
 
+def _pseudo_arg(fn, name, t, dtype, shape, device):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
+        raise RuntimeError(f"rtsds_amd: {fn}: {name} must be contiguous {dtype} {tuple(shape)} on {device}, "
+                           f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def confidence_histogram(acc, hist, passes=1, pred=None, cbin=None):
+    """Per-class confidence histogram of a probability sum (rtsds_conf_hist).  ``acc``: fp32
+    [n, H, W, c] as predict_multiscale / upsample_softmax_accumulate leave it, summed over
+    ``passes`` passes.  Per pixel: k = argmax over classes (first maximum wins), conf =
+    acc[k] * float32(1 / passes), b = floor(conf * bins) clamped to [0, bins - 1].  ``hist``
+    (int64 [c, bins], bins a power of two in [16, 1024]) is ADDED to: it accumulates over
+    batches.  ``pred`` (uint8 [n, H, W]) receives k, ``cbin`` (uint16 [n, H, W]) receives b;
+    either may be None.  No host sync.  Returns ``hist``."""
+    fn = "confidence_histogram"
+    if not (acc.is_cuda and hist.is_cuda):
+        raise RuntimeError(f"rtsds_amd: {fn}: acc and hist must be HIP tensors; there is no CPU fallback")
+    if acc.dim() != 4 or acc.dtype != torch.float32 or not acc.is_contiguous():
+        raise RuntimeError(f"rtsds_amd: {fn}: acc must be contiguous fp32 [n, H, W, c], got {acc.dtype} "
+                           f"{tuple(acc.shape)}")
+    n, h, w, c = acc.shape
+    if acc.numel() == 0 or not 2 <= c <= 32:
+        raise RuntimeError(f"rtsds_amd: {fn}: acc needs pixels and 2..32 classes, got {tuple(acc.shape)}")
+    if hist.dim() != 2 or hist.shape[0] != c:
+        raise RuntimeError(f"rtsds_amd: {fn}: hist must be int64 [{c}, bins], got {tuple(hist.shape)}")
+    bins = int(hist.shape[1])
+    if bins < 16 or bins > 1024 or bins & (bins - 1):
+        raise RuntimeError(f"rtsds_amd: {fn}: bins must be a power of two in [16, 1024], got {bins}")
+    _pseudo_arg(fn, "hist", hist, torch.int64, (c, bins), acc.device)
+    if pred is not None:
+        _pseudo_arg(fn, "pred", pred, torch.uint8, (n, h, w), acc.device)
+    if cbin is not None:
+        _pseudo_arg(fn, "cbin", cbin, torch.uint16, (n, h, w), acc.device)
+    if int(passes) != passes or passes < 1:
+        raise RuntimeError(f"rtsds_amd: {fn}: passes must be a positive integer, got {passes}")
+    inv = float(np.float32(1.0) / np.float32(int(passes)))
+    lib.rtsds_conf_hist(_P(acc), _P(hist), _P(pred), _P(cbin), n * h * w, c, bins, inv, stream())
+    return hist
+
+
+def pseudo_select(pred, cbin, tbin, ignore_index, out=None):
+    """Thresholded pseudo-labels (rtsds_pseudo_select): int64 ``out`` (same shape as ``pred``)
+    = pred where cbin >= tbin[pred], else ``ignore_index``.  ``pred`` uint8 / ``cbin`` uint16 as
+    confidence_histogram wrote them, ``tbin`` int32 [c] on the same device (a value >= bins keeps
+    nothing of that class).  No host sync.  Returns ``out``."""
+    fn = "pseudo_select"
+    if not (pred.is_cuda and cbin.is_cuda and tbin.is_cuda):
+        raise RuntimeError(f"rtsds_amd: {fn}: pred, cbin and tbin must be HIP tensors; there is no CPU fallback")
+    if pred.numel() == 0:
+        raise RuntimeError(f"rtsds_amd: {fn}: pred is empty")
+    _pseudo_arg(fn, "pred", pred, torch.uint8, pred.shape, pred.device)
+    _pseudo_arg(fn, "cbin", cbin, torch.uint16, pred.shape, pred.device)
+    if tbin.dim() != 1 or not 2 <= tbin.numel() <= 32:
+        raise RuntimeError(f"rtsds_amd: {fn}: tbin must be int32 [c] with 2..32 classes, got {tuple(tbin.shape)}")
+    _pseudo_arg(fn, "tbin", tbin, torch.int32, tbin.shape, pred.device)
+    if out is None:
+        out = torch.empty(pred.shape, dtype=torch.int64, device=pred.device)
+    else:
+        _pseudo_arg(fn, "out", out, torch.int64, pred.shape, pred.device)
+    lib.rtsds_pseudo_select(_P(pred), _P(cbin), _P(tbin), _P(out), pred.numel(), tbin.numel(), int(ignore_index),
+                            stream())
+    return out
+
+
 class BCEWithLogitsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, target):

@@ -3,6 +3,7 @@ config.yaml, factories main.py:110-231, dispatch main.py:272-374) on the HIP pat
 
     python -m rtsds_amd.main [--config rtsds_amd/config.yaml] [--domain_adaptation]
                              [--model bisenet|deeplab] [--dataset cityscapes|gta5] [--seed 42]
+                             [--self_training]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m rtsds_amd.main --domain_adaptation
 
 Datasets (main.py:46-108): when the configured directories exist, the reference's readers
@@ -156,6 +157,74 @@ def datasets_loader(config, is_augmented):
     return city, val_l, gta5
 
 
+def ordered_target_loader(config, train_dl):
+    """The target-train loader self-training sweeps: it must replay the same batches in the same
+    order on every iteration (selftrain.PseudoLabelLoader).  Synthetic data: ``train_dl`` itself
+    (SyntheticLoader is a fixed list).  Real data: Cityscapes train through the device pipeline,
+    not shuffled and not augmented; under data parallelism each rank reads its own fixed shard
+    (DistributedSampler(shuffle=False))."""
+    cs, gta = config.data["cityscapes"], config.data["gta5_modified"]
+    if not (os.path.isdir(cs["images_train_dir"]) and os.path.isdir(gta["images_dir"])):
+        return train_dl
+    from torch.utils.data import DataLoader
+    from torch.utils.data.distributed import DistributedSampler
+
+    from . import transforms as T
+    from .datasets import CityScapes
+    size = T.parse_size(cs["image_size"])
+    rank, _, world = dist_env()
+    ds = CityScapes(cs["segmentation_train_dir"], cs["images_train_dir"])
+    sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=False) if world > 1 else None
+    dl = DataLoader(ds, batch_size=cs["batch_size"], shuffle=False, sampler=sampler, pin_memory=False,
+                    num_workers=cs["num_workers"], collate_fn=T.collate_raw)
+    return T.DeviceLoader(dl, T.ImagePipeline(size), T.LabelPipeline(size, clamp=(0, cs["num_classes"])), config.device)
+
+
+SELF_TRAINING_KEYS = ("rounds", "epochs", "portion", "portion_step", "cap", "bins", "lr_scale", "scales", "flip")
+
+
+def self_training_config(config):
+    """The training.self_training block (commented out in the shipped config.yaml), complete."""
+    st = config.training.get("self_training")
+    if st is None:
+        raise RuntimeError("rtsds_amd: --self_training needs the config block training.self_training "
+                           f"(keys: {', '.join(SELF_TRAINING_KEYS)}); config.yaml ships it commented out")
+    missing = [k for k in SELF_TRAINING_KEYS if k not in st]
+    if missing:
+        raise RuntimeError(f"rtsds_amd: training.self_training lacks {', '.join(missing)}")
+    return st
+
+
+def self_train(config, st, model, optimizer, criterion, init_lr, power, lr_decay_iter, num_classes, target_dl,
+               validate, callbacks):
+    """Class-balanced self-training after the normal run (rtsds_amd.selftrain): per round one
+    sweep over the ordered target loader (generate), global per-class thresholds for the round's
+    portion (class_thresholds), then ``epochs`` epochs of train.train on the thresholded labels
+    with the branch's model, optimizer and criterion; lr = init_lr * lr_scale, poly-decayed over
+    all self-training iterations.  ``validate(epoch)`` runs after every epoch."""
+    from . import selftrain
+    ignore_index = getattr(criterion, "ignore_index", None)
+    if ignore_index is None:
+        raise RuntimeError("rtsds_amd: --self_training needs a criterion with ignore_index (CrossEntropy)")
+    loader = ordered_target_loader(config, target_dl)
+    max_iter = st["rounds"] * st["epochs"] * len(loader)
+    for rnd in range(st["rounds"]):
+        labels = selftrain.generate(model, loader, num_classes, bins=st["bins"], scales=tuple(st["scales"]),
+                                    flip=bool(st["flip"]), device=config.device)
+        portion = min(1.0, st["portion"] + rnd * st["portion_step"])
+        tbin = selftrain.class_thresholds(labels.hist, portion, st["cap"])
+        kept = selftrain.kept_fraction(labels, tbin)
+        print(f"Self-training round {rnd + 1}: portion {portion:.3f}, thresholds "
+              f"{[round(int(b) / st['bins'], 3) for b in tbin]}, kept {[round(float(k), 3) for k in kept]}")
+        pseudo = selftrain.PseudoLabelLoader(loader, labels, tbin, ignore_index)
+        for e in range(st["epochs"]):
+            epoch = rnd * st["epochs"] + e
+            train(model=model, optimizer=optimizer, criterion=criterion, train_loader=pseudo, epoch=epoch,
+                  init_lr=init_lr * st["lr_scale"], lr_decay_iter=lr_decay_iter, power=power, max_iter=max_iter,
+                  callbacks=callbacks, device=config.device)
+            validate(epoch)
+
+
 def argumnet_parser(argv=None):
     p = argparse.ArgumentParser(description="Semantic Segmentation and Domain Adaptation (MI355X)")
     p.add_argument("--config", type=str, default=os.path.join(os.path.dirname(__file__), "config.yaml"))
@@ -165,6 +234,9 @@ def argumnet_parser(argv=None):
     p.add_argument("--model", type=str, default="bisenet")
     p.add_argument("--wandb", action="store_true")
     p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--self_training", action="store_true",
+                   help="class-balanced self-training on the target set after the normal run "
+                        "(config block training.self_training)")
     return p.parse_args(argv)
 
 
@@ -186,7 +258,9 @@ def main(argv=None):
     set_seed(args.seed)
     config = load_config(args.config)
     set_compute_dtype(torch.bfloat16 if getattr(config, "precision", "fp32") == "bf16" else torch.float32)
+    st = self_training_config(config) if args.self_training else None
     train_dl, val_dl, gta_dl = datasets_loader(config, args.augmented)
+    target_dl = train_dl
     callbacks = []
     if args.domain_adaptation:
         (g, g_opt, g_loss, g_hp), (d, d_opt, d_loss, d_hp) = model_loader(config, True, args.model)
@@ -200,6 +274,11 @@ def main(argv=None):
                           num_classes=t["num_classes"], class_names=config.meta["class_names"],
                           val_loader=val_dl, do_validation=t["do_validation"], when_print=t["when_print"],
                           callbacks=callbacks, device=config.device)
+        if st is not None:
+            self_train(config, st, g, g_opt, g_loss, g_hp["gen_init_lr"], g_hp["gen_power"], t["lr_decay_iter"],
+                       t["num_classes"], target_dl,
+                       lambda epoch: val_GTA5(epoch, g, val_dl, t["num_classes"], config.meta["class_names"],
+                                              callbacks, device=config.device), callbacks)
     else:
         if args.dataset == "gta5":
             train_dl = gta_dl
@@ -213,6 +292,13 @@ def main(argv=None):
             val(epoch=epoch, model=model, val_loader=val_dl, num_classes=t["num_classes"],
                 class_names=config.meta["class_names"], detailed_report=True, device=config.device,
                 callbacks=callbacks, scales=t.get("eval_scales"), flip=bool(t.get("eval_flip", False)))
+        if st is not None:
+            self_train(config, st, model, opt, crit, hp["init_lr"], hp["power"], t["lr_decay_iter"], t["num_classes"],
+                       target_dl,
+                       lambda epoch: val(epoch=epoch, model=model, val_loader=val_dl, num_classes=t["num_classes"],
+                                         class_names=config.meta["class_names"], detailed_report=True,
+                                         device=config.device, callbacks=callbacks, scales=t.get("eval_scales"),
+                                         flip=bool(t.get("eval_flip", False))), callbacks)
 
 
 if __name__ == "__main__":

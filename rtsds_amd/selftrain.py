@@ -1,0 +1,195 @@
+"""Class-balanced self-training on the unlabelled target set (CBST; no reference counterpart:
+its loops never train on target pixels).
+
+    labels = generate(model, target_loader, num_classes)        # one sweep, everything on device
+    tbin = class_thresholds(labels.hist, portion=0.2, cap=0.9)   # one host sync
+    loader = PseudoLabelLoader(target_loader, labels, tbin, ignore_index=19)
+    train.train(..., train_loader=loader, ...)                   # ordinary cross-entropy
+
+``generate`` predicts every batch (validation.predict_multiscale), and the HIP kernel
+rtsds_conf_hist turns the fp32 probability sum into a per-class confidence histogram plus, per
+pixel, the predicted class (uint8) and its confidence bin (uint16): 3 B/pixel, 4.7 GB for the
+Cityscapes train set at 512 x 1024.  ``class_thresholds`` picks, per class, the confidence above
+which the wanted share of that class's pixels lies; ``PseudoLabelLoader`` applies the thresholds
+per batch with rtsds_pseudo_select and yields the (inputs, labels) pairs train.train expects.
+
+Quantisation.  Confidences are compared as bins of width 1 / bins: ``cbin >= tbin[k]`` is the
+test ``conf >= tbin[k] / bins``.  A threshold is therefore a bin edge, and the pixels kept for
+class k are exactly sum_{b >= tbin[k]} hist[k, b]: at least portion * N_k, and at most that
+plus the population of bin tbin[k] (all of that bin is kept, not the part of it the exact
+quantile would cut off).  With 1024 bins the confidence step is below 0.1 %.
+
+Batch order.  The per-batch pred / cbin are recorded in the order the loader yielded them, so
+the loader must replay the same batches in the same order on every iteration (main's
+SyntheticLoader does; so does a non-shuffled, non-augmented transforms.DeviceLoader).  A
+different batch count or batch shape is refused; different images of the same shape cannot be
+detected.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import functional as F
+from .validation import predict_multiscale
+
+
+def _global_hist(hist):
+    """``hist`` summed over the ranks of an initialised process group (a copy), else ``hist``."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        hist = hist.clone()
+        dist.all_reduce(hist, op=dist.ReduceOp.SUM)
+    return hist
+
+
+def _check_tbin(tbin, c):
+    t = np.asarray(tbin.cpu() if torch.is_tensor(tbin) else tbin).astype(np.int64).reshape(-1)
+    if t.shape[0] != c:
+        raise RuntimeError(f"rtsds_amd: selftrain: {t.shape[0]} thresholds for {c} classes")
+    return t
+
+
+def class_thresholds(hist, portion, cap=None):
+    """Per-class confidence thresholds, as bin indices (int32 CPU tensor [c]), from the int64
+    [c, bins] histogram of ``generate`` -- on the host (numpy), one sync per sweep.
+
+    For class k with N_k = sum_b hist[k, b] pixels: need = max(1, ceil(portion * N_k)) (float64)
+    and tbin[k] is the largest b whose tail sum_{b' >= b} hist[k, b'] reaches ``need``; an empty
+    class gets ``bins`` (keeps nothing).  ``cap`` (a confidence in (0, 1]) limits every threshold
+    to floor(cap * bins): no class demands more than ``cap``.  Without ``cap`` class k keeps
+    exactly sum_{b >= tbin[k]} hist[k, b] pixels (see the module docstring for the bin
+    quantisation).  Under an initialised process group of more than one rank the histogram is
+    all-reduced (SUM) first, so every rank gets the same, global thresholds."""
+    if not 0.0 < float(portion) <= 1.0:
+        raise RuntimeError(f"rtsds_amd: class_thresholds: portion must be in (0, 1], got {portion}")
+    if cap is not None and not 0.0 < float(cap) <= 1.0:
+        raise RuntimeError(f"rtsds_amd: class_thresholds: cap must be in (0, 1], got {cap}")
+    if hist.dim() != 2 or hist.dtype != torch.int64:
+        raise RuntimeError(f"rtsds_amd: class_thresholds: hist must be int64 [c, bins], got {hist.dtype} "
+                           f"{tuple(hist.shape)}")
+    h = _global_hist(hist).cpu().numpy()
+    c, bins = h.shape
+    tail = np.cumsum(h[:, ::-1], axis=1)[:, ::-1]  # tail[k, b] = sum_{b' >= b} hist[k, b']
+    tbin = np.full(c, bins, dtype=np.int32)
+    for k in range(c):
+        n_k = int(tail[k, 0])
+        if n_k == 0:
+            continue
+        need = max(1, math.ceil(np.float64(portion) * np.float64(n_k)))
+        tbin[k] = np.nonzero(tail[k] >= need)[0].max()  # the tail is non-increasing in b
+    if cap is not None:
+        tbin = np.minimum(tbin, np.int32(math.floor(float(cap) * bins)))
+    return torch.from_numpy(tbin.astype(np.int32))
+
+
+class PseudoLabels:
+    """One sweep's result: ``hist`` (int64 [c, bins], on the sweep's device), the per-batch
+    ``pred`` (uint8 [n, H, W]) and ``cbin`` (uint16 [n, H, W]) in loader order, and ``bins``."""
+
+    def __init__(self, hist, pred, cbin, bins):
+        self.hist, self.pred, self.cbin, self.bins = hist, pred, cbin, bins
+
+    def __len__(self):
+        return len(self.pred)
+
+    @property
+    def num_classes(self):
+        return int(self.hist.shape[0])
+
+
+def generate(model, loader, num_classes, bins=1024, scales=(1.0,), flip=False, device="cuda", store="device"):
+    """One sweep over ``loader`` in its own order: every batch is predicted at the input size
+    (predict_multiscale with ``scales`` / ``flip``) and reduced to (pred, cbin) plus the running
+    histogram by functional.confidence_histogram.  The loader's own labels are ignored.
+    ``store``: "device" keeps pred / cbin (3 B/pixel) in device memory, "cpu" copies each batch
+    to the host.  Returns a PseudoLabels."""
+    if store not in ("device", "cpu"):
+        raise RuntimeError(f"rtsds_amd: selftrain.generate: store must be 'device' or 'cpu', got {store!r}")
+    scales = tuple(float(s) for s in scales)
+    passes = len(scales) * (2 if flip else 1)
+    hist = None
+    preds, cbins = [], []
+    for inputs, _ in loader:
+        inputs = inputs.to(device)
+        acc, _ = predict_multiscale(model, inputs, inputs.shape[-2:], scales, flip)
+        if acc.shape[-1] != num_classes:
+            raise RuntimeError(f"rtsds_amd: selftrain.generate: the model predicts {acc.shape[-1]} classes, "
+                               f"num_classes is {num_classes}")
+        if hist is None:
+            hist = torch.zeros((num_classes, bins), dtype=torch.int64, device=acc.device)
+        pred = torch.empty(acc.shape[:3], dtype=torch.uint8, device=acc.device)
+        cbin = torch.empty(acc.shape[:3], dtype=torch.uint16, device=acc.device)
+        F.confidence_histogram(acc, hist, passes=passes, pred=pred, cbin=cbin)
+        preds.append(pred.cpu() if store == "cpu" else pred)
+        cbins.append(cbin.cpu() if store == "cpu" else cbin)
+    if hist is None:
+        raise RuntimeError("rtsds_amd: selftrain.generate: the loader yielded no batch")
+    return PseudoLabels(hist, preds, cbins, bins)
+
+
+class PseudoLabelLoader:
+    """Iterates ``loader`` and yields ``(inputs, pseudo)`` with ``pseudo`` int64 [N, 1, H, W] --
+    the format train.train expects -- made per batch by functional.pseudo_select from the
+    recorded ``labels`` (a PseudoLabels) and the thresholds ``tbin`` (class_thresholds).
+    ``len()`` is the loader's.
+
+    The loader must replay the same batches in the same order on every iteration, the order
+    ``generate`` saw: main's SyntheticLoader does, and so does a non-shuffled, non-augmented
+    transforms.DeviceLoader.  A different number of batches or a batch of another shape raises
+    RuntimeError.  ``set_thresholds`` replaces the thresholds between rounds without another
+    sweep."""
+
+    def __init__(self, loader, labels, tbin, ignore_index):
+        self.loader, self.labels, self.ignore_index = loader, labels, int(ignore_index)
+        if len(loader) != len(labels):
+            raise RuntimeError(f"rtsds_amd: PseudoLabelLoader: the loader has {len(loader)} batches, "
+                               f"{len(labels)} were recorded")
+        self.set_thresholds(tbin)
+
+    def set_thresholds(self, tbin):
+        self.tbin = torch.from_numpy(_check_tbin(tbin, self.labels.num_classes).astype(np.int32))
+        self._tbin_dev = {}
+
+    def __len__(self):
+        return len(self.loader)
+
+    def _tbin_on(self, device):
+        if device not in self._tbin_dev:
+            self._tbin_dev[device] = self.tbin.to(device)
+        return self._tbin_dev[device]
+
+    def __iter__(self):
+        n = 0
+        for inputs, _ in self.loader:
+            if n >= len(self.labels):
+                raise RuntimeError(f"rtsds_amd: PseudoLabelLoader: the loader yielded more than the "
+                                   f"{len(self.labels)} recorded batches")
+            pred, cbin = self.labels.pred[n], self.labels.cbin[n]
+            want = (inputs.shape[0], inputs.shape[2], inputs.shape[3])
+            if tuple(pred.shape) != want:
+                raise RuntimeError(f"rtsds_amd: PseudoLabelLoader: batch {n} has shape {want}, "
+                                   f"{tuple(pred.shape)} was recorded")
+            if not pred.is_cuda:  # store="cpu": back to the device of the sweep
+                dev = self.labels.hist.device
+                pred, cbin = pred.to(dev, non_blocking=True), cbin.to(dev, non_blocking=True)
+            out = F.pseudo_select(pred, cbin, self._tbin_on(pred.device), self.ignore_index)
+            yield inputs, out.unsqueeze(1)
+            n += 1
+        if n != len(self.labels):
+            raise RuntimeError(f"rtsds_amd: PseudoLabelLoader: the loader yielded {n} batches, "
+                               f"{len(self.labels)} were recorded")
+
+
+def kept_fraction(labels, tbin):
+    """Per-class share of the predicted pixels that ``tbin`` keeps (float64 numpy [c]; NaN for a
+    class nothing was predicted as), from the histogram alone -- for logging."""
+    h = _global_hist(labels.hist).cpu().numpy()
+    c, bins = h.shape
+    t = _check_tbin(tbin, c)
+    kept = np.array([h[k, min(int(t[k]), bins):].sum() for k in range(c)], dtype=np.float64)
+    total = h.sum(axis=1).astype(np.float64)
+    return np.where(total > 0, kept / np.maximum(total, 1), np.nan)
+
+
+__all__ = ["class_thresholds", "generate", "PseudoLabels", "PseudoLabelLoader", "kept_fraction"]
