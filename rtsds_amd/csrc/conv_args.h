@@ -1,5 +1,6 @@
 // Implicit-GEMM convolution: the kernel arguments and the tile choice shared by the host code
-// (conv.hip) and the kernel translation units (conv_gemm_{fwd,dgrad,wgrad}.hip).
+// (conv_{fwd,dgrad,wgrad}.hip through conv_host.h) and the kernel translation units
+// (conv_gemm_{fwd,dgrad,wgrad}.hip).
 #pragma once
 #include "common.h"
 

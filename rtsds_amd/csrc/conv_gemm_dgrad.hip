@@ -1,4 +1,4 @@
-// Implicit-GEMM conv kernels, DGRAD instantiations (conv_gemm_kernel.h; host side in conv.hip).
+// Implicit-GEMM conv kernels, DGRAD instantiations (conv_gemm_kernel.h; host side in conv_dgrad.hip).
 #include "conv_gemm_kernel.h"
 
 template void dispatch_align<bf16, MODE_DGRAD>(const ConvArgs&, int, hipStream_t, int);

@@ -1,4 +1,4 @@
-// Implicit-GEMM conv kernels, FWD instantiations (conv_gemm_kernel.h; host side in conv.hip).
+// Implicit-GEMM conv kernels, FWD instantiations (conv_gemm_kernel.h; host side in conv_fwd.hip).
 // One translation unit per GEMM mode so the three compile in parallel.
 #include "conv_gemm_kernel.h"
 

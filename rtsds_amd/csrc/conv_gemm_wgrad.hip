@@ -1,4 +1,4 @@
-// Implicit-GEMM conv kernels, WGRAD instantiations (conv_gemm_kernel.h; host side in conv.hip).
+// Implicit-GEMM conv kernels, WGRAD instantiations (conv_gemm_kernel.h; host side in conv_wgrad.hip).
 #include "conv_gemm_kernel.h"
 
 template void wgrad_launch<bf16>(const ConvArgs&, int, int, int, hipStream_t);

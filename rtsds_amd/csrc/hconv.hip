@@ -19,7 +19,7 @@
 // channels).  Epilogue: bias (or eval-BN scale/shift), activation, the following BatchNorm's
 // per-tile partial statistics (count, mean, M2 -- the exact two-pass form, as the GEMM
 // epilogue), scalar bf16 stores of the Cout valid channels.
-#include "common.h"
+#include "conv_host.h"
 #include <algorithm>
 #include <utility>
 
@@ -167,7 +167,7 @@ __global__ void __launch_bounds__(256, 1) hconv_fwd_kernel(const HconvArgs P) {
       __builtin_amdgcn_sched_barrier(0);
     }
     // every wave is done with this buffer before it is refilled: its ds_reads retired first
-    // (a raw s_barrier does not wait for them; see gl_barrier in conv.hip)
+    // (a raw s_barrier does not wait for them; see gl_barrier in conv_gemm_kernel.h)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");

@@ -8,7 +8,7 @@
 // gather, then a full epilogue -- 73 / 112 us per launch (30 % of the HBM bound).  Here a
 // workgroup owns a 4 x 64 output tile with all 64 channels:
 //  * the tile's input rows are staged ONCE into LDS as 16-B "superpixels" (two horizontally
-//    adjacent pixels of the 4-channel-padded image, conv.hip sp_path): (2*4 + kh - 2) rows x
+//    adjacent pixels of the 4-channel-padded image, conv_host.h sp_path): (2*4 + kh - 2) rows x
 //    (64 + (kw+1)/2 - 1) superpixels, one buffer-resource LDS-DMA per 16 B, padding zero-filled
 //    by the DMA (offsets past num_records);
 //  * with odd padding, taps s = 2p - 1 + q of output column ow read superpixel ow - (pw+1)/2 + p,
@@ -25,7 +25,7 @@
 //    from the (transposed) accumulators.
 // Inference also has a variant with the stem's 3x3 stride-2 max pool in the epilogue
 // (imgconv_pool_kernel): the full-resolution activation is never written.
-#include "common.h"
+#include "conv_host.h"
 
 template <int N> RT_DEV void wait_vmcnt_img() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // Sum over the 16 lanes of a DPP row (every lane of the row ends with the total): quad_perm
@@ -535,7 +535,7 @@ __global__ void __launch_bounds__(256, 2) imgconv_pool_kernel(const ImgPoolArgs 
 }
 
 // ---- host -------------------------------------------------------------------------------
-// The superpixel geometry of conv.hip's sp_path with 64 output channels and a 7x7 or 3x3 kernel.
+// The superpixel geometry of conv_host.h's sp_path with 64 output channels and a 7x7 or 3x3 kernel.
 bool imgconv_ok(const rtsds_conv_desc* d) {
   if (!(d->dtype == RTSDS_BF16 && d->c == 3 && d->k == kCo && d->sh == 2 && d->sw == 2 && d->dh == 1 && d->dw == 1 &&
         (d->pw & 1) == 1 && (d->w & 1) == 0))

@@ -22,7 +22,7 @@ extern "C" int rtsds_nchw_to_nhwc(const float* x, void* y, int n, int c, int h, 
 
 // NCHW fp32 -> NHWC T with channel pitch cp >= c, channels c..cp-1 zero: the image batch in
 // the layout its convs gather (3 -> 4 channels: the superpixel view of the stem / spatial-path
-// convs, conv.hip sp_path), so they skip their own pad pass.  One thread per pixel.
+// convs, conv_host.h sp_path), so they skip their own pad pass.  One thread per pixel.
 template <typename T, int CP>
 __global__ void nchw_to_nhwc_pad_kernel(const float* __restrict__ x, T* __restrict__ y, int c, long hw, long pixels) {
   GRID_STRIDE(p, pixels) {

@@ -9,7 +9,7 @@
 // are staged in LDS as fp32 and read as broadcasts.  512 -> 19 at 65536 pixels: 28 us vs
 // 43 us for the generic GEMM path; 19 -> 19: 7 vs 18 us.  (The weight gradient stays on the
 // split-K GEMM, which measured faster than a VALU reduction here: 25 vs 42 us.)
-#include "common.h"
+#include "conv_host.h"
 
 namespace {
 constexpr int kPwMaxK = 32;

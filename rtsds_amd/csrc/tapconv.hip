@@ -23,7 +23,7 @@
 // BatchNorm's (count, mean, M2) merged per wave over its tiles (Chan).  DGRAD -- accumulate
 // (GradJoin), the LeakyReLU / ReLU backward of the input's activation (mask), or the backward
 // statistics (sum g, sum g (x - mean)) of the BatchNorm + activation that produced the input.
-#include "common.h"
+#include "conv_host.h"
 
 namespace {
 constexpr int kC = 64;                    // input = output channels

@@ -237,6 +237,71 @@ def test_pw_backward_accumulate(c, hw):
         assert torch.equal(dw_p, dw_f) and torch.equal(db_p, db_f)
 
 
+WS_CASES = [
+    # n, c, h, w, k, kh, stride, pad, dil; dtype -- each reaches another workspace layout
+    ((2, 19, 32, 64, 64, 4, 2, 1, 1), torch.bfloat16),     # padded x and w; stride-2 phases; padded dY
+    ((2, 3, 32, 48, 64, 7, 2, 3, 1), torch.bfloat16),      # superpixel forward and weight gradient
+    ((2, 256, 16, 32, 19, 3, 1, 2, 2), torch.bfloat16),    # forward split-K slabs; Cout-padded data gradient
+    ((2, 512, 16, 32, 512, 3, 1, 1, 1), torch.bfloat16),   # data-gradient split-K slabs
+    ((2, 19, 16, 16, 19, 1, 1, 0, 1), torch.bfloat16),     # narrow pointwise weight gradient
+    ((2, 256, 6, 100, 19, 3, 1, 1, 1), torch.bfloat16),    # halo weight gradient
+    ((2, 64, 16, 16, 128, 3, 2, 1, 1), torch.float32),     # the f32 GEMM plan
+]
+WS_GUARD = 4096
+
+
+@pytest.mark.parametrize("case,dt", WS_CASES)
+def test_conv_workspace_query_matches_launch(case, dt):
+    """The workspace queries and the launches agree, for forward, data gradient and weight
+    gradient through the C ABI: with a workspace of exactly the queried size, followed in the
+    same allocation by 4 KiB of a fixed byte pattern, the pattern stays untouched and the results
+    equal, bit for bit, those of a call with a generously larger workspace; with one byte less
+    the call returns RTSDS_ERR_WORKSPACE and writes nothing."""
+    import ctypes
+    from rtsds_amd import _lib
+    from rtsds_amd.functional import _conv_desc, _P
+    from rtsds_amd.runtime import stream
+
+    raw = _lib.load()  # the entry points themselves: their status is the return value
+    n, c, h, w, k, kh, s, p, dil = case
+    g = torch.Generator().manual_seed(hash(case) & 0xFFFF)
+    x = _dev(torch.randn(n, c, h, w, generator=g), dt)
+    wq = _dev(torch.randn(k, c, kh, kh, generator=g) / (c * kh * kh) ** 0.5, dt)
+    d = _conv_desc(x, k, kh, kh, (s, s), (p, p), (dil, dil))
+    dy = _dev(torch.randn(n, k, d.ho, d.wo, generator=g), dt)
+    dp = ctypes.byref(d)
+    f32 = dict(dtype=torch.float32, device=DEV)
+    passes = {
+        "fwd": (raw.rtsds_conv2d_fwd_workspace, lambda: [torch.empty_like(dy)],
+                lambda o, ws, nb: raw.rtsds_conv2d_fwd(dp, _P(x), _P(wq), None, _P(o[0]), 0, None, ws, nb, stream())),
+        "dgrad": (raw.rtsds_conv2d_dgrad_workspace, lambda: [torch.empty_like(x)],
+                  lambda o, ws, nb: raw.rtsds_conv2d_dgrad(dp, _P(dy), _P(wq), _P(o[0]), 0, ws, nb, stream())),
+        "wgrad": (raw.rtsds_conv2d_wgrad_workspace, lambda: [torch.empty(k * kh * kh * c, **f32), torch.empty(k, **f32)],
+                  lambda o, ws, nb: raw.rtsds_conv2d_wgrad(dp, _P(x), _P(dy), _P(o[0]), _P(o[1]), 0, ws, nb, stream())),
+    }
+    for name, (query, outputs, call) in passes.items():
+        need = query(dp)
+        exact = torch.full((need + WS_GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
+        if need > 0:  # one byte short: refused before any launch
+            out = outputs()
+            for t in out:
+                t.fill_(7)
+            assert call(out, _P(exact), need - 1) == 4, name
+            torch.cuda.synchronize()
+            assert all(bool((t == 7).all()) for t in out), name
+            assert bool((exact == 0xA5).all()), name
+        out = outputs()
+        assert call(out, _P(exact), need) == 0, name
+        torch.cuda.synchronize()
+        assert bool((exact[need:] == 0xA5).all()), (name, "wrote past the queried workspace")
+        roomy = torch.full((2 * need + (1 << 20),), 0xA5, dtype=torch.uint8, device=DEV)
+        ref = outputs()
+        assert call(ref, _P(roomy), roomy.numel()) == 0, name
+        torch.cuda.synchronize()
+        for u, v in zip(out, ref):
+            assert torch.equal(u, v), name
+
+
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("act", [0, 1, 2])
 def test_conv_fused_act(dt, act):

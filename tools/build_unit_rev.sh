@@ -7,15 +7,19 @@ set -e
 root="$(cd "$(dirname "$0")/.." && pwd)"
 cd "$root"
 name=$1; rev=$2; shift 2
-# the conv host side (conv.hip) and the GEMM kernel units share conv_args.h (the tile choice,
-# which also sizes the BatchNorm-statistics partials): swapping one without the others mixes two
-# tile rules -- a launch then writes partials for more M tiles than its caller allocated (a GPU
-# memory fault, round 5).  They always travel together.
+# the conv host side (conv_fwd / conv_dgrad / conv_wgrad / conv_pooled; conv.hip in older
+# revisions) and the GEMM kernel units share conv_args.h (the tile choice, which also sizes the
+# BatchNorm-statistics partials): swapping one without the others mixes two tile rules -- a launch
+# then writes partials for more M tiles than its caller allocated (a GPU memory fault, round 5).
+# They always travel together.
+conv_host="conv_fwd conv_dgrad conv_wgrad conv_pooled"
 units=" $* "
-if [[ "$units" =~ " conv " || "$units" == *" conv_gemm_"* ]]; then
-  for u in conv conv_gemm_fwd conv_gemm_dgrad conv_gemm_wgrad; do
+if [[ "$units" == *" conv "* || "$units" == *" conv_"* ]]; then
+  for u in conv $conv_host conv_gemm_fwd conv_gemm_dgrad conv_gemm_wgrad; do
     git cat-file -e $rev:rtsds_amd/csrc/$u.hip 2>/dev/null && [[ "$units" != *" $u "* ]] && units="$units$u "
   done
+  # "conv" asked of a revision after the split: its four units (added above) stand for it
+  git cat-file -e $rev:rtsds_amd/csrc/conv.hip 2>/dev/null || units="${units/ conv / }"
 fi
 set -- $units
 src=_revtmp/src   # two levels below the root: the sources' ../../include/rtsds_hip.h resolves
@@ -28,8 +32,11 @@ for unit in "$@"; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-variable -c $src/$unit.hip -o $out/$unit.o &
 done
 wait
-# a revision's ew unit is today's layout + pool + chan + resize + optim
-[[ "$units" == *" ew "* ]] && split=" layout pool chan resize optim " || split=""
+# a revision's ew unit is today's layout + pool + chan + resize + optim, its conv unit today's
+# conv_fwd + conv_dgrad + conv_wgrad + conv_pooled
+split=""
+[[ "$units" == *" ew "* ]] && split="$split layout pool chan resize optim "
+[[ "$units" == *" conv "* ]] && split="$split $conv_host "
 for f in rtsds_amd/csrc/build/*.o; do
   b=$(basename $f .o); [ -e $out/$b.o ] || [[ "$split" == *" $b "* ]] || cp $f $out/
 done

@@ -5,7 +5,8 @@
 # linked from the main build's objects (make -C rtsds_amd/csrc first).  Default: all units.
 set -e
 cd "$(dirname "$0")/../rtsds_amd/csrc"
-all="conv conv_gemm_fwd conv_gemm_dgrad conv_gemm_wgrad hconv imgconv tapconv pw bn layout pool chan resize optim upce data graph"
+# every unit of the library: the Makefile's SRCS
+all=$(sed -n 's/^SRCS *= *//p' Makefile | sed 's/\.hip//g')
 name=$1; flags=$2; units=${3:-$all}
 out=build/var_$name
 rm -rf $out && mkdir -p $out

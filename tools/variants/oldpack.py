@@ -22,4 +22,4 @@ OLD = """#pragma unroll
     const int co = ot * 64 + ly + 4 * k, ci = ct * 64 + lx;
     tile[ly + 4 * k][lx] = (co < g.co_n && ci < g.ci_n) ? to_f(w[((co * g.kh + r) * g.kw + sc) * g.ci_n + ci]) : 0.f;
   }"""
-build("oldpack", {"conv.hip": [(NEW, OLD)]}, ["conv"])
+build("oldpack", {"conv_dgrad.hip": [(NEW, OLD)]}, ["conv_dgrad"])
