@@ -464,7 +464,17 @@ int rtsds_pseudo_select(const uint8_t* pred, const uint16_t* cbin, const int* tb
  *   uint8 (else fp32) source.  dst is the image's slot in an NHWC batch.
  * rtsds_gaussian_blur: GaussianBlur((kx, ky), sigma) of a HWC image (uint8 or fp32 source),
  *   fp32 HWC out, reflect padding.
- * rtsds_gta5_decode: RGB label (HWC uint8) -> train id 0..18 (unmatched colours -> 0).      */
+ * rtsds_gta5_decode: RGB label (HWC uint8) -> train id 0..18 (unmatched colours -> 0).
+ * rtsds_color_jitter: torchvision ColorJitter of a HWC RGB image (c == 3, else
+ *   RTSDS_ERR_UNSUPPORTED; uint8 or fp32 source with values in [0, bound]), fp32 HWC out; dst may
+ *   be src for an fp32 source.  Op ids 0 brightness, 1 contrast, 2 saturation, 3 hue are applied in
+ *   `order` (four host ints, a permutation of 0..3); bit k of `mask` switches id k on; fb / fc / fs
+ *   >= 0 and fh in [-0.5, 0.5] are the factors torchvision's get_params draws.  Every op clamps
+ *   to [0, bound]; hue works on p / bound (bound = 1 is torchvision's float image, 255 the
+ *   reference's 0-255 scale).  With contrast on, a first launch reduces the grey mean of the image
+ *   as it stands when contrast is applied into the workspace (rtsds_color_jitter_workspace bytes;
+ *   not read otherwise, ws may be NULL); the result is bitwise reproducible.  Arguments are
+ *   validated before any HIP call.                                                              */
 size_t rtsds_resize_aa_workspace(int c, int h, int w, int ho, int wo);
 int rtsds_resize_aa(const void* src, int src_u8, int c, int h, int w, void* dst, int kind, int ho, int wo,
                     int flip, const float* mean, const float* std, int clamp_lo, int clamp_hi, void* ws,
@@ -472,6 +482,10 @@ int rtsds_resize_aa(const void* src, int src_u8, int c, int h, int w, void* dst,
 int rtsds_gaussian_blur(const void* src, int src_u8, float* dst, int c, int h, int w, int kx, int ky,
                         float sigma_x, float sigma_y, void* stream);
 int rtsds_gta5_decode(const uint8_t* rgb, int64_t* out, int h, int w, void* stream);
+size_t rtsds_color_jitter_workspace(int h, int w);
+int rtsds_color_jitter(const void* src, int src_u8, float* dst, int c, int h, int w, const int* order,
+                       int mask, float fb, float fc, float fs, float fh, float bound, void* ws,
+                       size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- graph replay
  * Replaces hipGraphLaunch of a captured multi-stream iteration (runtime.GraphedStep /
@@ -515,7 +529,7 @@ int rtsds_pooled_mlp_fwd(const void* p, const void* w1, const float* b1, const v
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 12
+#define RTSDS_ABI_VERSION 13
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSDS_LIB: alternative in-tree build of the same ABI (kernel-variant A/B measurements)
 DEFAULT_LIB_PATH = os.path.join(_HERE, "librtsds_hip.so")
-ABI_VERSION = 12  # include/rtsds_hip.h RTSDS_ABI_VERSION
+ABI_VERSION = 13  # include/rtsds_hip.h RTSDS_ABI_VERSION
 LIB_PATH = os.environ.get("RTSDS_LIB") or DEFAULT_LIB_PATH
 
 F32, BF16 = 0, 1
@@ -130,6 +130,9 @@ SIGNATURES = {
                                 P, c_size_t, P]),
     "rtsds_gaussian_blur": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P]),
     "rtsds_gta5_decode": (c_int, [P, P, c_int, c_int, P]),
+    "rtsds_color_jitter_workspace": (c_size_t, [c_int, c_int]),
+    "rtsds_color_jitter": (c_int, [P, c_int, P, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, c_float, c_float,
+                                   c_float, c_float, c_float, P, c_size_t, P]),
     "rtsds_sgd_step": (c_int, [P, P, P, P, c_long, P, c_float, c_float, c_float, c_float, c_int, c_int,
                                c_float, c_int, P]),
     "rtsds_adam_step": (c_int, [P, P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float,

@@ -13,6 +13,9 @@
 //            (utils.py:67-75), and the NHWC compute-dtype store the network reads.
 //   blur     GaussianBlur(kernel_size, sigma): the separable Gaussian of torchvision applied as
 //            its 2-D outer-product kernel with reflect padding.
+//   jitter   ColorJitter(brightness, contrast, saturation, hue) in the permutation drawn per
+//            call, all adjustments in one pass over registers; contrast's grey mean comes
+//            from a reduction launch in front of it.
 //   decode   GTA5 RGB label -> train id (gta5.py:111-118: every pixel whose colour equals the
 //            colour of train id i gets i, others 0).
 //
@@ -207,6 +210,238 @@ extern "C" int rtsds_gaussian_blur(const void* src, int src_u8, float* dst, int 
   const long n = (long)h * w * c;
   hipLaunchKernelGGL(gblur_kernel, dim3((int)std::min<long>(8192, (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src,
                      src_u8, dst, h, w, c, kx, ky, sigma_x, sigma_y);
+  RET_LAUNCH();
+}
+
+// ---- ColorJitter(brightness, contrast, saturation, hue): HWC c = 3, uint8 or fp32 -> fp32 HWC ----
+// (torchvision adjust_brightness / _contrast / _saturation / _hue on a float image in
+// [0, bound], applied in the permutation drawn per call; the host passes the enabled ops already
+// in application order.  Contrast blends with the mean grey of the image as it stands when
+// contrast is applied, so with contrast on a first launch reduces gray(prefix(p)) into one
+// partial per block, and every block of the apply launch adds those partials in a fixed order.)
+static const int kCjMaxParts = 1024;  // grid cap of the reduction = partials in the workspace
+static const int kCjPix = 4;          // consecutive pixels per thread: 12 B uint8 / 3 x 16 B fp32
+
+struct CjOps {
+  int n;     // enabled ops, in application order
+  int cpos;  // index of contrast among them, -1 when off
+  int id[4];
+  float f[4];
+  float bound, inv_bound;
+};
+
+RT_DEV float cj_gray(float r, float g, float b) { return fmaf(0.114f, b, fmaf(0.587f, g, 0.2989f * r)); }
+RT_DEV float cj_clamp(float v, float hi) { return fminf(fmaxf(v, 0.f), hi); }
+// blend(a, b, f) = clamp(f a + (1 - f) b); fb = (1 - f) b is the same for the three channels
+RT_DEV float cj_blend(float a, float fb, float f, float bound) { return cj_clamp(fmaf(f, a, fb), bound); }
+
+RT_DEV void cj_hue(float& r, float& g, float& b, float fh, float bound, float inv_bound) {
+  r *= inv_bound;
+  g *= inv_bound;
+  b *= inv_bound;
+  const float maxc = fmaxf(r, fmaxf(g, b)), minc = fminf(r, fminf(g, b));
+  const bool eq = maxc == minc;
+  const float cr = maxc - minc;
+  const float s = cr / (eq ? 1.f : maxc);
+  const float crd = eq ? 1.f : cr;
+  // h = bc - gc | 2 + rc - bc | 4 + gc - rc with xc = (maxc - x) / crd: only two quotients are used
+  const bool mr = maxc == r, mg = maxc == g;
+  const float x = mr ? b : (mg ? r : g), y = mr ? g : (mg ? b : r);
+  const float off = mr ? 0.f : (mg ? 2.f : 4.f);
+  float h = (off + (maxc - x) / crd) - (maxc - y) / crd;
+  h = h / 6.f + 1.f;
+  h -= floorf(h);  // fmod(h, 1), h > 0
+  h += fh;
+  h -= floorf(h);  // floor-mod
+  const float h6 = h * 6.f, fi = floorf(h6), f = h6 - fi;
+  int i = (int)fi;
+  i = i >= 6 ? i - 6 : i;
+  const float v = maxc;
+  const float p_ = cj_clamp(v * (1.f - s), 1.f), q_ = cj_clamp(v * (1.f - f * s), 1.f),
+              t_ = cj_clamp(v * (1.f - (1.f - f) * s), 1.f);
+  r = (i == 0 || i == 5 ? v : (i == 1 ? q_ : (i == 4 ? t_ : p_))) * bound;
+  g = (i == 1 || i == 2 ? v : (i == 0 ? t_ : (i == 3 ? q_ : p_))) * bound;
+  b = (i == 3 || i == 4 ? v : (i == 2 ? t_ : (i == 5 ? q_ : p_))) * bound;
+}
+
+// The first `count` ops of the order on N pixels in registers (a = r g b r g b ...); m = mean
+// grey for contrast.  The reduction calls it with count = cpos, the apply kernel with count = n:
+// the same instructions on the same values per pixel (explicit fma, branches uniform over the
+// launch), so the mean is the mean of what the apply kernel recomputes.  The ops are the outer
+// loop: one read of the op and one branch serve the N independent pixels.
+template <int N>
+RT_DEV void cj_prefix(float* a, const CjOps& o, int count, float m) {
+  for (int k = 0; k < count; ++k) {
+    const int id = o.id[k];
+    const float f = o.f[k];
+    if (id == 3) {
+#pragma unroll
+      for (int j = 0; j < N; ++j) cj_hue(a[3 * j], a[3 * j + 1], a[3 * j + 2], f, o.bound, o.inv_bound);
+      continue;
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      float other = 0.f;  // brightness: blend with black
+      if (id == 1) other = m;
+      if (id == 2) other = cj_gray(a[3 * j], a[3 * j + 1], a[3 * j + 2]);
+      const float fb = (1.f - f) * other;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) a[3 * j + ch] = cj_blend(a[3 * j + ch], fb, f, o.bound);
+    }
+  }
+}
+
+// kCjPix consecutive pixels (12 values) of group gi.  VEC: three dwords of uint8 / three 16-B
+// vectors of fp32 (the host checks the base alignment); else scalar loads.
+template <typename S, bool VEC>
+RT_DEV void cj_load(const S* src, long gi, float a[12]) {
+  if constexpr (VEC && sizeof(S) == 1) {
+    const uint32_t* p = (const uint32_t*)src + gi * 3;
+    const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      a[j] = (float)((w0 >> (8 * j)) & 255u);
+      a[4 + j] = (float)((w1 >> (8 * j)) & 255u);
+      a[8 + j] = (float)((w2 >> (8 * j)) & 255u);
+    }
+  } else if constexpr (VEC) {
+    const f32x4* p = (const f32x4*)src + gi * 3;
+    const f32x4 v0 = p[0], v1 = p[1], v2 = p[2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      a[j] = v0[j];
+      a[4 + j] = v1[j];
+      a[8 + j] = v2[j];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 12; ++j) a[j] = (float)src[gi * 12 + j];
+  }
+}
+
+// launch 1 (contrast on): part[block] = sum over the block's pixels of gray(prefix(p))
+template <typename S, bool VEC>
+__global__ void __launch_bounds__(256) cj_mean_kernel(const S* src, float* __restrict__ part, long npix, CjOps o) {
+  __shared__ float wsum[4];
+  const long ngroups = npix / kCjPix;
+  float acc = 0.f;
+  for (long gi = blockIdx.x * (long)blockDim.x + threadIdx.x; gi < ngroups; gi += (long)gridDim.x * blockDim.x) {
+    float a[12];
+    cj_load<S, VEC>(src, gi, a);
+    cj_prefix<kCjPix>(a, o, o.cpos, 0.f);
+#pragma unroll
+    for (int j = 0; j < kCjPix; ++j) acc += cj_gray(a[3 * j], a[3 * j + 1], a[3 * j + 2]);
+  }
+  const long tail = ngroups * kCjPix + threadIdx.x;  // the last npix % kCjPix pixels: block 0
+  if (blockIdx.x == 0 && tail < npix) {
+    float p[3] = {(float)src[tail * 3], (float)src[tail * 3 + 1], (float)src[tail * 3 + 2]};
+    cj_prefix<1>(p, o, o.cpos, 0.f);
+    acc += cj_gray(p[0], p[1], p[2]);
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// launch 2: m = (sum of the partials in fp64, a fixed order) / npix in every block, then all
+// ops on the block's pixels.  src may be dst (fp32): a thread reads its pixels before it stores.
+template <typename S, bool VEC>
+__global__ void __launch_bounds__(256) cj_apply_kernel(const S* src, float* dst, long npix, const float* __restrict__ part,
+                                                       int nparts, CjOps o) {
+  __shared__ double chunk[64];
+  __shared__ float mean;
+  float m = 0.f;
+  if (o.cpos >= 0) {
+    // lane l of wave 0 adds partials [16 l, 16 l + 16) in index order, thread 0 the 64 sums in
+    // index order: the same association in every block and every run
+    if (threadIdx.x < 64) {
+      double t = 0.0;
+      for (int i = threadIdx.x * (kCjMaxParts / 64); i < (threadIdx.x + 1) * (kCjMaxParts / 64); ++i)
+        if (i < nparts) t += (double)part[i];
+      chunk[threadIdx.x] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double t = 0.0;
+      for (int i = 0; i < 64; ++i) t += chunk[i];
+      mean = (float)(t / (double)npix);
+    }
+    __syncthreads();
+    m = mean;
+  }
+  const long ngroups = npix / kCjPix;
+  for (long gi = blockIdx.x * (long)blockDim.x + threadIdx.x; gi < ngroups; gi += (long)gridDim.x * blockDim.x) {
+    float a[12];
+    cj_load<S, VEC>(src, gi, a);
+    cj_prefix<kCjPix>(a, o, o.n, m);
+    if constexpr (VEC) {
+      f32x4* q = (f32x4*)dst + gi * 3;
+      q[0] = f32x4{a[0], a[1], a[2], a[3]};
+      q[1] = f32x4{a[4], a[5], a[6], a[7]};
+      q[2] = f32x4{a[8], a[9], a[10], a[11]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 12; ++j) dst[gi * 12 + j] = a[j];
+    }
+  }
+  const long tail = ngroups * kCjPix + threadIdx.x;
+  if (blockIdx.x == 0 && tail < npix) {
+    float p[3] = {(float)src[tail * 3], (float)src[tail * 3 + 1], (float)src[tail * 3 + 2]};
+    cj_prefix<1>(p, o, o.n, m);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) dst[tail * 3 + ch] = p[ch];
+  }
+}
+
+static int cj_parts(long npix) {
+  return (int)std::max<long>(1, std::min<long>(kCjMaxParts, (npix / kCjPix + 255) / 256));
+}
+
+template <typename S, bool VEC>
+static void cj_launch(const void* src, float* dst, long npix, float* part, const CjOps& o, hipStream_t st) {
+  const int nparts = cj_parts(npix);
+  if (o.cpos >= 0)
+    hipLaunchKernelGGL((cj_mean_kernel<S, VEC>), dim3(nparts), dim3(256), 0, st, (const S*)src, part, npix, o);
+  const int blocks = (int)std::max<long>(1, std::min<long>(2048, (npix / kCjPix + 255) / 256));
+  hipLaunchKernelGGL((cj_apply_kernel<S, VEC>), dim3(blocks), dim3(256), 0, st, (const S*)src, dst, npix, part, nparts, o);
+}
+
+extern "C" size_t rtsds_color_jitter_workspace(int h, int w) {
+  if (h <= 0 || w <= 0) return 0;
+  return al256((size_t)cj_parts((long)h * w) * sizeof(float));
+}
+
+extern "C" int rtsds_color_jitter(const void* src, int src_u8, float* dst, int c, int h, int w, const int* order, int mask,
+                                  float fb, float fc, float fs, float fh, float bound, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  if (c <= 0 || h <= 0 || w <= 0 || !src || !dst || !order || mask < 0 || mask > 15) return RTSDS_ERR_SHAPE;
+  int seen = 0;
+  for (int k = 0; k < 4; ++k) {
+    if (order[k] < 0 || order[k] > 3 || (seen >> order[k] & 1)) return RTSDS_ERR_SHAPE;
+    seen |= 1 << order[k];
+  }
+  if (!(fb >= 0.f) || !(fc >= 0.f) || !(fs >= 0.f) || !(fh >= -0.5f && fh <= 0.5f) || !(bound > 0.f)) return RTSDS_ERR_SHAPE;
+  if (c != 3) return RTSDS_ERR_UNSUPPORTED;
+  const float factor[4] = {fb, fc, fs, fh};
+  CjOps o = {0, -1, {0, 0, 0, 0}, {1.f, 1.f, 1.f, 1.f}, bound, 1.f / bound};
+  for (int k = 0; k < 4; ++k) {  // the enabled ops in application order (none: dst = float(src))
+    if (!(mask >> order[k] & 1)) continue;
+    if (order[k] == 1) o.cpos = o.n;
+    o.id[o.n] = order[k];
+    o.f[o.n++] = factor[order[k]];
+  }
+  if (o.cpos >= 0 && (!ws || ws_bytes < rtsds_color_jitter_workspace(h, w))) return RTSDS_ERR_WORKSPACE;
+  const long npix = (long)h * w;
+  const bool vec = (uintptr_t)dst % 16 == 0 && (uintptr_t)src % (src_u8 ? 4 : 16) == 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (src_u8) {
+    if (vec) cj_launch<uint8_t, true>(src, dst, npix, (float*)ws, o, st);
+    else cj_launch<uint8_t, false>(src, dst, npix, (float*)ws, o, st);
+  } else {
+    if (vec) cj_launch<float, true>(src, dst, npix, (float*)ws, o, st);
+    else cj_launch<float, false>(src, dst, npix, (float*)ws, o, st);
+  }
   RET_LAUNCH();
 }
 

@@ -5,16 +5,22 @@ Reference pipelines (main.py:60-96), reproduced here per sample of a batch:
 
 * Cityscapes image:  Resize(image_size, antialias=True) -> Normalize(mean, std)
 * Cityscapes label:  Resize(image_size, antialias=True) -> IntRangeTransformer(0, num_classes)
-* GTA5 image:        [RandomApply([GaussianBlur(k, sigma), RandomHorizontalFlip(p)], p)] ->
-                     Resize(image_size) -> Normalize(mean, std)
+* GTA5 image:        [RandomApply([GaussianBlur(k, sigma), RandomHorizontalFlip(p),
+                     ColorJitter(b, c, s, h)], p)] -> Resize(image_size) -> Normalize(mean, std);
+                     blur and jitter run in the order the config lists them (they do not
+                     commute, because of the clamps); the flip commutes with both and stays
+                     fused into the resize
 * GTA5 label:        Resize(image_size)   (the augmentation flips the image only, as the
                      reference's pipeline does)
 
 The image comes out in the network's input layout (NHWC, the runtime compute dtype), so the
 model's input packing is a no-op; labels come out int64 [N, 1, H, W] as the reference's loaders
 deliver them (train.py squeezes dim 1).  Random decisions draw from torch's CPU generator in
-torchvision's call order (RandomApply's coin, GaussianBlur's sigma, the flip coin).
+torchvision's call order (RandomApply's coin, then per listed transform: GaussianBlur's sigma,
+the flip coin, ColorJitter's permutation and factors).
 """
+import ctypes
+
 import torch
 
 from ._lib import lib
@@ -48,6 +54,51 @@ class RandomHorizontalFlip:
         self.p = p
 
 
+def _jitter_range(name, value, center, lo_bound, hi_bound):
+    """torchvision ColorJitter._check_input: a number x means [center - x, center + x] (floored
+    at 0 around center 1), a pair is taken as given; None when the range is the identity."""
+    if isinstance(value, bool):
+        raise ValueError(f"{name} should be a single number or a sequence of two numbers.")
+    if isinstance(value, (int, float)):
+        if value < 0:
+            raise ValueError(f"If {name} is a single number, it must be non negative.")
+        rng = [center - float(value), center + float(value)]
+        if center == 1:
+            rng[0] = max(rng[0], 0.0)
+    elif isinstance(value, (tuple, list)) and len(value) == 2 and \
+            all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in value):
+        rng = [float(value[0]), float(value[1])]
+    else:
+        raise ValueError(f"{name} should be a single number or a sequence of two numbers.")
+    if not lo_bound <= rng[0] <= rng[1] <= hi_bound:
+        raise ValueError(f"{name} values should be ordered and between {lo_bound} and {hi_bound}, got {rng}.")
+    return None if rng[0] == rng[1] == center else (rng[0], rng[1])
+
+
+class ColorJitter:
+    """torchvision ColorJitter(brightness, contrast, saturation, hue): per call a permutation of
+    the four adjustments and one factor for each that is on.  ``value_range`` is the image's
+    scale (the clamp bound): 255 for the decoded images of this pipeline, 1 for torchvision's
+    float convention."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, value_range=255.0):
+        inf = float("inf")
+        self.brightness = _jitter_range("brightness", brightness, 1, 0.0, inf)
+        self.contrast = _jitter_range("contrast", contrast, 1, 0.0, inf)
+        self.saturation = _jitter_range("saturation", saturation, 1, 0.0, inf)
+        self.hue = _jitter_range("hue", hue, 0, -0.5, 0.5)
+        if not value_range > 0:
+            raise ValueError("value_range should be positive.")
+        self.value_range = float(value_range)
+
+    def params(self):
+        """(order, fb, fc, fs, fh) in get_params' draw order; None for an op that is off."""
+        order = tuple(int(i) for i in torch.randperm(4))
+        fs = tuple(None if r is None else float(torch.empty(1).uniform_(r[0], r[1]))
+                   for r in (self.brightness, self.contrast, self.saturation, self.hue))
+        return (order,) + fs
+
+
 class RandomApply:
     """RandomApply(transforms, p): the listed transforms all run with probability p."""
 
@@ -67,25 +118,54 @@ def augmentation_loader(config, probability):
                                     sigma=[float(i) for i in str(c["sigma"]).split(",")]))
         elif key == "RandomHorizontalFlip":
             out.append(RandomHorizontalFlip(p=aug["RandomHorizontalFlip"]["p"]))
-        elif key in ("ColorJitter", "ColorJitterWithRandomBrightness"):
-            raise NotImplementedError("rtsds_amd.transforms: ColorJitter is not implemented (the reference "
-                                      "config has it commented out, config.yaml:111-123)")
+        elif key == "ColorJitter":
+            c = aug["ColorJitter"]
+            out.append(ColorJitter(brightness=c["brightness"], contrast=c["contrast"], saturation=c["saturation"],
+                                   hue=c["hue"]))
+        elif key == "ColorJitterWithRandomBrightness":
+            raise NotImplementedError("rtsds_amd.transforms: ColorJitterWithRandomBrightness is not implemented "
+                                      "(the reference config has it commented out, config.yaml:118-123)")
     return RandomApply(out, p=probability)
 
 
 def _decisions(augment):
-    """(blur sigma or None, flip) for one sample, drawing in torchvision's order."""
+    """([(transform, its draw)] for the blur / jitter in list order, flip) for one sample,
+    drawing in torchvision's order."""
     if augment is None or not augment.transforms:
-        return None, False
+        return [], False
     if augment.p < torch.rand(1):
-        return None, False
-    sigma, flip = None, False
+        return [], False
+    ops, flip = [], False
     for t in augment.transforms:
-        if isinstance(t, GaussianBlur):
-            sigma = (t, t.params())
+        if isinstance(t, (GaussianBlur, ColorJitter)):
+            ops.append((t, t.params()))
         elif isinstance(t, RandomHorizontalFlip):
             flip = bool(torch.rand(1) < t.p)
-    return sigma, flip
+    return ops, flip
+
+
+def color_jitter(img, order, fb, fc, fs, fh, value_range=255.0, out=None):
+    """ColorJitter's forward with the draws given: the adjustments 0 brightness, 1 contrast,
+    2 saturation, 3 hue applied in ``order`` with their factors (None = off) to an HWC RGB
+    device image (uint8, or fp32 in [0, value_range]).  fp32 HWC out; ``out`` may be ``img``
+    itself when that is fp32."""
+    if img.dtype not in (torch.uint8, torch.float32) or img.dim() != 3 or not img.is_contiguous():
+        raise RuntimeError("rtsds_amd.transforms: color_jitter takes a contiguous HWC uint8 or fp32 image")
+    h, w, c = img.shape
+    if out is None:
+        out = torch.empty((h, w, c), dtype=torch.float32, device=img.device)
+    elif out.dtype != torch.float32 or out.shape != img.shape or not out.is_contiguous() or out.device != img.device:
+        raise RuntimeError("rtsds_amd.transforms: color_jitter writes a contiguous fp32 image of the source's shape")
+    factors = (fb, fc, fs, fh)
+    mask = sum(1 << k for k, f in enumerate(factors) if f is not None)
+    fb, fc, fs, fh = (ident if f is None else f for f, ident in zip(factors, (1.0, 1.0, 1.0, 0.0)))
+    # contrast: the partial sums of the grey mean
+    ws = workspace(lib.rtsds_color_jitter_workspace(h, w), img.device) if mask & 2 else None
+    _check(lib.rtsds_color_jitter(img.data_ptr(), int(img.dtype == torch.uint8), out.data_ptr(), c, h, w,
+                                  (ctypes.c_int * 4)(*order), mask, fb, fc, fs, fh, value_range,
+                                  ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
+                                  stream()), "color jitter")
+    return out
 
 
 def _as_hwc_u8(img):
@@ -123,13 +203,16 @@ class ImagePipeline:
             img = _as_hwc_u8(img)
             h, w, c = img.shape
             src, src_u8 = img, 1
-            sigma, flip = _decisions(self.augment)
-            if sigma is not None:
-                blur, s = sigma
-                src = torch.empty((h, w, c), dtype=torch.float32, device=dev)
-                _check(lib.rtsds_gaussian_blur(img.data_ptr(), 1, src.data_ptr(), c, h, w, blur.kernel_size[0],
-                                               blur.kernel_size[1], s, s, stream()), "gaussian blur")
-                src_u8 = 0
+            ops, flip = _decisions(self.augment)
+            for t, drawn in ops:
+                if isinstance(t, GaussianBlur):
+                    dstf = torch.empty((h, w, c), dtype=torch.float32, device=dev)
+                    _check(lib.rtsds_gaussian_blur(src.data_ptr(), src_u8, dstf.data_ptr(), c, h, w, t.kernel_size[0],
+                                                   t.kernel_size[1], drawn, drawn, stream()), "gaussian blur")
+                else:  # ColorJitter: in place in an fp32 intermediate, else straight from the uint8 image
+                    dstf = torch.empty((h, w, c), dtype=torch.float32, device=dev) if src_u8 else src
+                    color_jitter(src, *drawn, value_range=t.value_range, out=dstf)
+                src, src_u8 = dstf, 0
             ws = workspace(lib.rtsds_resize_aa_workspace(c, h, w, ho, wo), dev)
             dst = out[n].permute(1, 2, 0)  # this image's HWC slot of the NHWC batch
             _check(lib.rtsds_resize_aa(src.data_ptr(), src_u8, c, h, w, dst.data_ptr(),
@@ -219,5 +302,5 @@ def parse_size(s):
     return [int(v) for v in str(s).split(",")]
 
 
-__all__ = ["ImagePipeline", "LabelPipeline", "DeviceLoader", "GaussianBlur", "RandomHorizontalFlip", "RandomApply",
-           "augmentation_loader", "decode_gta5_labels", "collate_raw", "parse_size"]
+__all__ = ["ImagePipeline", "LabelPipeline", "DeviceLoader", "GaussianBlur", "RandomHorizontalFlip", "ColorJitter",
+           "RandomApply", "augmentation_loader", "color_jitter", "decode_gta5_labels", "collate_raw", "parse_size"]
