@@ -14,13 +14,32 @@ static const int kBnMaxRB = 2048;  // row blocks of the partial-statistics pass
 static const int kBnTinyRows = 64;  // up to this many rows: one block per channel finalizes and applies
 
 // Threads of a 256-block are laid out [row group][channel vector]; TPR = threads per row.
+// Host and device: the launch planning (bn_need) divides the rows by the kernels' own arithmetic.
 template <int VEC> struct BnLayout {
   int tpr, rpi;  // threads per row, rows per block iteration
-  RT_DEV BnLayout(int c) {
+  __host__ __device__ BnLayout(int c) {
     tpr = (c + VEC - 1) / VEC;
     if (tpr > 256) tpr = 256;
     rpi = 256 / tpr;
   }
+};
+// A thread's place in grid (row blocks, blocks of 256 * VEC channels): channel vector cv of row
+// group rg; channels ch0 .. ch0 + VEC - 1, of which cvalid exist; rows row0(), row0() + step(), ...
+template <int VEC> struct BnTile : BnLayout<VEC> {
+  int cl, cv, rg, ch0, cvalid;  // cl: channels of this block
+  bool col, active;             // col: the channel vector exists; active: its row group too
+  RT_DEV static int block_channels(int c) { return min(c - (int)blockIdx.y * 256 * VEC, 256 * VEC); }
+  RT_DEV BnTile(int c) : BnLayout<VEC>(block_channels(c)) {
+    cl = block_channels(c);
+    cv = threadIdx.x % this->tpr;
+    rg = threadIdx.x / this->tpr;
+    ch0 = blockIdx.y * 256 * VEC + cv * VEC;
+    cvalid = c - ch0;
+    col = cv * VEC < cl;
+    active = rg < this->rpi && col;
+  }
+  RT_DEV long row0() const { return (long)blockIdx.x * this->rpi + rg; }
+  RT_DEV long step() const { return (long)gridDim.x * this->rpi; }
 };
 
 // VEC is either the 16-B vector width (dispatched only when c % VEC == 0, so an active thread's
@@ -70,26 +89,22 @@ RT_DEV void chan_merge(float& na, float& ma, float& Ma, float nb, float mb, floa
 template <typename T, int VEC>
 __global__ void __launch_bounds__(256) bn_stats_kernel(const T* __restrict__ x, float* __restrict__ part, long rows, int c) {
   __shared__ float sh[3][256][VEC];
-  const int cbase = blockIdx.y * 256 * VEC;
-  const int cl = min(c - cbase, 256 * VEC);
-  const BnLayout<VEC> L(cl);
-  const int tid = threadIdx.x, cv = tid % L.tpr, rg = tid / L.tpr;
-  const int ch0 = cbase + cv * VEC;
-  const bool active = rg < L.rpi && cv * VEC < cl;
+  const BnTile<VEC> t(c);
+  const int tid = threadIdx.x, ch0 = t.ch0;
   float cnt = 0.f, shift[VEC], s1[VEC], s2[VEC];
 #pragma unroll
   for (int j = 0; j < VEC; ++j) { shift[j] = 0.f; s1[j] = 0.f; s2[j] = 0.f; }
-  if (active) {
-    long r = (long)blockIdx.x * L.rpi + rg;
-    const long step = (long)gridDim.x * L.rpi;
+  if (t.active) {
+    long r = t.row0();
+    const long step = t.step();
     if (r < rows) {
-      load_vec<T, VEC>(x + r * c + ch0, shift, c - ch0);
+      load_vec<T, VEC>(x + r * c + ch0, shift, t.cvalid);
       cnt = 1.f;
       r += step;
     }
     for (; r < rows; r += step) {
       float v[VEC];
-      load_vec<T, VEC>(x + r * c + ch0, v, c - ch0);
+      load_vec<T, VEC>(x + r * c + ch0, v, t.cvalid);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         const float d = v[j] - shift[j];
@@ -109,13 +124,13 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(const T* __restrict__ x, 
     sh[2][tid][j] = fmaxf(m2, 0.f);
   }
   __syncthreads();
-  if (rg == 0 && cv * VEC < cl) {
+  if (t.rg == 0 && t.col) {
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
       float n = sh[0][tid][j], m = sh[1][tid][j], M = sh[2][tid][j];
-      for (int g = 1; g < L.rpi; ++g) {
-        const int t = g * L.tpr + cv;
-        chan_merge(n, m, M, sh[0][t][j], sh[1][t][j], sh[2][t][j]);
+      for (int g = 1; g < t.rpi; ++g) {
+        const int o = g * t.tpr + t.cv;
+        chan_merge(n, m, M, sh[0][o][j], sh[1][o][j], sh[2][o][j]);
       }
       if (ch0 + j < c) {
         *(f32x4*)(part + ((long)(ch0 + j) * gridDim.x + blockIdx.x) * 4) = f32x4{n, m, M, 0.f};
@@ -271,17 +286,17 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const T* __restrict__ x, 
                                                         const float* __restrict__ scale, const float* __restrict__ shift,
                                                         long rows, int c, int act_rt, long ldy) {
   const int act = ACT >= 0 ? ACT : act_rt;
-  const int cbase = blockIdx.y * 256 * VEC;
-  const int cl = min(c - cbase, 256 * VEC);
-  const BnLayout<VEC> L(cl);
-  const int tid = threadIdx.x, cv = tid % L.tpr, rg = tid / L.tpr;
-  if (rg >= L.rpi || cv * VEC >= cl) return;
-  const int ch0 = cbase + cv * VEC, cvalid = c - ch0;
+  const BnTile<VEC> t(c);
+  if (!t.active) return;
   float sc[VEC], sh[VEC];
-  load_coef<VEC>(scale, ch0, c, sc);
-  load_coef<VEC>(shift, ch0, c, sh);
-  const long step = (long)gridDim.x * L.rpi;
-  long r = (long)blockIdx.x * L.rpi + rg;
+  load_coef<VEC>(scale, t.ch0, c, sc);
+  load_coef<VEC>(shift, t.ch0, c, sh);
+  const int ch0 = t.ch0, cvalid = t.cvalid;
+  const long step = t.step();
+  long r = t.row0();
+  // The row body stays written twice (two rows, then one): split into a load and a finish phase
+  // per row, the compiler sinks the second row's loads behind the first row's wait whenever
+  // there is a residual.
   for (; r + step < rows; r += 2 * step) {  // two independent rows in flight per thread
     float v0[VEC], v1[VEC], r0[VEC], r1[VEC];
     load_vec<T, VEC>(x + r * c + ch0, v0, cvalid);
@@ -314,23 +329,17 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const T* __restrict__ x, 
   }
 }
 
-// Activation derivative from either the saved output y, or -- when y is not kept (no
-// residual, monotone activation with act'(v) determined by sign(v)) -- from the recomputed
-// pre-activation x*scale+shift, which is bit-identical to the forward's.
-template <typename T, int VEC>
-RT_DEV void bn_act_grad(float* g, const T* y, const float* xv, const float* sc, const float* sh, int act, int cvalid) {
+// g *= act'(.): the activation derivative from the saved output's values yv (HAS_Y), or -- when y
+// is not kept (no residual, monotone activation with act'(v) determined by sign(v)) -- from the
+// sign of the recomputed pre-activation x*scale+shift, which is bit-identical to the forward's.
+// The one mask of the statistics loop and the apply passes.
+template <int VEC, bool HAS_Y>
+RT_DEV void bn_mask(float* g, const float* yv, const float* xv, const float* sc, const float* sh, int act) {
   if (!act) return;
-  if (y) {
-    float yv[VEC];
-    load_vec<T, VEC>(y, yv, cvalid);
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) g[j] *= act_grad(yv[j], act);
-  } else {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      const bool pos = fmaf(xv[j], sc[j], sh[j]) > 0.f;
-      g[j] = pos ? g[j] : (act == RTSDS_ACT_LEAKY ? 0.2f * g[j] : 0.f);
-    }
+  for (int j = 0; j < VEC; ++j) {
+    if constexpr (HAS_Y) g[j] *= act_grad(yv[j], act);
+    else g[j] = fmaf(xv[j], sc[j], sh[j]) > 0.f ? g[j] : (act == RTSDS_ACT_LEAKY ? 0.2f * g[j] : 0.f);
   }
 }
 
@@ -383,15 +392,183 @@ struct GradPool {
   }
 };
 
+// A thread's per-channel backward coefficients: dx = a*g + b*(x - mu) + k, and the forward's
+// sc / sh for the mask recomputed from x.
+template <int VEC> struct BnDx {
+  float a[VEC], b[VEC], k[VEC], mu[VEC], sc[VEC], sh[VEC];
+};
 template <int VEC>
 RT_DEV void bn_bwd_coef(int ch0, int c, const float* gamma, const float* beta, const float* mean, const float* sinv,
-                        float* mu, float* sc, float* sh) {
+                        BnDx<VEC>& k) {
 #pragma unroll
   for (int j = 0; j < VEC; ++j) {
     const int ch = min(ch0 + j, c - 1);
-    mu[j] = mean[ch];
-    bn_coef(gamma ? gamma[ch] : 1.f, beta ? beta[ch] : 0.f, mu[j], sinv[ch], sc[j], sh[j]);
+    k.mu[j] = mean[ch];
+    bn_coef(gamma ? gamma[ch] : 1.f, beta ? beta[ch] : 0.f, k.mu[j], sinv[ch], k.sc[j], k.sh[j]);
   }
+}
+
+// The backward statistics loop over the rows r0, r0 + step, ... of a thread's channel vector:
+// sg += g, sgx += g * (x - mean), with g = dy * act'(.) (bn_mask).  kBnU rows are in flight per
+// thread (loads issued before any use).  gout (HAS_Y, may be null): g is also stored.  g_last /
+// xv_last (may be null): receive the last iteration's masked g and its x (rows past the end:
+// g = 0), for a caller that applies from registers.
+constexpr int kBnU = 2;
+template <typename T, int VEC, bool HAS_Y, class GS>
+RT_DEV void bn_bwd_sums(const GS& gs, const T* __restrict__ x, const T* __restrict__ y, T* __restrict__ gout, long r0,
+                        long step, long rows, int c, const BnTile<VEC>& t, const BnDx<VEC>& k, int act, float* sg,
+                        float* sgx, float (*g_last)[VEC], float (*xv_last)[VEC]) {
+  const int ch0 = t.ch0;
+  for (long r = r0; r < rows; r += kBnU * step) {
+    // (loop-local: arrays owned by the caller cost bn_bwd_stats_kernel registers)
+    float g[kBnU][VEC], xv[kBnU][VEC], yv[HAS_Y ? kBnU : 1][VEC];
+#pragma unroll
+    for (int u = 0; u < kBnU; ++u) {
+      // clamped, unconditional loads (all rows in flight together); rows past the end
+      // contribute g = 0
+      const long rr = min(r + u * step, rows - 1);
+      gs.template load<VEC>(rr, ch0, g[u], t.cvalid);
+      load_vec<T, VEC>(x + rr * c + ch0, xv[u], t.cvalid);
+      if constexpr (HAS_Y) load_vec<T, VEC>(y + rr * c + ch0, yv[u], t.cvalid);
+    }
+#pragma unroll
+    for (int u = 0; u < kBnU; ++u)
+      if (r + u * step >= rows) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) g[u][j] = 0.f;
+      }
+#pragma unroll
+    for (int u = 0; u < kBnU; ++u) {
+      bn_mask<VEC, HAS_Y>(g[u], yv[HAS_Y ? u : 0], xv[u], k.sc, k.sh, act);
+      if (HAS_Y && gout && r + u * step < rows) store_vec<T, VEC>(gout + (r + u * step) * c + ch0, g[u], t.cvalid);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        sg[j] += g[u][j];
+        sgx[j] = fmaf(g[u][j], xv[u][j] - k.mu[j], sgx[j]);
+        if (g_last) { g_last[u][j] = g[u][j]; xv_last[u][j] = xv[u][j]; }
+      }
+    }
+  }
+}
+
+// Sums sg / sgx over the block's row groups, in place.  True in the threads that then hold their
+// channel vector's block totals (the first row group's: threadIdx.x == cv).
+template <int VEC>
+RT_DEV bool bn_bwd_block_sum(const BnTile<VEC>& t, float (*red)[256][VEC], float* sg, float* sgx) {
+  const int tid = threadIdx.x;
+  if ((t.tpr & (t.tpr - 1)) == 0 && t.tpr <= 64) {
+    // power-of-two row width: sum the wave's rows with xor shuffles (lanes l and l ^ (tpr << i)
+    // hold the same channel vector), then the four wave sums through LDS -- a per-block tail of
+    // a few hundred cycles instead of a serial LDS loop over all rpi rows.
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int o = t.tpr; o < 64; o <<= 1) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        sg[j] += __shfl_xor(sg[j], o, 64);
+        sgx[j] += __shfl_xor(sgx[j], o, 64);
+      }
+    }
+    if (lane < t.tpr) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) { red[0][wave * 64 + lane][j] = sg[j]; red[1][wave * 64 + lane][j] = sgx[j]; }
+    }
+    __syncthreads();
+    if (tid >= t.tpr || tid * VEC >= t.cl) return false;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      sg[j] = (red[0][tid][j] + red[0][64 + tid][j]) + (red[0][128 + tid][j] + red[0][192 + tid][j]);
+      sgx[j] = (red[1][tid][j] + red[1][64 + tid][j]) + (red[1][128 + tid][j] + red[1][192 + tid][j]);
+    }
+    return true;
+  }
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) { red[0][tid][j] = sg[j]; red[1][tid][j] = sgx[j]; }
+  __syncthreads();
+  if (t.rg != 0 || !t.col) return false;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    float a = red[0][tid][j], b = red[1][tid][j];
+    for (int gi = 1; gi < t.rpi; ++gi) {
+      a += red[0][gi * t.tpr + t.cv][j];
+      b += red[1][gi * t.tpr + t.cv][j];
+    }
+    sg[j] = a;
+    sgx[j] = b;
+  }
+  return true;
+}
+
+// The backward finalize of one channel: its operands, loaded up front (in flight with the
+// partials, see bn_finalize_body), and the tail that turns the channel's (sum g, sum g*(x-mean))
+// into dgamma, dbeta and the coefficients A, B, C of dx = A*g + B*(x-mean) + C.
+struct BnBwdOps {
+  float inv = 0.f, g = 1.f, bt = 0.f, mu = 0.f, dg0 = 0.f, db0 = 0.f;
+};
+RT_DEV BnBwdOps bn_bwd_ops(int ch, const float* gamma, const float* beta, const float* smean, const float* sinv,
+                           const float* dgamma, const float* dbeta, int accumulate) {
+  BnBwdOps o;
+  o.inv = sinv[ch];
+  o.mu = smean[ch];
+  if (gamma) o.g = gamma[ch];
+  if (beta) o.bt = beta[ch];
+  if (accumulate && dgamma) o.dg0 = dgamma[ch];
+  if (accumulate && dbeta) o.db0 = dbeta[ch];
+  return o;
+}
+RT_DEV void bn_bwd_tail(const BnBwdOps& o, float sg, float sgx, int ch, long rows, int training, int accumulate,
+                        float* dgamma, float* dbeta, float& A, float& B, float& C) {
+  const float inv = o.inv;
+  if (dgamma) dgamma[ch] = accumulate ? o.dg0 + sgx * inv : sgx * inv;
+  if (dbeta) dbeta[ch] = accumulate ? o.db0 + sg : sg;
+  const float a = o.g * inv;
+  const float invn = 1.f / (float)rows;
+  A = a;
+  B = training ? -a * inv * inv * sgx * invn : 0.f;
+  C = training ? -a * sg * invn : 0.f;
+}
+// ... and the six coefficient rows of the apply pass:
+// coef = [A | B | C | mean | scale | shift] x c  (the last three for the mask recompute).
+RT_DEV void bn_bwd_coef_rows(const BnBwdOps& o, float sg, float sgx, int ch, int c, long rows, int training, int accumulate,
+                             float* dgamma, float* dbeta, float* coef) {
+  bn_bwd_tail(o, sg, sgx, ch, rows, training, accumulate, dgamma, dbeta, coef[ch], coef[c + ch], coef[2 * c + ch]);
+  coef[3 * c + ch] = o.mu;
+  bn_coef(o.g, o.bt, o.mu, o.inv, coef[4 * c + ch], coef[5 * c + ch]);
+}
+
+// The backward apply's row pieces: dx = a*g + b*(x - mu) + k, dres = g.
+// The mask of one row; y: the row of the stored output (null: recomputed from x).
+template <typename T, int VEC>
+RT_DEV void bn_row_mask(float* g, const T* __restrict__ y, const float* xv, const BnDx<VEC>& k, int act, int cvalid) {
+  if (!act) return;
+  if (y) {
+    float yv[VEC];
+    load_vec<T, VEC>(y, yv, cvalid);
+    bn_mask<VEC, true>(g, yv, xv, k.sc, k.sh, act);
+  } else {
+    bn_mask<VEC, false>(g, nullptr, xv, k.sc, k.sh, act);
+  }
+}
+template <int VEC>
+RT_DEV float bn_bwd_dx(const BnDx<VEC>& k, int j, float g, float x) { return fmaf(k.a[j], g, fmaf(k.b[j], x - k.mu[j], k.k[j])); }
+// dx (in place of xv) and dres of one row from its masked g and x; off = r * c + ch0
+template <typename T, int VEC>
+RT_DEV void bn_bwd_row_store(T* __restrict__ dx, T* __restrict__ dres, long off, const BnDx<VEC>& k, int cvalid, const float* g,
+                             float* xv) {
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) xv[j] = bn_bwd_dx<VEC>(k, j, g[j], xv[j]);
+  if (dx) store_vec<T, VEC>(dx + off, xv, cvalid);
+  if (dres) store_vec<T, VEC>(dres + off, g, cvalid);
+}
+// One whole row r: load, mask, store.
+template <typename T, int VEC, class GS>
+RT_DEV void bn_bwd_row(const GS& gs, const T* __restrict__ x, const T* __restrict__ y, T* __restrict__ dx, T* __restrict__ dres,
+                       long r, int c, const BnTile<VEC>& t, const BnDx<VEC>& k, int act) {
+  const long off = r * c + t.ch0;
+  float g[VEC], xv[VEC];
+  gs.template load<VEC>(r, t.ch0, g, t.cvalid);
+  load_vec<T, VEC>(x + off, xv, t.cvalid);
+  bn_row_mask<T, VEC>(g, y ? y + off : nullptr, xv, k, act, t.cvalid);
+  bn_bwd_row_store<T, VEC>(dx, dres, off, k, t.cvalid, g, xv);
 }
 
 // Backward pass 1: part[(rb*c+ch)*2 + {0,1}] = (sum g, sum g*(x-mean)) with g = dy*act'(y) --
@@ -409,98 +586,19 @@ __global__ void __launch_bounds__(256) bn_bwd_stats_kernel(const GS gs, const T*
                                                             long rows, int c, int act_rt, T* __restrict__ gout) {
   const int act = ACT >= 0 ? ACT : act_rt;
   __shared__ float red[2][256][VEC];
-  const int cbase = blockIdx.y * 256 * VEC;
-  const int cl = min(c - cbase, 256 * VEC);
-  const BnLayout<VEC> L(cl);
-  const int tid = threadIdx.x, cv = tid % L.tpr, rg = tid / L.tpr;
-  const int ch0 = cbase + cv * VEC;
-  const bool active = rg < L.rpi && cv * VEC < cl;
-  float sg[VEC], sgx[VEC], mu[VEC], sc[VEC], sh[VEC];
+  const BnTile<VEC> t(c);
+  BnDx<VEC> k;
+  float sg[VEC], sgx[VEC];
 #pragma unroll
   for (int j = 0; j < VEC; ++j) { sg[j] = 0.f; sgx[j] = 0.f; }
-  if (active) {
-    bn_bwd_coef<VEC>(ch0, c, gamma, beta, mean, sinv, mu, sc, sh);
-    const long step = (long)gridDim.x * L.rpi;
-    constexpr int U = 2;  // rows in flight per thread (loads issued before any use)
-    for (long r = (long)blockIdx.x * L.rpi + rg; r < rows; r += U * step) {
-      float g[U][VEC], xv[U][VEC], yv[HAS_Y ? U : 1][VEC];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        // clamped, unconditional loads (all U rows in flight together); rows past the end
-        // contribute g = 0
-        const long rr = min(r + u * step, rows - 1);
-        gs.template load<VEC>(rr, ch0, g[u], c - ch0);
-        load_vec<T, VEC>(x + rr * c + ch0, xv[u], c - ch0);
-        if constexpr (HAS_Y) load_vec<T, VEC>(y + rr * c + ch0, yv[u], c - ch0);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (r + u * step >= rows) {
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) g[u][j] = 0.f;
-        }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (act) {
-#pragma unroll
-          for (int j = 0; j < VEC; ++j)
-            g[u][j] *= HAS_Y ? act_grad(yv[HAS_Y ? u : 0][j], act)
-                             : (fmaf(xv[u][j], sc[j], sh[j]) > 0.f ? 1.f : (act == RTSDS_ACT_LEAKY ? 0.2f : 0.f));
-        }
-        if (HAS_Y && gout && r + u * step < rows) store_vec<T, VEC>(gout + (r + u * step) * c + ch0, g[u], c - ch0);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-          sg[j] += g[u][j];
-          sgx[j] = fmaf(g[u][j], xv[u][j] - mu[j], sgx[j]);
-        }
-      }
-    }
+  if (t.active) {
+    bn_bwd_coef<VEC>(t.ch0, c, gamma, beta, mean, sinv, k);
+    bn_bwd_sums<T, VEC, HAS_Y>(gs, x, y, gout, t.row0(), t.step(), rows, c, t, k, act, sg, sgx, nullptr, nullptr);
   }
-  if ((L.tpr & (L.tpr - 1)) == 0 && L.tpr <= 64) {
-    // power-of-two row width: sum the wave's rows with xor shuffles (lanes l and l ^ (tpr << i)
-    // hold the same channel vector), then the four wave sums through LDS -- a per-block tail of
-    // a few hundred cycles instead of a serial LDS loop over all rpi rows.
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int o = L.tpr; o < 64; o <<= 1) {
+  if (!bn_bwd_block_sum<VEC>(t, red, sg, sgx)) return;
 #pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        sg[j] += __shfl_xor(sg[j], o, 64);
-        sgx[j] += __shfl_xor(sgx[j], o, 64);
-      }
-    }
-    if (lane < L.tpr) {
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) { red[0][wave * 64 + lane][j] = sg[j]; red[1][wave * 64 + lane][j] = sgx[j]; }
-    }
-    __syncthreads();
-    if (tid < L.tpr && tid * VEC < cl) {
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        const float a = (red[0][tid][j] + red[0][64 + tid][j]) + (red[0][128 + tid][j] + red[0][192 + tid][j]);
-        const float b = (red[1][tid][j] + red[1][64 + tid][j]) + (red[1][128 + tid][j] + red[1][192 + tid][j]);
-        if (ch0 + j < c) {
-          *(float2*)(part + ((long)blockIdx.x * c + ch0 + j) * 2) = make_float2(a, b);
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) { red[0][tid][j] = sg[j]; red[1][tid][j] = sgx[j]; }
-  __syncthreads();
-  if (rg == 0 && cv * VEC < cl) {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      float a = red[0][tid][j], b = red[1][tid][j];
-      for (int gi = 1; gi < L.rpi; ++gi) {
-        a += red[0][gi * L.tpr + cv][j];
-        b += red[1][gi * L.tpr + cv][j];
-      }
-      if (ch0 + j < c) {
-        *(float2*)(part + ((long)blockIdx.x * c + ch0 + j) * 2) = make_float2(a, b);
-      }
-    }
-  }
+  for (int j = 0; j < VEC; ++j)
+    if (t.ch0 + j < c) *(float2*)(part + ((long)blockIdx.x * c + t.ch0 + j) * 2) = make_float2(sg[j], sgx[j]);
 }
 
 // All three backward passes in one launch when the statistics pass has a single row block
@@ -518,158 +616,50 @@ __global__ void __launch_bounds__(256) bn_bwd_tiny_kernel(const GS gs, const T* 
   const int act = ACT >= 0 ? ACT : act_rt;
   __shared__ float red[2][256][VEC];
   __shared__ float cf[3][256 * VEC];
-  const int cbase = blockIdx.y * 256 * VEC;
-  const int cl = min(c - cbase, 256 * VEC);
-  const BnLayout<VEC> L(cl);
-  const int tid = threadIdx.x, cv = tid % L.tpr, rg = tid / L.tpr;
-  const int ch0 = cbase + cv * VEC;
-  const bool active = rg < L.rpi && cv * VEC < cl;
-  float sg[VEC], sgx[VEC], mu[VEC], sc[VEC], sh[VEC];
-  constexpr int U = 2;
-  // rows <= U * rpi: the statistics loop runs once and its (masked) g and x stay in registers
+  const BnTile<VEC> t(c);
+  // rows <= kBnU * rpi: the statistics loop runs once and its (masked) g and x stay in registers
   // for the apply -- one memory round trip fewer
-  const bool one_pass = rows <= U * (long)L.rpi;
-  float g[U][VEC], xv[U][VEC];
-  // the accumulated parameter gradients and the finalize's operands, loaded up front
-  float dg0[VEC], db0[VEC], inv0[VEC], gm0[VEC];
+  const bool one_pass = rows <= kBnU * (long)t.rpi;
+  BnDx<VEC> k;
+  float sg[VEC], sgx[VEC], g[kBnU][VEC], xv[kBnU][VEC];
+  BnBwdOps ops[VEC];
 #pragma unroll
   for (int j = 0; j < VEC; ++j) {
     sg[j] = 0.f;
     sgx[j] = 0.f;
-    const int ch = min(ch0 + j, c - 1);
-    inv0[j] = sinv[ch];
-    gm0[j] = gamma ? gamma[ch] : 1.f;
-    dg0[j] = accumulate && dgamma ? dgamma[ch] : 0.f;
-    db0[j] = accumulate && dbeta ? dbeta[ch] : 0.f;
+    ops[j] = bn_bwd_ops(min(t.ch0 + j, c - 1), gamma, beta, mean, sinv, dgamma, dbeta, accumulate);
   }
-  if (active) {
-    bn_bwd_coef<VEC>(ch0, c, gamma, beta, mean, sinv, mu, sc, sh);
-    const long step = L.rpi;  // (one row block)
-    for (long r = rg; r < rows; r += U * step) {
-      float yv[HAS_Y ? U : 1][VEC];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const long rr = min(r + u * step, rows - 1);
-        gs.template load<VEC>(rr, ch0, g[u], c - ch0);
-        load_vec<T, VEC>(x + rr * c + ch0, xv[u], c - ch0);
-        if constexpr (HAS_Y) load_vec<T, VEC>(y + rr * c + ch0, yv[u], c - ch0);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (r + u * step >= rows) {
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) g[u][j] = 0.f;
-        }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (act) {
-#pragma unroll
-          for (int j = 0; j < VEC; ++j)
-            g[u][j] *= HAS_Y ? act_grad(yv[HAS_Y ? u : 0][j], act)
-                             : (fmaf(xv[u][j], sc[j], sh[j]) > 0.f ? 1.f : (act == RTSDS_ACT_LEAKY ? 0.2f : 0.f));
-        }
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-          sg[j] += g[u][j];
-          sgx[j] = fmaf(g[u][j], xv[u][j] - mu[j], sgx[j]);
-        }
-      }
-    }
+  if (t.active) {
+    bn_bwd_coef<VEC>(t.ch0, c, gamma, beta, mean, sinv, k);
+    bn_bwd_sums<T, VEC, HAS_Y>(gs, x, y, (T*)nullptr, t.rg, t.rpi, rows, c, t, k, act, sg, sgx, g, xv);  // (one row block)
   }
-  // the block sums (bn_bwd_stats_kernel's two reduction forms), then the single partial's finalize
-  float tg[VEC], tgx[VEC];
-  bool have = false;
-  if ((L.tpr & (L.tpr - 1)) == 0 && L.tpr <= 64) {
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int o = L.tpr; o < 64; o <<= 1) {
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        sg[j] += __shfl_xor(sg[j], o, 64);
-        sgx[j] += __shfl_xor(sgx[j], o, 64);
-      }
-    }
-    if (lane < L.tpr) {
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) { red[0][wave * 64 + lane][j] = sg[j]; red[1][wave * 64 + lane][j] = sgx[j]; }
-    }
-    __syncthreads();
-    if (tid < L.tpr && tid * VEC < cl) {
-      have = true;
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        tg[j] = (red[0][tid][j] + red[0][64 + tid][j]) + (red[0][128 + tid][j] + red[0][192 + tid][j]);
-        tgx[j] = (red[1][tid][j] + red[1][64 + tid][j]) + (red[1][128 + tid][j] + red[1][192 + tid][j]);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) { red[0][tid][j] = sg[j]; red[1][tid][j] = sgx[j]; }
-    __syncthreads();
-    if (rg == 0 && cv * VEC < cl) {
-      have = true;
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        float a = red[0][tid][j], b = red[1][tid][j];
-        for (int gi = 1; gi < L.rpi; ++gi) {
-          a += red[0][gi * L.tpr + cv][j];
-          b += red[1][gi * L.tpr + cv][j];
-        }
-        tg[j] = a;
-        tgx[j] = b;
-      }
-    }
-  }
-  if (have) {  // (tid == cv here: the first row group holds the channel vector)
+  if (bn_bwd_block_sum<VEC>(t, red, sg, sgx)) {
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      const int ch = ch0 + j;
+      const int ch = t.ch0 + j, o = t.cv * VEC + j;
       if (ch >= c) continue;
-      const float sgv = 0.f + tg[j], sgxv = 0.f + tgx[j];  // bn_bwd_finalize_rb_kernel: one partial
-      const float inv = inv0[j], gm = gm0[j];
-      if (dgamma) dgamma[ch] = accumulate ? dg0[j] + sgxv * inv : sgxv * inv;
-      if (dbeta) dbeta[ch] = accumulate ? db0[j] + sgv : sgv;
-      const float a = gm * inv;
-      const float invn = 1.f / (float)rows;
-      cf[0][cv * VEC + j] = a;
-      cf[1][cv * VEC + j] = training ? -a * inv * inv * sgxv * invn : 0.f;
-      cf[2][cv * VEC + j] = training ? -a * sgv * invn : 0.f;
+      // 0 + p: bn_bwd_finalize_rb_kernel's sum of one partial
+      bn_bwd_tail(ops[j], 0.f + sg[j], 0.f + sgx[j], ch, rows, training, accumulate, dgamma, dbeta, cf[0][o], cf[1][o],
+                  cf[2][o]);
     }
   }
   __syncthreads();
-  if (!active || (!dx && !dres)) return;
-  const int cvalid = c - ch0;
-  float ca[VEC], cb[VEC], ck[VEC];
+  if (!t.active || (!dx && !dres)) return;
 #pragma unroll
   for (int j = 0; j < VEC; ++j) {
-    ca[j] = cf[0][cv * VEC + j];
-    cb[j] = cf[1][cv * VEC + j];
-    ck[j] = cf[2][cv * VEC + j];
+    k.a[j] = cf[0][t.cv * VEC + j];
+    k.b[j] = cf[1][t.cv * VEC + j];
+    k.k[j] = cf[2][t.cv * VEC + j];
   }
   if (one_pass) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long r = rg + u * (long)L.rpi;
-      if (r >= rows) break;
-      const long off = r * c + ch0;
-      float o[VEC];
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) o[j] = fmaf(ca[j], g[u][j], fmaf(cb[j], xv[u][j] - mu[j], ck[j]));
-      if (dx) store_vec<T, VEC>(dx + off, o, cvalid);
-      if (dres) store_vec<T, VEC>(dres + off, g[u], cvalid);
+    for (int u = 0; u < kBnU; ++u) {
+      const long r = t.rg + u * (long)t.rpi, off = r * c + t.ch0;
+      if (r < rows) bn_bwd_row_store<T, VEC>(dx, dres, off, k, t.cvalid, g[u], xv[u]);
     }
     return;
   }
-  for (long r = rg; r < rows; r += L.rpi) {
-    const long off = r * c + ch0;
-    float gr[VEC], xr[VEC];
-    gs.template load<VEC>(r, ch0, gr, cvalid);
-    load_vec<T, VEC>(x + off, xr, cvalid);
-    bn_act_grad<T, VEC>(gr, HAS_Y ? y + off : nullptr, xr, sc, sh, act, cvalid);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) xr[j] = fmaf(ca[j], gr[j], fmaf(cb[j], xr[j] - mu[j], ck[j]));
-    if (dx) store_vec<T, VEC>(dx + off, xr, cvalid);
-    if (dres) store_vec<T, VEC>(dres + off, gr, cvalid);
-  }
+  for (long r = t.rg; r < rows; r += t.rpi) bn_bwd_row<T, VEC>(gs, x, HAS_Y ? y : (const T*)nullptr, dx, dres, r, c, t, k, act);
 }
 
 // Backward pass 2: coefficients  dx = A*g + B*(x-mean) + C  per channel (one wave each).
@@ -679,16 +669,8 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const float* __res
                                        float* coef, int training, int accumulate) {
   __shared__ float wr[4][2];
   const int ch = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // the tail's per-channel operands up front (see bn_finalize_kernel)
-  float inv = 0.f, g = 1.f, bt = 0.f, mu = 0.f, dg0 = 0.f, db0 = 0.f;
-  if (threadIdx.x == 0) {
-    inv = sinv[ch];
-    mu = smean[ch];
-    if (gamma) g = gamma[ch];
-    if (beta) bt = beta[ch];
-    if (accumulate && dgamma) dg0 = dgamma[ch];
-    if (accumulate && dbeta) db0 = dbeta[ch];
-  }
+  BnBwdOps ops;  // (thread 0 alone reads and writes the channel's operands)
+  if (threadIdx.x == 0) ops = bn_bwd_ops(ch, gamma, beta, smean, sinv, dgamma, dbeta, accumulate);
   float sg = 0.f, sgx = 0.f;
   for (int b0 = threadIdx.x; b0 < nrb; b0 += 256 * 8) {  // 8 partials in flight per thread
     float pg[8], px[8];
@@ -711,15 +693,7 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const float* __res
   if (threadIdx.x != 0) return;
   sg = (wr[0][0] + wr[1][0]) + (wr[2][0] + wr[3][0]);
   sgx = (wr[0][1] + wr[1][1]) + (wr[2][1] + wr[3][1]);
-  if (dgamma) dgamma[ch] = accumulate ? dg0 + sgx * inv : sgx * inv;
-  if (dbeta) dbeta[ch] = accumulate ? db0 + sg : sg;
-  const float a = g * inv;
-  const float invn = 1.f / (float)rows;
-  coef[ch] = a;
-  coef[c + ch] = training ? -a * inv * inv * sgx * invn : 0.f;
-  coef[2 * c + ch] = training ? -a * sg * invn : 0.f;
-  coef[3 * c + ch] = mu;
-  bn_coef(g, bt, mu, inv, coef[4 * c + ch], coef[5 * c + ch]);
+  bn_bwd_coef_rows(ops, sg, sgx, ch, c, rows, training, accumulate, dgamma, dbeta, coef);
 }
 
 // Backward pass 2 for the row-block-major partials of bn_bwd_stats_kernel: 16 channels per
@@ -733,16 +707,8 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_rb_kernel(const float* __
   __shared__ float wr[16][16][2];
   const int cl = threadIdx.x & 15, q = threadIdx.x >> 4, ch = blockIdx.x * 16 + cl;
   const int chc = min(ch, c - 1);
-  // the tail's per-channel operands up front (see bn_finalize_kernel)
-  float inv = 0.f, g = 1.f, bt = 0.f, mu = 0.f, dg0 = 0.f, db0 = 0.f;
-  if (q == 0) {
-    inv = sinv[chc];
-    mu = smean[chc];
-    if (gamma) g = gamma[chc];
-    if (beta) bt = beta[chc];
-    if (accumulate && dgamma) dg0 = dgamma[chc];
-    if (accumulate && dbeta) db0 = dbeta[chc];
-  }
+  BnBwdOps ops;
+  if (q == 0) ops = bn_bwd_ops(chc, gamma, beta, smean, sinv, dgamma, dbeta, accumulate);
   float sg = 0.f, sgx = 0.f;
   for (int b0 = q; b0 < nrb; b0 += 16 * 8) {
     float2 pv[8];
@@ -766,15 +732,7 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_rb_kernel(const float* __
   for (int i = 0; i < 4; ++i) { t0[i] = t0[2 * i] + t0[2 * i + 1]; t1[i] = t1[2 * i] + t1[2 * i + 1]; }
   sg = (t0[0] + t0[1]) + (t0[2] + t0[3]);
   sgx = (t1[0] + t1[1]) + (t1[2] + t1[3]);
-  if (dgamma) dgamma[ch] = accumulate ? dg0 + sgx * inv : sgx * inv;
-  if (dbeta) dbeta[ch] = accumulate ? db0 + sg : sg;
-  const float a = g * inv;
-  const float invn = 1.f / (float)rows;
-  coef[ch] = a;
-  coef[c + ch] = training ? -a * inv * inv * sgx * invn : 0.f;
-  coef[2 * c + ch] = training ? -a * sg * invn : 0.f;
-  coef[3 * c + ch] = mu;
-  bn_coef(g, bt, mu, inv, coef[4 * c + ch], coef[5 * c + ch]);
+  bn_bwd_coef_rows(ops, sg, sgx, ch, c, rows, training, accumulate, dgamma, dbeta, coef);
 }
 
 // Backward pass 3: dx = A*g + B*(x - mean) + C;  dres = g.  Layout as bn_apply_kernel.
@@ -783,23 +741,23 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const GS gs, const T*
                                                             const T* __restrict__ y, T* __restrict__ dx, T* __restrict__ dres,
                                                             const float* __restrict__ coef, long rows, int c, int act_rt) {
   const int act = ACT >= 0 ? ACT : act_rt;
-  const int cbase = blockIdx.y * 256 * VEC;
-  const int cl = min(c - cbase, 256 * VEC);
-  const BnLayout<VEC> L(cl);
-  const int tid = threadIdx.x, cv = tid % L.tpr, rg = tid / L.tpr;
-  if (rg >= L.rpi || cv * VEC >= cl) return;
-  const int ch0 = cbase + cv * VEC, cvalid = c - ch0;
-  float a[VEC], b[VEC], k[VEC], mu[VEC], sc[VEC], sh[VEC];
-  load_coef<VEC>(coef, ch0, c, a);
-  load_coef<VEC>(coef + c, ch0, c, b);
-  load_coef<VEC>(coef + 2 * c, ch0, c, k);
-  load_coef<VEC>(coef + 3 * c, ch0, c, mu);
+  const BnTile<VEC> t(c);
+  if (!t.active) return;
+  BnDx<VEC> k;
+  load_coef<VEC>(coef, t.ch0, c, k.a);
+  load_coef<VEC>(coef + c, t.ch0, c, k.b);
+  load_coef<VEC>(coef + 2 * c, t.ch0, c, k.k);
+  load_coef<VEC>(coef + 3 * c, t.ch0, c, k.mu);
   if (act && !y) {
-    load_coef<VEC>(coef + 4 * c, ch0, c, sc);
-    load_coef<VEC>(coef + 5 * c, ch0, c, sh);
+    load_coef<VEC>(coef + 4 * c, t.ch0, c, k.sc);
+    load_coef<VEC>(coef + 5 * c, t.ch0, c, k.sh);
   }
-  const long step = (long)gridDim.x * L.rpi;
-  long r = (long)blockIdx.x * L.rpi + rg;
+  const long step = t.step();
+  long r = t.row0();
+  const int ch0 = t.ch0, cvalid = t.cvalid;
+  // (the row body written twice, as in bn_apply_kernel: phase by phase per row, the x loads of
+  // the two rows wait for each other and the runtime-activation instantiations take 14 more
+  // registers)
   for (; r + step < rows; r += 2 * step) {  // two independent rows in flight per thread
     const long o0 = r * c + ch0, o1 = o0 + step * c;
     float g0[VEC], x0[VEC], g1[VEC], x1[VEC];
@@ -807,12 +765,12 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const GS gs, const T*
     load_vec<T, VEC>(x + o0, x0, cvalid);
     gs.template load<VEC>(r + step, ch0, g1, cvalid);
     load_vec<T, VEC>(x + o1, x1, cvalid);
-    bn_act_grad<T, VEC>(g0, y ? y + o0 : nullptr, x0, sc, sh, act, cvalid);
-    bn_act_grad<T, VEC>(g1, y ? y + o1 : nullptr, x1, sc, sh, act, cvalid);
+    bn_row_mask<T, VEC>(g0, y ? y + o0 : nullptr, x0, k, act, cvalid);
+    bn_row_mask<T, VEC>(g1, y ? y + o1 : nullptr, x1, k, act, cvalid);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      x0[j] = fmaf(a[j], g0[j], fmaf(b[j], x0[j] - mu[j], k[j]));
-      x1[j] = fmaf(a[j], g1[j], fmaf(b[j], x1[j] - mu[j], k[j]));
+      x0[j] = bn_bwd_dx<VEC>(k, j, g0[j], x0[j]);
+      x1[j] = bn_bwd_dx<VEC>(k, j, g1[j], x1[j]);
     }
     if (dx) {
       store_vec<T, VEC>(dx + o0, x0, cvalid);
@@ -823,17 +781,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const GS gs, const T*
       store_vec<T, VEC>(dres + o1, g1, cvalid);
     }
   }
-  if (r < rows) {
-    const long off = r * c + ch0;
-    float g[VEC], xv[VEC];
-    gs.template load<VEC>(r, ch0, g, cvalid);
-    load_vec<T, VEC>(x + off, xv, cvalid);
-    bn_act_grad<T, VEC>(g, y ? y + off : nullptr, xv, sc, sh, act, cvalid);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) xv[j] = fmaf(a[j], g[j], fmaf(b[j], xv[j] - mu[j], k[j]));
-    if (dx) store_vec<T, VEC>(dx + off, xv, cvalid);
-    if (dres) store_vec<T, VEC>(dres + off, g, cvalid);
-  }
+  if (r < rows) bn_bwd_row<T, VEC>(gs, x, y, dx, dres, r, c, t, k, act);
 }
 
 // ------------------------------------------------------------------ host
@@ -844,28 +792,67 @@ static void with_act(int act, F f) {
   else if (act == RTSDS_ACT_RELU) f(std::integral_constant<int, RTSDS_ACT_RELU>());
   else f(std::integral_constant<int, -1>());
 }
-static long bn_need(long rows, int c, int vec) {
-  int tpr = (c + vec - 1) / vec;
-  if (tpr > 256) tpr = 256;
-  const int rpi = 256 / tpr;
-  return (rows + rpi - 1) / rpi;
+template <typename F>
+static void with_bool(bool b, F f) {
+  if (b) f(std::true_type());
+  else f(std::false_type());
+}
+// f(BnKind<T, VEC>) for the storage type and channel vector of (dtype, c)
+template <typename T_, int VEC_> struct BnKind {
+  typedef T_ T;
+  static constexpr int VEC = VEC_;
+};
+template <typename F>
+static int bn_dispatch(int dtype, int c, F f) {
+  if (dtype == RTSDS_BF16) {
+    if (c % 8 == 0) f(BnKind<bf16, 8>());
+    else f(BnKind<bf16, 1>());
+  } else if (dtype == RTSDS_F32) {
+    if (c % 4 == 0) f(BnKind<float, 4>());
+    else f(BnKind<float, 1>());
+  } else return RTSDS_ERR_UNSUPPORTED;
+  return RTSDS_OK;
+}
+
+// Row-block iterations that cover the rows (the kernels' own layout arithmetic)
+template <int VEC>
+static long bn_need(long rows, int c) {
+  const BnLayout<VEC> L(c);
+  return (rows + L.rpi - 1) / L.rpi;
 }
 // Row blocks of the reduction passes: enough to fill the chip (8+ waves per CU), at least
 // 4 row-iterations per thread, at most kBnMaxRB partials to merge.
-static int bn_rb(long rows, int c, int vec) {
-  const long need = bn_need(rows, c, vec);
+template <int VEC>
+static int bn_rb(long rows, int c) {
+  const long need = bn_need<VEC>(rows, c);
   long rb = std::min<long>(need, kBnMaxRB);
   rb = std::max<long>(1, std::min<long>(rb, (need + 7) / 8));
   return (int)rb;
 }
 // Row blocks of the elementwise passes: ~2 rows per thread.
 static constexpr auto kBnApplyMaxRB = (1L << 24);
-static int bn_apply_rb(long rows, int c, int vec) {
-  const long need = bn_need(rows, c, vec);
+template <int VEC>
+static int bn_apply_rb(long rows, int c) {
+  const long need = bn_need<VEC>(rows, c);
   return (int)std::max<long>(1, std::min<long>((need + 1) / 2, kBnApplyMaxRB));
 }
+static constexpr auto kBnBwdRBMax = 512;
+static constexpr auto kBnBwdRBDiv = 8;
+// Row blocks of the backward statistics pass (row-block-major partials, merged 16 lanes per
+// channel by bn_bwd_finalize_rb_kernel).  At most 512 (tools/ab_bn2.sh, stats pass: 33,540 x
+// 1024 58.8 -> 29.2 us, 262,144 x 128 41.3 -> 27.7 us, 262,144 x 64 17.6 -> 15.6 us against 2048
+// channel-major row blocks; finalize unchanged at ~5 us).
+template <int VEC>
+static int bn_bwd_rb(long rows, int c) {
+  const long need = bn_need<VEC>(rows, c);
+  long rb = std::min<long>(need, kBnBwdRBMax);
+  rb = std::max<long>(1, std::min<long>(rb, (need + kBnBwdRBDiv - 1) / kBnBwdRBDiv));
+  return (int)rb;
+}
+template <int VEC>
+static dim3 bn_grid(int rb, int c) { return dim3(rb, rt_cdiv(c, 256 * VEC)); }
 
-static size_t bn_part_floats(long rows, int c) { return (size_t)bn_rb(rows, c, 1) * c * 4; }
+static size_t bn_part_floats(long rows, int c) { return (size_t)bn_rb<1>(rows, c) * c * 4; }
 
 // Workspace: [row-block partials | 8 coefficient arrays], each part
 // 256-B aligned (coefficient arrays are read with 16-B vector loads).
@@ -885,35 +872,78 @@ extern "C" size_t rtsds_bn_workspace(long rows, int c) {
   return (al64f(bn_part_floats(rows, c)) + al64f((size_t)c * 8)) * 4 + 256;
 }
 
-
-template <typename T, int VEC>
-static void bn_fwd_launch(const void* x, const void* res, void* y, long rows, int c, const float* gamma, const float* beta,
-                          float* rm, float* rv, float* sm, float* si, float mom, float eps, int training, int act,
-                          const float* pre, int pre_nrb, long long* nbt, const BnWs& w, hipStream_t st, long ldy) {
-  float* scale = w.coef;
-  float* shift = w.coef + c;
-  if (training) {
-    int rb = pre_nrb;
-    const float* part = pre;  // statistics already produced by the conv epilogue, or:
-    if (!pre) {
-      rb = bn_rb(rows, c, VEC);
-      hipLaunchKernelGGL((bn_stats_kernel<T, VEC>), dim3(rb, rt_cdiv(c, 256 * VEC)), dim3(256), 0, st, (const T*)x, w.part, rows, c);
-      part = w.part;
-    }
-    if (rows <= kBnTinyRows) {  // finalize + apply in one launch
-      hipLaunchKernelGGL(bn_finalize_apply_kernel<T>, dim3(c), dim3(256), 0, st, part, rb, c, rows, gamma, beta, rm, rv, sm, si,
-                         scale, shift, mom, eps, nbt, (const T*)x, (const T*)res, (T*)y, ldy, act);
-      return;
-    }
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(c), dim3(256), 0, st, part, rb, c, rows, gamma, beta, rm, rv,
-                       sm, si, scale, shift, mom, eps, nbt);
-  } else {
-    hipLaunchKernelGGL(bn_eval_coef_kernel, dim3(rt_cdiv(c, 256)), dim3(256), 0, st, c, gamma, beta, rm, rv, scale, shift, sm, si, eps);
+// One BatchNorm call, either direction, as the entry points hand it to the launch functions.
+struct BnArgs {
+  long rows = 0;
+  int c = 0, training = 0, act = 0, accumulate = 0;
+  const void *x = nullptr, *res = nullptr, *dy = nullptr, *ykept = nullptr;  // ykept: the backward's mask source
+  void *y = nullptr, *dx = nullptr, *dres = nullptr;                         // y: the forward's output
+  long ldy = 0;                                                              // row pitch of y (forward) / dy (backward)
+  const float *gamma = nullptr, *beta = nullptr;
+  float *rmean = nullptr, *rvar = nullptr, *dgamma = nullptr, *dbeta = nullptr;
+  float *smean = nullptr, *sinv = nullptr;  // written by the forward, read by the backward
+  long long* nbt = nullptr;
+  float momentum = 0.f, eps = 0.f;
+  const float* pre = nullptr;  // partial statistics a conv epilogue already produced, pre_nrb per channel
+  int pre_nrb = 0;
+  BnWs w = {nullptr, nullptr};
+  hipStream_t st = nullptr;
+  BnArgs(long rows_, int c_, void* ws, void* stream)
+      : rows(rows_), c(c_), w(bn_ws(ws, rows_, c_)), st((hipStream_t)stream) {}
+  void affine(const float* g, const float* b, const float* sm, const float* si) {
+    gamma = g, beta = b, smean = const_cast<float*>(sm), sinv = const_cast<float*>(si);
   }
-  with_act(act, [&](auto a) {
-    hipLaunchKernelGGL((bn_apply_kernel<T, VEC, decltype(a)::value>), dim3(bn_apply_rb(rows, c, VEC), rt_cdiv(c, 256 * VEC)),
-                       dim3(256), 0, st, (const T*)x, (const T*)res, (T*)y, scale, shift, rows, c, act, ldy);
+};
+
+// The forward's prologue: scale | shift into the first two coefficient rows.  Training: the
+// statistics pass (unless a conv epilogue produced the partials), then the finalize; eval: from the
+// running statistics.  apply_too (training, few rows): the finalize's block also applies, and
+// nothing is left to launch.
+template <typename T, int VEC>
+static void bn_fwd_coefs(const BnArgs& a, bool apply_too = false) {
+  const int c = a.c;
+  float *scale = a.w.coef, *shift = a.w.coef + c;
+  if (!a.training) {
+    hipLaunchKernelGGL(bn_eval_coef_kernel, dim3(rt_cdiv(c, 256)), dim3(256), 0, a.st, c, a.gamma, a.beta, a.rmean, a.rvar, scale,
+                       shift, a.smean, a.sinv, a.eps);
+    return;
+  }
+  int rb = a.pre_nrb;
+  const float* part = a.pre;
+  if (!part) {
+    rb = bn_rb<VEC>(a.rows, c);
+    hipLaunchKernelGGL((bn_stats_kernel<T, VEC>), bn_grid<VEC>(rb, c), dim3(256), 0, a.st, (const T*)a.x, a.w.part, a.rows, c);
+    part = a.w.part;
+  }
+  if (apply_too)
+    hipLaunchKernelGGL(bn_finalize_apply_kernel<T>, dim3(c), dim3(256), 0, a.st, part, rb, c, a.rows, a.gamma, a.beta, a.rmean,
+                       a.rvar, a.smean, a.sinv, scale, shift, a.momentum, a.eps, a.nbt, (const T*)a.x, (const T*)a.res, (T*)a.y,
+                       a.ldy, a.act);
+  else
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(c), dim3(256), 0, a.st, part, rb, c, a.rows, a.gamma, a.beta, a.rmean, a.rvar,
+                       a.smean, a.sinv, scale, shift, a.momentum, a.eps, a.nbt);
+}
+template <typename T, int VEC>
+static void bn_fwd_launch(const BnArgs& a) {
+  const bool tiny = a.training && a.rows <= kBnTinyRows;  // finalize + apply in one launch
+  bn_fwd_coefs<T, VEC>(a, tiny);
+  if (tiny) return;
+  with_act(a.act, [&](auto av) {
+    hipLaunchKernelGGL((bn_apply_kernel<T, VEC, decltype(av)::value>), bn_grid<VEC>(bn_apply_rb<VEC>(a.rows, a.c), a.c), dim3(256),
+                       0, a.st, (const T*)a.x, (const T*)a.res, (T*)a.y, a.w.coef, a.w.coef + a.c, a.rows, a.c, a.act, a.ldy);
   });
+}
+// The forward's operands, as rtsds_bn_fwd_ld and rtsds_bn_relu_maxpool_fwd take them
+static int bn_fwd_args(BnArgs& a, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                       long long* num_batches_tracked, float* save_mean, float* save_invstd, float momentum, float eps,
+                       int training, const float* stats_part, int stats_nrb) {
+  if (!training && (!running_mean || !running_var)) return RTSDS_ERR_UNSUPPORTED;
+  if (training && (!save_mean || !save_invstd)) return RTSDS_ERR_UNSUPPORTED;
+  a.affine(gamma, beta, save_mean, save_invstd);
+  a.rmean = running_mean, a.rvar = running_var, a.nbt = training ? num_batches_tracked : nullptr;
+  a.momentum = momentum, a.eps = eps, a.training = training;
+  a.pre = stats_part, a.pre_nrb = stats_nrb;
+  return RTSDS_OK;
 }
 
 extern "C" int rtsds_bn_fwd_ld(const void* x, const void* res, void* y, long ldy, long rows, int c, const float* gamma,
@@ -923,19 +953,13 @@ extern "C" int rtsds_bn_fwd_ld(const void* x, const void* res, void* y, long ldy
   if (rows <= 0 || c <= 0 || ldy < c) return RTSDS_ERR_SHAPE;
   if (ldy != c && !(dtype == RTSDS_BF16 && c % 8 == 0 && ldy % 8 == 0)) return RTSDS_ERR_UNSUPPORTED;
   if (ws_bytes < rtsds_bn_workspace(rows, c)) return RTSDS_ERR_WORKSPACE;
-  if (!training && (!running_mean || !running_var)) return RTSDS_ERR_UNSUPPORTED;
-  if (training && (!save_mean || !save_invstd)) return RTSDS_ERR_UNSUPPORTED;
+  BnArgs a(rows, c, ws, stream);
+  if (int rc = bn_fwd_args(a, gamma, beta, running_mean, running_var, num_batches_tracked, save_mean, save_invstd, momentum, eps,
+                           training, stats_part, stats_nrb))
+    return rc;
   if (c > 65535 * 256) return RTSDS_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const BnWs w = bn_ws(ws, rows, c);
-  long long* nbt = training ? num_batches_tracked : nullptr;
-  if (dtype == RTSDS_BF16) {
-    if (c % 8 == 0) bn_fwd_launch<bf16, 8>(x, res, y, rows, c, gamma, beta, running_mean, running_var, save_mean, save_invstd, momentum, eps, training, act, stats_part, stats_nrb, nbt, w, st, ldy);
-    else bn_fwd_launch<bf16, 1>(x, res, y, rows, c, gamma, beta, running_mean, running_var, save_mean, save_invstd, momentum, eps, training, act, stats_part, stats_nrb, nbt, w, st, ldy);
-  } else if (dtype == RTSDS_F32) {
-    if (c % 4 == 0) bn_fwd_launch<float, 4>(x, res, y, rows, c, gamma, beta, running_mean, running_var, save_mean, save_invstd, momentum, eps, training, act, stats_part, stats_nrb, nbt, w, st, ldy);
-    else bn_fwd_launch<float, 1>(x, res, y, rows, c, gamma, beta, running_mean, running_var, save_mean, save_invstd, momentum, eps, training, act, stats_part, stats_nrb, nbt, w, st, ldy);
-  } else return RTSDS_ERR_UNSUPPORTED;
+  a.x = x, a.res = res, a.y = y, a.ldy = ldy, a.act = act;
+  if (int rc = bn_dispatch(dtype, c, [&](auto k) { bn_fwd_launch<typename decltype(k)::T, decltype(k)::VEC>(a); })) return rc;
   RET_LAUNCH();
 }
 
@@ -948,83 +972,65 @@ extern "C" int rtsds_bn_fwd(const void* x, const void* res, void* y, long rows, 
                          save_invstd, momentum, eps, training, act, stats_part, stats_nrb, dtype, ws, ws_bytes, stream);
 }
 
-static constexpr auto kBnBwdRBMax = 512;
-static constexpr auto kBnBwdRBDiv = 8;
-// Row blocks of the backward statistics pass (row-block-major partials, merged 16 lanes per
-// channel by bn_bwd_finalize_rb_kernel).  At most 512 (tools/ab_bn2.sh, stats pass: 33,540 x
-// 1024 58.8 -> 29.2 us, 262,144 x 128 41.3 -> 27.7 us, 262,144 x 64 17.6 -> 15.6 us against 2048
-// channel-major row blocks; finalize unchanged at ~5 us).
-static int bn_bwd_rb(long rows, int c, int vec) {
-  const long need = bn_need(rows, c, vec);
-  long rb = std::min<long>(need, kBnBwdRBMax);
-  rb = std::max<long>(1, std::min<long>(rb, (need + kBnBwdRBDiv - 1) / kBnBwdRBDiv));
-  return (int)rb;
-}
 template <typename T, int VEC, class GS>
-static void bn_bwd_launch(const GS& gs, const void* x, const void* y, void* dx, void* dres, float* dgamma, float* dbeta,
-                          long rows, int c, const float* gamma, const float* beta, const float* smean, const float* sinv, int training,
-                          int act, int accumulate, const BnWs& w, hipStream_t st, const float* pre = nullptr, int pre_nrb = 0) {
-  int rb = bn_bwd_rb(rows, c, VEC);
-  const float* part = w.part;
+static void bn_bwd_launch(const GS& gs, const BnArgs& a) {
+  const T *x = (const T*)a.x, *y = (const T*)a.ykept;
+  T *dx = (T*)a.dx, *dres = (T*)a.dres;
+  const long rows = a.rows;
+  const int c = a.c, act = a.act;
+  // statistics already produced by the consumer conv's data-gradient epilogue, or our own pass's
+  const int rb = a.pre ? a.pre_nrb : bn_bwd_rb<VEC>(rows, c);
   // residual BatchNorm + ReLU with both gradients wanted: the statistics pass stores
   // g = dy * relu'(y) as dres, and the apply pass reads g and x (not dy, y) -- one full read
   // less; g is exactly dy or 0, so the arithmetic is unchanged
-  const bool g_out = !pre && y && act == RTSDS_ACT_RELU && dres && dx && GS::kDirect;
-  if (!pre && rb == 1 && GS::kDirect && !g_out) {  // one row block: the three passes in one launch
-    const dim3 grid(1, rt_cdiv(c, 256 * VEC));
-    if (y && act)
-      with_act(act, [&](auto a) {
-        hipLaunchKernelGGL((bn_bwd_tiny_kernel<T, VEC, true, GS, decltype(a)::value>), grid, dim3(256), 0, st, gs, (const T*)x,
-                           (const T*)y, gamma, beta, smean, sinv, dgamma, dbeta, (T*)dx, (T*)dres, rows, c, act, training,
-                           accumulate);
+  const bool g_out = !a.pre && y && act == RTSDS_ACT_RELU && dres && dx && GS::kDirect;
+  if (!a.pre && rb == 1 && GS::kDirect && !g_out) {  // one row block: the three passes in one launch
+    with_bool(y && act, [&](auto hy) {
+      with_act(act, [&](auto av) {
+        hipLaunchKernelGGL((bn_bwd_tiny_kernel<T, VEC, decltype(hy)::value, GS, decltype(av)::value>), bn_grid<VEC>(1, c), dim3(256),
+                           0, a.st, gs, x, y, a.gamma, a.beta, a.smean, a.sinv, a.dgamma, a.dbeta, dx, dres, rows, c, act,
+                           a.training, a.accumulate);
       });
-    else
-      with_act(act, [&](auto a) {
-        hipLaunchKernelGGL((bn_bwd_tiny_kernel<T, VEC, false, GS, decltype(a)::value>), grid, dim3(256), 0, st, gs, (const T*)x,
-                           (const T*)y, gamma, beta, smean, sinv, dgamma, dbeta, (T*)dx, (T*)dres, rows, c, act, training,
-                           accumulate);
-      });
+    });
     return;
   }
-  if (pre) {  // statistics already produced by the consumer conv's data-gradient epilogue
-    part = pre;
-    rb = pre_nrb;
-  } else if (y && act)
-    with_act(act, [&](auto a) {
-      hipLaunchKernelGGL((bn_bwd_stats_kernel<T, VEC, true, GS, decltype(a)::value>), dim3(rb, rt_cdiv(c, 256 * VEC)), dim3(256), 0,
-                         st, gs, (const T*)x, (const T*)y, gamma, beta, smean, sinv, w.part, rows, c, act,
-                         g_out ? (T*)dres : (T*)nullptr);
+  if (a.pre)  // channel-major [c][tile][2] partials of the data-gradient epilogue
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(c), dim3(256), 0, a.st, a.pre, rb, c, rows, a.gamma, a.beta, a.smean, a.sinv,
+                       a.dgamma, a.dbeta, a.w.coef, a.training, a.accumulate);
+  else {
+    with_bool(y && act, [&](auto hy) {
+      with_act(act, [&](auto av) {
+        hipLaunchKernelGGL((bn_bwd_stats_kernel<T, VEC, decltype(hy)::value, GS, decltype(av)::value>), bn_grid<VEC>(rb, c), dim3(256),
+                           0, a.st, gs, x, y, a.gamma, a.beta, a.smean, a.sinv, a.w.part, rows, c, act,
+                           g_out ? dres : (T*)nullptr);
+      });
     });
-  else
-    with_act(act, [&](auto a) {
-      hipLaunchKernelGGL((bn_bwd_stats_kernel<T, VEC, false, GS, decltype(a)::value>), dim3(rb, rt_cdiv(c, 256 * VEC)), dim3(256),
-                         0, st, gs, (const T*)x, (const T*)y, gamma, beta, smean, sinv, w.part, rows, c, act, (T*)nullptr);
-    });
-  if (pre)  // channel-major [c][tile][2] partials of the data-gradient epilogue
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(c), dim3(256), 0, st, part, rb, c, rows, gamma, beta, smean, sinv,
-                       dgamma, dbeta, w.coef, training, accumulate);
-  else
-    hipLaunchKernelGGL(bn_bwd_finalize_rb_kernel, dim3(rt_cdiv(c, 16)), dim3(256), 0, st, part, rb, c, rows, gamma, beta, smean,
-                       sinv, dgamma, dbeta, w.coef, training, accumulate);
+    hipLaunchKernelGGL(bn_bwd_finalize_rb_kernel, dim3(rt_cdiv(c, 16)), dim3(256), 0, a.st, a.w.part, rb, c, rows, a.gamma, a.beta,
+                       a.smean, a.sinv, a.dgamma, a.dbeta, a.w.coef, a.training, a.accumulate);
+  }
+  const dim3 grid = bn_grid<VEC>(bn_apply_rb<VEC>(rows, c), c);
   if (g_out) {
-    const GradDirect<T> gg{(const T*)dres, c};
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, VEC, GradDirect<T>, RTSDS_ACT_NONE>), dim3(bn_apply_rb(rows, c, VEC), rt_cdiv(c, 256 * VEC)),
-                       dim3(256), 0, st, gg, (const T*)x, (const T*)nullptr, (T*)dx, (T*)nullptr, w.coef, rows, c, 0);
+    const GradDirect<T> gg{dres, c};
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, VEC, GradDirect<T>, RTSDS_ACT_NONE>), grid, dim3(256), 0, a.st, gg, x,
+                       (const T*)nullptr, dx, (T*)nullptr, a.w.coef, rows, c, 0);
   } else if (dx || dres) {
-    with_act(act, [&](auto a) {
-      hipLaunchKernelGGL((bn_bwd_apply_kernel<T, VEC, GS, decltype(a)::value>), dim3(bn_apply_rb(rows, c, VEC), rt_cdiv(c, 256 * VEC)),
-                         dim3(256), 0, st, gs, (const T*)x, (const T*)y, (T*)dx, (T*)dres, w.coef, rows, c, act);
+    with_act(act, [&](auto av) {
+      hipLaunchKernelGGL((bn_bwd_apply_kernel<T, VEC, GS, decltype(av)::value>), grid, dim3(256), 0, a.st, gs, x, y, dx, dres,
+                         a.w.coef, rows, c, act);
     });
   }
 }
 template <typename T, int VEC>
-static void bn_bwd_launch(const void* dy, const void* x, const void* y, void* dx, void* dres, float* dgamma, float* dbeta,
-                          long rows, int c, const float* gamma, const float* beta, const float* smean, const float* sinv, int training,
-                          int act, int accumulate, const BnWs& w, hipStream_t st, const float* pre = nullptr, int pre_nrb = 0,
-                          long ldy = 0) {
-  const GradDirect<T> gs{(const T*)dy, (int)(ldy ? ldy : c)};
-  bn_bwd_launch<T, VEC, GradDirect<T>>(gs, x, y, dx, dres, dgamma, dbeta, rows, c, gamma, beta, smean, sinv, training, act,
-                                       accumulate, w, st, pre, pre_nrb);
+static void bn_bwd_launch(const BnArgs& a) {
+  const GradDirect<T> gs{(const T*)a.dy, (int)(a.ldy ? a.ldy : a.c)};
+  bn_bwd_launch<T, VEC, GradDirect<T>>(gs, a);
+}
+// The backward's operands, as its three entry points take them
+static void bn_bwd_args(BnArgs& a, const void* x, void* dx, float* dgamma, float* dbeta, const float* gamma, const float* beta,
+                        const float* save_mean, const float* save_invstd, int training, int act, int accumulate) {
+  a.affine(gamma, beta, save_mean, save_invstd);
+  a.x = x, a.dx = dx, a.dgamma = dgamma, a.dbeta = dbeta;
+  a.training = training, a.act = act, a.accumulate = accumulate;
 }
 
 extern "C" int rtsds_bn_bwd_part(const void* dy, const void* x, void* dx, float* dgamma, float* dbeta, long rows, int c,
@@ -1035,8 +1041,10 @@ extern "C" int rtsds_bn_bwd_part(const void* dy, const void* x, void* dx, float*
   if (ws_bytes < rtsds_bn_workspace(rows, c)) return RTSDS_ERR_WORKSPACE;
   if (dtype != RTSDS_BF16 || c % 8 != 0) return RTSDS_ERR_UNSUPPORTED;
   if (!(act == RTSDS_ACT_NONE || act == RTSDS_ACT_RELU || act == RTSDS_ACT_LEAKY)) return RTSDS_ERR_UNSUPPORTED;
-  bn_bwd_launch<bf16, 8>(dy, x, nullptr, dx, nullptr, dgamma, dbeta, rows, c, gamma, beta, save_mean, save_invstd, training, act,
-                         accumulate_params, bn_ws(ws, rows, c), (hipStream_t)stream, part, nrb);
+  BnArgs a(rows, c, ws, stream);
+  bn_bwd_args(a, x, dx, dgamma, dbeta, gamma, beta, save_mean, save_invstd, training, act, accumulate_params);
+  a.dy = dy, a.pre = part, a.pre_nrb = nrb;
+  bn_bwd_launch<bf16, 8>(a);
   RET_LAUNCH();
 }
 
@@ -1049,15 +1057,10 @@ extern "C" int rtsds_bn_bwd_ld(const void* dy, long ldy, const void* x, const vo
   if (ws_bytes < rtsds_bn_workspace(rows, c)) return RTSDS_ERR_WORKSPACE;
   if (!y && !(act == RTSDS_ACT_NONE || act == RTSDS_ACT_RELU || act == RTSDS_ACT_LEAKY)) return RTSDS_ERR_UNSUPPORTED;
   if (!y && act && dres) return RTSDS_ERR_UNSUPPORTED;  // residual: the mask needs y
-  hipStream_t st = (hipStream_t)stream;
-  const BnWs w = bn_ws(ws, rows, c);
-  if (dtype == RTSDS_BF16) {
-    if (c % 8 == 0) bn_bwd_launch<bf16, 8>(dy, x, y, dx, dres, dgamma, dbeta, rows, c, gamma, beta, save_mean, save_invstd, training, act, accumulate_params, w, st, nullptr, 0, ldy);
-    else bn_bwd_launch<bf16, 1>(dy, x, y, dx, dres, dgamma, dbeta, rows, c, gamma, beta, save_mean, save_invstd, training, act, accumulate_params, w, st, nullptr, 0, ldy);
-  } else if (dtype == RTSDS_F32) {
-    if (c % 4 == 0) bn_bwd_launch<float, 4>(dy, x, y, dx, dres, dgamma, dbeta, rows, c, gamma, beta, save_mean, save_invstd, training, act, accumulate_params, w, st, nullptr, 0, ldy);
-    else bn_bwd_launch<float, 1>(dy, x, y, dx, dres, dgamma, dbeta, rows, c, gamma, beta, save_mean, save_invstd, training, act, accumulate_params, w, st, nullptr, 0, ldy);
-  } else return RTSDS_ERR_UNSUPPORTED;
+  BnArgs a(rows, c, ws, stream);
+  bn_bwd_args(a, x, dx, dgamma, dbeta, gamma, beta, save_mean, save_invstd, training, act, accumulate_params);
+  a.dy = dy, a.ldy = ldy, a.ykept = y, a.dres = dres;
+  if (int rc = bn_dispatch(dtype, c, [&](auto k) { bn_bwd_launch<typename decltype(k)::T, decltype(k)::VEC>(a); })) return rc;
   RET_LAUNCH();
 }
 extern "C" int rtsds_bn_bwd(const void* dy, const void* x, const void* y, void* dx, void* dres, float* dgamma, float* dbeta,
@@ -1137,31 +1140,17 @@ extern "C" int rtsds_bn_relu_maxpool_fwd(const void* x, void* y, uint8_t* idx, i
   const long rows = (long)n * h * w;
   if (!bn_pool_ok(n, h, w, c, ho, wo, p, dtype)) return RTSDS_ERR_UNSUPPORTED;
   if (ws_bytes < rtsds_bn_workspace(rows, c)) return RTSDS_ERR_WORKSPACE;
-  if (!training && (!running_mean || !running_var)) return RTSDS_ERR_UNSUPPORTED;
-  if (training && (!save_mean || !save_invstd)) return RTSDS_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const BnWs wsb = bn_ws(ws, rows, c);
-  float* scale = wsb.coef;
-  float* shift = wsb.coef + c;
-  long long* nbt = training ? num_batches_tracked : nullptr;
-  if (training) {
-    int rb = stats_nrb;
-    const float* part = stats_part;
-    if (!part) {
-      rb = bn_rb(rows, c, 8);
-      hipLaunchKernelGGL((bn_stats_kernel<bf16, 8>), dim3(rb, rt_cdiv(c, 256 * 8)), dim3(256), 0, st, (const bf16*)x, wsb.part, rows, c);
-      part = wsb.part;
-    }
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(c), dim3(256), 0, st, part, rb, c, rows, gamma, beta, running_mean, running_var,
-                       save_mean, save_invstd, scale, shift, momentum, eps, nbt);
-  } else {
-    hipLaunchKernelGGL(bn_eval_coef_kernel, dim3(rt_cdiv(c, 256)), dim3(256), 0, st, c, gamma, beta, running_mean, running_var,
-                       scale, shift, save_mean, save_invstd, eps);
-  }
+  BnArgs a(rows, c, ws, stream);
+  if (int rc = bn_fwd_args(a, gamma, beta, running_mean, running_var, num_batches_tracked, save_mean, save_invstd, momentum, eps,
+                           training, stats_part, stats_nrb))
+    return rc;
+  a.x = x;
+  bn_fwd_coefs<bf16, 8>(a);
+  hipStream_t st = a.st;
+  const float *scale = a.w.coef, *shift = a.w.coef + c;
   const long total = (long)n * ho * wo * (c / 8);
   const int blocks = (int)std::max<long>(1, std::min<long>((total + 255) / 256, 1L << 20));
-  hipLaunchKernelGGL(bn_relu_pool_fwd_kernel<bf16>, dim3(blocks), dim3(256), 0, st, (const bf16*)x, (const float*)scale,
-                     (const float*)shift, (bf16*)y, idx, h, w, c, ho, wo, p, total, fastdiv_make(c / 8), fastdiv_make(wo),
+  hipLaunchKernelGGL(bn_relu_pool_fwd_kernel<bf16>, dim3(blocks), dim3(256), 0, st, (const bf16*)x, scale, shift, (bf16*)y, idx, h, w, c, ho, wo, p, total, fastdiv_make(c / 8), fastdiv_make(wo),
                      fastdiv_make(ho));
   RET_LAUNCH();
 }
@@ -1173,8 +1162,9 @@ extern "C" int rtsds_bn_relu_maxpool_bwd(const void* dy_pool, const uint8_t* idx
   if (!bn_pool_ok(n, h, w, c, ho, wo, p, dtype)) return RTSDS_ERR_UNSUPPORTED;
   if (ws_bytes < rtsds_bn_workspace(rows, c)) return RTSDS_ERR_WORKSPACE;
   const GradPool<bf16> gs{(const bf16*)dy_pool, idx, c, h, w, ho, wo, p, fastdiv_make(w), fastdiv_make(h)};
-  bn_bwd_launch<bf16, 8, GradPool<bf16>>(gs, x, nullptr, dx, nullptr, dgamma, dbeta, rows, c, gamma, beta, save_mean, save_invstd,
-                                         training, RTSDS_ACT_RELU, accumulate_params, bn_ws(ws, rows, c), (hipStream_t)stream);
+  BnArgs a(rows, c, ws, stream);
+  bn_bwd_args(a, x, dx, dgamma, dbeta, gamma, beta, save_mean, save_invstd, training, RTSDS_ACT_RELU, accumulate_params);
+  bn_bwd_launch<bf16, 8, GradPool<bf16>>(gs, a);
   RET_LAUNCH();
 }
 

@@ -69,6 +69,18 @@ def _sinks(*params):
     return out
 
 
+def _bn_param_grads(ctx, c, device):
+    """(dgamma, dbeta, accumulate) of a BatchNorm backward: the parameters' sinks (accumulate = 1, the
+    Function then returns None for both), else fresh fp32 [c] tensors for the gradients wanted."""
+    need_g, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+    sinks = _sinks(ctx.gamma if need_g else None, ctx.beta if need_b else None) if (need_g or need_b) else None
+    if sinks is not None:
+        return sinks[0], sinks[1], 1
+    dg = torch.empty(c, dtype=torch.float32, device=device) if need_g else None
+    db = torch.empty(c, dtype=torch.float32, device=device) if need_b else None
+    return dg, db, 0
+
+
 # ----------------------------------------------------------------------------- conv
 def _conv_desc(x, k, kh, kw, stride, padding, dilation):
     n, c, h, w = x.shape
@@ -606,17 +618,10 @@ class BatchNormFn(torch.autograd.Function):
         if not ldy:
             dy = nhwc(dy)
             ldy = c
-        need_dx, need_g, need_b, need_r = (ctx.needs_input_grad[0], ctx.needs_input_grad[1],
-                                           ctx.needs_input_grad[2], ctx.needs_input_grad[3])
+        need_dx, need_r = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
         dx = torch.empty_like(x, memory_format=CL) if need_dx else None
         dres = torch.empty_like(x, memory_format=CL) if (has_res and need_r) else None
-        sinks = _sinks(ctx.gamma if need_g else None, ctx.beta if need_b else None) if (need_g or need_b) else None
-        if sinks is not None:
-            dg, db, acc = sinks[0], sinks[1], 1
-        else:
-            dg = torch.empty(c, dtype=torch.float32, device=x.device) if need_g else None
-            db = torch.empty(c, dtype=torch.float32, device=x.device) if need_b else None
-            acc = 0
+        dg, db, acc = _bn_param_grads(ctx, c, x.device)
         ws = workspace(lib.rtsds_bn_workspace(rows, c), x.device)
         link = ctx.link
         if link is not None and link.part is not None and dy.dtype == x.dtype:
@@ -676,15 +681,21 @@ def _channel_slice_pitch(t):
     return ld
 
 
+def _bn_epilogue_stats(x, training, running_mean):
+    """(stats, nrb) a producing conv attached to ``x`` for a training-mode BatchNorm, else (None, None);
+    also notes that the call is about to change the running statistics."""
+    st = getattr(x, "_rt_bn_stats", None) if training else None
+    if training and running_mean is not None:
+        bump_params_epoch()  # running statistics change (raw-pointer write)
+    return st if st is not None else (None, None)
+
+
 def batch_norm(x, gamma, beta, running_mean, running_var, training, momentum, eps, act=0,
                residual=None, num_batches_tracked=None, res_join=None, link=None, out=None):
     """``num_batches_tracked`` (int64, optional) is incremented by the finalize kernel.
     ``res_join``: GradJoin shared with the other readers of ``residual``.  ``out``: (NHWC
     buffer, channel offset) to write y into (a view of it is returned; bf16 without residual)."""
-    st = getattr(x, "_rt_bn_stats", None) if training else None
-    stats, nrb = st if st is not None else (None, None)
-    if training and running_mean is not None:
-        bump_params_epoch()  # running statistics change (raw-pointer write)
+    stats, nrb = _bn_epilogue_stats(x, training, running_mean)
     return BatchNormFn.apply(x, gamma, beta, residual, running_mean, running_var, training,
                              momentum, eps, act, stats, nrb, num_batches_tracked, res_join, link, out)
 
@@ -1051,15 +1062,8 @@ class BnReluMaxPoolFn(torch.autograd.Function):
         dy = nhwc(dy)
         if dy.dtype != x.dtype:
             dy = cast(dy, x.dtype)
-        need_dx, need_g, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        dx = torch.empty_like(x, memory_format=CL) if need_dx else None
-        sinks = _sinks(ctx.gamma if need_g else None, ctx.beta if need_b else None) if (need_g or need_b) else None
-        if sinks is not None:
-            dg, db, acc = sinks[0], sinks[1], 1
-        else:
-            dg = torch.empty(c, dtype=torch.float32, device=x.device) if need_g else None
-            db = torch.empty(c, dtype=torch.float32, device=x.device) if need_b else None
-            acc = 0
+        dx = torch.empty_like(x, memory_format=CL) if ctx.needs_input_grad[0] else None
+        dg, db, acc = _bn_param_grads(ctx, c, x.device)
         # backward unfused: the pool gradient is materialised once (16-B scatter-free gather,
         # rtsds_maxpool_bwd) and the BatchNorm backward reads it directly -- measured faster
         # than gathering it inside both BatchNorm passes (rtsds_bn_relu_maxpool_bwd: 94 + 108
@@ -1081,10 +1085,7 @@ def bn_relu_maxpool_ok(x, k, s, p):
 
 def bn_relu_maxpool(x, gamma, beta, running_mean, running_var, training, momentum, eps, p, ceil_mode,
                     num_batches_tracked=None):
-    st = getattr(x, "_rt_bn_stats", None) if training else None
-    stats, nrb = st if st is not None else (None, None)
-    if training and running_mean is not None:
-        bump_params_epoch()  # running statistics change (raw-pointer write)
+    stats, nrb = _bn_epilogue_stats(x, training, running_mean)
     return BnReluMaxPoolFn.apply(x, gamma, beta, running_mean, running_var, training, momentum, eps, stats, nrb,
                                  num_batches_tracked, p, ceil_mode)
 
