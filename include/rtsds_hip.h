@@ -452,6 +452,45 @@ int rtsds_conf_hist(const float* acc, unsigned long long* hist, uint8_t* pred, u
 int rtsds_pseudo_select(const uint8_t* pred, const uint16_t* cbin, const int* tbin, int64_t* out,
                         long total, int c, int ignore_index, void* stream);
 
+/* ---------------------------------------------------------------- ClassMix (self-training)
+ * No counterpart in the reference.  ClassMix (DACS, DAFormer) pastes the pixels of half of the
+ * classes of a labelled source image, image and label, onto a target image; here the rest of
+ * the label map is the thresholded pseudo-label of rtsds_pseudo_select, formed on the fly.
+ * Geometry: n samples; source maps [n][hs][ws]; the window (= target) size h x w, hs >= h and
+ * ws >= w; per sample a window origin (y0, x0) = origins[i * origin_pitch + {0, 1}] (device
+ * int32, origin_pitch >= 2 ints per row) with 0 <= y0 <= hs - h, 0 <= x0 <= ws - w (a value
+ * outside that range is clamped into it: the origins are device data, no access may leave the
+ * buffers).  2 <= c <= 32 classes; a label s is a class iff 0 <= s < c.
+ * rtsds_class_presence: present[i] (uint32) = OR of 1u << s over the classes s in the window
+ *   slab[i][y0 : y0 + h][x0 : x0 + w] (int64).  present need not be cleared by the caller (an
+ *   asynchronous memset on the stream precedes the kernel).  Only the window is read.
+ * rtsds_classmix: with P = the classes of present[i] (bits >= c dropped), quota =
+ *   (|P| + 1) >> 1 and key row perm[i * perm_pitch + k] (device int32, perm_pitch >= c), class
+ *   k in P is chosen iff #{j in P : perm[j] < perm[k] or (perm[j] == perm[k] and j < k)} <
+ *   quota; chosen[i] (uint32, may be NULL) receives the mask of the chosen classes (P empty: 0).
+ *   Per window pixel with s = slab[i][y0 + y][x0 + x] and M = (s is a class and chosen):
+ *     out_img[i][y][x] = M ? src[i][y0 + y][x0 + x] : tgt[i][y][x]   (the whole record of
+ *                        pix_bytes bytes, bit for bit, pad lane included)
+ *     out_lab[i][y][x] = M ? s : (k = pred[i][y][x]) < c and cbin[i][y][x] >= tbin[k] ? k
+ *                        : ignore_index                    (int64; rtsds_pseudo_select's rule)
+ *     mask[i][y][x]    = M ? 1 : 0                          (uint8, may be NULL)
+ *   Images are opaque pixel records, pix_bytes in {6, 8, 12, 16} (bf16 / fp32 with a pixel
+ *   pitch of 3 or 4 elements), src [n][hs][ws], tgt and out_img [n][h][w], one form for all
+ *   three.  Rows whose target start is a multiple of 8 pixels move in 16-byte vectors when all
+ *   bases are 16-byte aligned (pred / mask 8) and the source row start is a multiple of 8 / 2 /
+ *   4 / 2 pixels for pix_bytes 6 / 8 / 12 / 16 (8 and 16: any start, with 8-byte source loads);
+ *   every other row takes a per-pixel path with the same results.
+ * RTSDS_ERR_SHAPE: n, h or w < 1, n > 65535, h > hs or w > ws, c outside [2, 32], a pitch too
+ * small.  RTSDS_ERR_UNSUPPORTED: another pix_bytes, a NULL or misaligned pointer.  Neither
+ * entry synchronises, allocates or touches the host (graph-capture safe).                    */
+int rtsds_class_presence(const int64_t* slab, const int* origins, int origin_pitch, unsigned int* present,
+                         int n, int hs, int ws, int h, int w, int c, void* stream);
+int rtsds_classmix(const void* src, const int64_t* slab, const void* tgt, const uint8_t* pred,
+                   const uint16_t* cbin, const int* tbin, const unsigned int* present, const int* perm,
+                   int perm_pitch, const int* origins, int origin_pitch, void* out_img, int64_t* out_lab,
+                   uint8_t* mask, unsigned int* chosen, int n, int hs, int ws, int h, int w, int c,
+                   int pix_bytes, int ignore_index, void* stream);
+
 /* ---------------------------------------------------------------- input pipeline
  * The reference's per-sample torchvision transforms (main.py:60-108; datasets/cityscapes.py:
  * 56-68, datasets/gta5.py:69-118) on a decoded HWC image in device memory.
@@ -529,7 +568,7 @@ int rtsds_pooled_mlp_fwd(const void* p, const void* w1, const float* b1, const v
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 13
+#define RTSDS_ABI_VERSION 14
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

@@ -1603,6 +1603,146 @@ def pseudo_select(pred, cbin, tbin, ignore_index, out=None):
     return out
 
 
+_U32 = getattr(torch, "uint32", torch.int32)  # a torch without uint32: int32 holding the same bits
+
+
+def _mix_labels(fn, slab):
+    """Source labels as contiguous int64 [N, Hs, Ws] (from [N, 1, Hs, Ws] or [N, Hs, Ws])."""
+    if slab.dim() == 4 and slab.shape[1] == 1:
+        slab = slab[:, 0]
+    if slab.dim() != 3 or slab.dtype != torch.int64 or not slab.is_contiguous() or slab.numel() == 0:
+        raise RuntimeError(f"rtsds_amd: {fn}: slab must be contiguous int64 [N, Hs, Ws] or [N, 1, Hs, Ws], got "
+                           f"{slab.dtype} {tuple(slab.shape)}")
+    return slab
+
+
+def _mix_rows(fn, name, t, n, cols, device):
+    """int32 [n, cols] on ``device`` with unit column stride (a column slice of one wider block is
+    fine: the kernels take the row pitch).  Returns the pitch in elements."""
+    if t.dtype != torch.int32 or tuple(t.shape) != (n, cols) or t.device != device or t.stride(1) != 1 or \
+            (n > 1 and t.stride(0) < cols):
+        raise RuntimeError(f"rtsds_amd: {fn}: {name} must be int32 {(n, cols)} on {device} with unit column stride, "
+                           f"got {t.dtype} {tuple(t.shape)} strides {tuple(t.stride())} on {t.device}")
+    return int(t.stride(0)) if n > 1 else cols
+
+
+def _mix_image(fn, name, x):
+    """(n, h, w, pitch) of an image batch in one of the two input forms of the networks: NHWC
+    (channels-last [N, 3, H, W]: pitch 3) or the 4-element pixel pitch of _pack (``_rt_cpad`` = 4)."""
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype not in (torch.bfloat16, torch.float32) or x.numel() == 0:
+        raise RuntimeError(f"rtsds_amd: {fn}: {name} must be a bf16 or fp32 [N, 3, H, W] batch, got {x.dtype} "
+                           f"{tuple(x.shape)}")
+    n, _, h, w = x.shape
+    if getattr(x, "_rt_cpad", None) == 4 and is_padded_input(x):
+        return n, h, w, 4
+    if getattr(x, "_rt_cpad", None) is None and x.is_contiguous(memory_format=CL):
+        return n, h, w, 3
+    raise RuntimeError(f"rtsds_amd: {fn}: {name} must be in an input form (pack_input): NHWC, or the 4-channel pitch "
+                       f"marked _rt_cpad = 4; got strides {tuple(x.stride())}")
+
+
+def _mix_empty_image(n, h, w, pitch, dtype, device):
+    if pitch == 3:
+        return empty_nhwc(n, 3, h, w, dtype, device)
+    y = torch.empty((n, h, w, 4), dtype=dtype, device=device).permute(0, 3, 1, 2)[:, :3]
+    y._rt_cpad = 4
+    return y
+
+
+def class_presence(slab, size, origins, num_classes=32):
+    """Classes present in a window of each source label map (rtsds_class_presence): ``slab``
+    int64 [N, Hs, Ws] (or [N, 1, Hs, Ws]), ``size`` = (H, W) of the window, ``origins`` int32
+    [N, 2] on the device, rows (y0, x0) with 0 <= y0 <= Hs - H and 0 <= x0 <= Ws - W.  Returns
+    uint32 [N]: bit k set iff some window pixel equals k, 0 <= k < ``num_classes`` (2..32; any
+    other label value sets no bit).  No host sync."""
+    fn = "class_presence"
+    if not (slab.is_cuda and origins.is_cuda):
+        raise RuntimeError(f"rtsds_amd: {fn}: slab and origins must be HIP tensors; there is no CPU fallback")
+    slab = _mix_labels(fn, slab)
+    n, hs, ws = slab.shape
+    h, w = int(size[0]), int(size[1])
+    if not (0 < h <= hs and 0 < w <= ws):
+        raise RuntimeError(f"rtsds_amd: {fn}: the window {(h, w)} does not fit the source {(hs, ws)}")
+    if not 2 <= int(num_classes) <= 32:
+        raise RuntimeError(f"rtsds_amd: {fn}: num_classes must be in 2..32, got {num_classes}")
+    opitch = _mix_rows(fn, "origins", origins, n, 2, slab.device)
+    present = torch.empty(n, dtype=_U32, device=slab.device)
+    lib.rtsds_class_presence(_P(slab), _P(origins), opitch, _P(present), n, hs, ws, h, w, int(num_classes), stream())
+    return present
+
+
+def classmix(src, slab, tgt, pred, cbin, tbin, perm, origins, ignore_index, present=None, out=None, out_labels=None,
+             mask=None, chosen=None):
+    """ClassMix of a labelled source batch onto a target batch (rtsds_classmix), fused with the
+    target's thresholded pseudo-labels.  Per sample n the classes present in the source window at
+    ``origins[n]`` = (y0, x0) are ranked by their keys ``perm[n, k]`` (ties: lower class first)
+    and the first (count + 1) >> 1 are chosen; a window pixel whose source label s is a chosen
+    class takes the source pixel and the label s, every other pixel keeps the target pixel and
+    gets pred where cbin >= tbin[pred], else ``ignore_index`` (pseudo_select's rule).
+
+    ``src`` / ``tgt``: [N, 3, Hs, Ws] / [N, 3, H, W] image batches of one input form (bf16 or
+    fp32; NHWC, or the 4-channel pitch of pack_input marked ``_rt_cpad``) -- pixels are copied bit
+    for bit.  ``slab``: int64 [N, Hs, Ws] or [N, 1, Hs, Ws]; ``pred`` uint8 / ``cbin`` uint16
+    [N, H, W]; ``tbin`` int32 [c], 2 <= c <= 32; ``perm`` int32 [N, c] and ``origins`` int32
+    [N, 2] on the device (column slices of one block are fine).  ``present`` (uint32 [N]): the
+    result of class_presence for the same window, computed here when None.  Optional outputs:
+    ``out`` (an image batch of the inputs' form, [N, 3, H, W]), ``out_labels`` (int64 [N, H, W]),
+    ``mask`` (uint8 [N, H, W]: 1 where the source was pasted), ``chosen`` (uint32 [N]: the chosen
+    classes as a bit mask).  No host sync.  Returns ``(out, out_labels)``; ``out`` keeps the
+    ``_rt_cpad`` marker of the inputs, so the model's pack_input passes it through."""
+    fn = "classmix"
+    tensors = (src, slab, tgt, pred, cbin, tbin, perm, origins)
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError(f"rtsds_amd: {fn}: src, slab, tgt, pred, cbin, tbin, perm and origins must be HIP tensors; "
+                           "there is no CPU fallback")
+    dev = tgt.device
+    n, h, w, pitch = _mix_image(fn, "tgt", tgt)
+    ns, hs, ws, spitch = _mix_image(fn, "src", src)
+    if src.dtype != tgt.dtype or spitch != pitch or ns != n or src.device != dev:
+        raise RuntimeError(f"rtsds_amd: {fn}: src and tgt must share the batch size, the dtype, the image form and the "
+                           f"device, got {src.dtype} pitch {spitch} x{ns} on {src.device} and {tgt.dtype} pitch {pitch} "
+                           f"x{n} on {dev}")
+    if hs < h or ws < w:
+        raise RuntimeError(f"rtsds_amd: {fn}: the window {(h, w)} does not fit the source {(hs, ws)}")
+    slab = _mix_labels(fn, slab)
+    _pseudo_arg(fn, "slab", slab, torch.int64, (n, hs, ws), dev)
+    _pseudo_arg(fn, "pred", pred, torch.uint8, (n, h, w), dev)
+    _pseudo_arg(fn, "cbin", cbin, torch.uint16, (n, h, w), dev)
+    if tbin.dim() != 1 or not 2 <= tbin.numel() <= 32:
+        raise RuntimeError(f"rtsds_amd: {fn}: tbin must be int32 [c] with 2..32 classes, got {tuple(tbin.shape)}")
+    c = tbin.numel()
+    _pseudo_arg(fn, "tbin", tbin, torch.int32, (c,), dev)
+    ppitch = _mix_rows(fn, "perm", perm, n, c, dev)
+    opitch = _mix_rows(fn, "origins", origins, n, 2, dev)
+    if present is None:
+        present = class_presence(slab, (h, w), origins, c)
+    elif present.dtype not in (_U32, torch.int32):
+        raise RuntimeError(f"rtsds_amd: {fn}: present must be uint32 (or int32) [N], got {present.dtype}")
+    else:
+        _pseudo_arg(fn, "present", present, present.dtype, (n,), dev)
+    if out is None:
+        out = _mix_empty_image(n, h, w, pitch, tgt.dtype, dev)
+    else:
+        on, oh, ow, opx = _mix_image(fn, "out", out)
+        if (on, oh, ow, opx) != (n, h, w, pitch) or out.dtype != tgt.dtype or out.device != dev:
+            raise RuntimeError(f"rtsds_amd: {fn}: out must be a {tgt.dtype} {(n, 3, h, w)} batch of the inputs' image "
+                               f"form on {dev}, got {out.dtype} {tuple(out.shape)} pitch {opx} on {out.device}")
+    if out_labels is None:
+        out_labels = torch.empty((n, h, w), dtype=torch.int64, device=dev)
+    else:
+        _pseudo_arg(fn, "out_labels", out_labels, torch.int64, (n, h, w), dev)
+    if mask is not None:
+        _pseudo_arg(fn, "mask", mask, torch.uint8, (n, h, w), dev)
+    if chosen is not None:
+        if chosen.dtype not in (_U32, torch.int32):
+            raise RuntimeError(f"rtsds_amd: {fn}: chosen must be uint32 (or int32) [N], got {chosen.dtype}")
+        _pseudo_arg(fn, "chosen", chosen, chosen.dtype, (n,), dev)
+    lib.rtsds_classmix(_P(src), _P(slab), _P(tgt), _P(pred), _P(cbin), _P(tbin), _P(present), _P(perm), ppitch,
+                       _P(origins), opitch, _P(out), _P(out_labels), _P(mask), _P(chosen), n, hs, ws, h, w, c,
+                       pitch * tgt.element_size(), int(ignore_index), stream())
+    return out, out_labels
+
+
 class BCEWithLogitsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, target):

@@ -192,20 +192,27 @@ def self_training_config(config):
     missing = [k for k in SELF_TRAINING_KEYS if k not in st]
     if missing:
         raise RuntimeError(f"rtsds_amd: training.self_training lacks {', '.join(missing)}")
+    if st.get("mix") not in (None, "classmix"):  # optional: absent = pseudo-labels alone
+        raise RuntimeError(f"rtsds_amd: training.self_training.mix must be 'classmix' when given, got {st['mix']!r}")
     return st
 
 
 def self_train(config, st, model, optimizer, criterion, init_lr, power, lr_decay_iter, num_classes, target_dl,
-               validate, callbacks):
+               validate, callbacks, source_dl=None):
     """Class-balanced self-training after the normal run (rtsds_amd.selftrain): per round one
     sweep over the ordered target loader (generate), global per-class thresholds for the round's
     portion (class_thresholds), then ``epochs`` epochs of train.train on the thresholded labels
     with the branch's model, optimizer and criterion; lr = init_lr * lr_scale, poly-decayed over
-    all self-training iterations.  ``validate(epoch)`` runs after every epoch."""
+    all self-training iterations.  ``validate(epoch)`` runs after every epoch.  With the optional
+    key ``mix: classmix`` every batch is mixed with the next batch of the labelled ``source_dl``
+    (selftrain.ClassMixLoader) instead of carrying pseudo-labels alone."""
     from . import selftrain
     ignore_index = getattr(criterion, "ignore_index", None)
     if ignore_index is None:
         raise RuntimeError("rtsds_amd: --self_training needs a criterion with ignore_index (CrossEntropy)")
+    mix = st.get("mix")  # self_training_config: None or "classmix"
+    if mix is not None and source_dl is None:
+        raise RuntimeError("rtsds_amd: training.self_training.mix: classmix needs the labelled source loader")
     loader = ordered_target_loader(config, target_dl)
     max_iter = st["rounds"] * st["epochs"] * len(loader)
     for rnd in range(st["rounds"]):
@@ -216,7 +223,10 @@ def self_train(config, st, model, optimizer, criterion, init_lr, power, lr_decay
         kept = selftrain.kept_fraction(labels, tbin)
         print(f"Self-training round {rnd + 1}: portion {portion:.3f}, thresholds "
               f"{[round(int(b) / st['bins'], 3) for b in tbin]}, kept {[round(float(k), 3) for k in kept]}")
-        pseudo = selftrain.PseudoLabelLoader(loader, labels, tbin, ignore_index)
+        if mix is None:
+            pseudo = selftrain.PseudoLabelLoader(loader, labels, tbin, ignore_index)
+        else:
+            pseudo = selftrain.ClassMixLoader(loader, source_dl, labels, tbin, ignore_index)
         for e in range(st["epochs"]):
             epoch = rnd * st["epochs"] + e
             train(model=model, optimizer=optimizer, criterion=criterion, train_loader=pseudo, epoch=epoch,
@@ -278,7 +288,7 @@ def main(argv=None):
             self_train(config, st, g, g_opt, g_loss, g_hp["gen_init_lr"], g_hp["gen_power"], t["lr_decay_iter"],
                        t["num_classes"], target_dl,
                        lambda epoch: val_GTA5(epoch, g, val_dl, t["num_classes"], config.meta["class_names"],
-                                              callbacks, device=config.device), callbacks)
+                                              callbacks, device=config.device), callbacks, source_dl=gta_dl)
     else:
         if args.dataset == "gta5":
             train_dl = gta_dl
@@ -298,7 +308,7 @@ def main(argv=None):
                        lambda epoch: val(epoch=epoch, model=model, val_loader=val_dl, num_classes=t["num_classes"],
                                          class_names=config.meta["class_names"], detailed_report=True,
                                          device=config.device, callbacks=callbacks, scales=t.get("eval_scales"),
-                                         flip=bool(t.get("eval_flip", False))), callbacks)
+                                         flip=bool(t.get("eval_flip", False))), callbacks, source_dl=gta_dl)
 
 
 if __name__ == "__main__":

@@ -24,6 +24,14 @@ the loader must replay the same batches in the same order on every iteration (ma
 SyntheticLoader does; so does a non-shuffled, non-augmented transforms.DeviceLoader).  A
 different batch count or batch shape is refused; different images of the same shape cannot be
 detected.
+
+ClassMix.  Trained on pseudo-labels alone the network sees no ground-truth pixel and its own
+mistakes become its labels.  ``ClassMixLoader(target_loader, source_loader, labels, tbin,
+ignore_index)`` replaces PseudoLabelLoader (config key training.self_training.mix: classmix):
+every batch carries the pixels of half of the classes of a labelled source image, pasted into
+target context, with their true labels (the HIP kernels rtsds_class_presence and
+rtsds_classmix; the pseudo-label map of the target side is formed inside the mix and never
+materialised).
 """
 import math
 
@@ -181,6 +189,90 @@ class PseudoLabelLoader:
                                f"{len(self.labels)} were recorded")
 
 
+class ClassMixLoader(PseudoLabelLoader):
+    """PseudoLabelLoader with ClassMix (DACS): per target batch the next batch of the labelled
+    ``source_loader`` is drawn and, per sample, the pixels of half of the classes present in a
+    random target-sized window of the source image are pasted, image and label, onto the target
+    image; every other pixel keeps the target image and its thresholded pseudo-label.  Yields
+    ``(mixed_inputs, mixed_labels)`` -- inputs in the compute-dtype input form (pack_input),
+    labels int64 [N, 1, H, W] -- which train.train consumes unchanged.  One pair of launches per
+    batch (functional.class_presence + functional.classmix), no device -> host transfer.
+
+    ``loader`` / ``labels`` / ``tbin``: PseudoLabelLoader's contract (same replay order, same
+    refusals, ``set_thresholds``, ``len()``).  ``source_loader`` may be shuffled and augmented; it
+    is restarted with a fresh iter() when exhausted.  Of a source batch the first N_target samples
+    are used; one with fewer samples, or smaller than the target in H or W, raises RuntimeError.
+
+    Random draws, per sample in order, from torch's default CPU generator:
+    ``y0 = randint(0, Hs - H + 1, (1,))``, ``x0 = randint(0, Ws - W + 1, (1,))``,
+    ``perm = randperm(c)``; the int32 [N, 2 + c] block goes to the device in one copy.
+    ``last_chosen`` holds the last batch's chosen classes (uint32 bit masks [N], on the device)."""
+
+    def __init__(self, loader, source_loader, labels, tbin, ignore_index):
+        super().__init__(loader, labels, tbin, ignore_index)
+        self.source_loader = source_loader
+        self._source_iter = None
+        self.last_chosen = None
+
+    def _next_source(self):
+        for fresh in (False, True):
+            if self._source_iter is None or fresh:
+                self._source_iter = iter(self.source_loader)
+            try:
+                return next(self._source_iter)
+            except StopIteration:
+                continue
+        raise RuntimeError("rtsds_amd: ClassMixLoader: the source loader yielded no batch")
+
+    @staticmethod
+    def draw(n, c, hs, ws, h, w):
+        """The [n, 2 + c] int32 block of one batch's draws: rows (y0, x0, perm[0..c))."""
+        blk = torch.empty((n, 2 + c), dtype=torch.int32)
+        for i in range(n):
+            blk[i, 0] = torch.randint(0, hs - h + 1, (1,))
+            blk[i, 1] = torch.randint(0, ws - w + 1, (1,))
+            blk[i, 2:] = torch.randperm(c)
+        return blk
+
+    def __iter__(self):
+        from .runtime import compute_dtype
+        n, c = 0, self.labels.num_classes
+        for inputs, _ in self.loader:
+            if n >= len(self.labels):
+                raise RuntimeError(f"rtsds_amd: ClassMixLoader: the loader yielded more than the "
+                                   f"{len(self.labels)} recorded batches")
+            pred, cbin = self.labels.pred[n], self.labels.cbin[n]
+            nt, h, w = inputs.shape[0], inputs.shape[2], inputs.shape[3]
+            if tuple(pred.shape) != (nt, h, w):
+                raise RuntimeError(f"rtsds_amd: ClassMixLoader: batch {n} has shape {(nt, h, w)}, "
+                                   f"{tuple(pred.shape)} was recorded")
+            simg, slab = self._next_source()
+            if simg.shape[0] < nt or simg.shape[2] < h or simg.shape[3] < w:
+                raise RuntimeError(f"rtsds_amd: ClassMixLoader: the source batch {tuple(simg.shape)} is smaller than "
+                                   f"the target batch {tuple(inputs.shape)} (samples, H or W)")
+            if slab.shape[0] != simg.shape[0] or tuple(slab.shape[-2:]) != tuple(simg.shape[-2:]):
+                raise RuntimeError(f"rtsds_amd: ClassMixLoader: source labels {tuple(slab.shape)} do not match the "
+                                   f"source images {tuple(simg.shape)}")
+            dev = pred.device if pred.is_cuda else self.labels.hist.device
+            if not pred.is_cuda:  # store="cpu": back to the device of the sweep
+                pred, cbin = pred.to(dev, non_blocking=True), cbin.to(dev, non_blocking=True)
+            hs, ws = simg.shape[2], simg.shape[3]
+            blk = self.draw(nt, c, hs, ws, h, w).to(dev, non_blocking=True)
+            dtype = compute_dtype()
+            tgt = F.pack_input(inputs.to(dev), dtype)
+            src = F.pack_input(simg[:nt].to(dev), dtype)
+            slab = slab[:nt].to(dev).long().contiguous()
+            chosen = torch.empty(nt, dtype=F._U32, device=dev)
+            mixed, mixed_labels = F.classmix(src, slab, tgt, pred, cbin, self._tbin_on(dev), blk[:, 2:], blk[:, :2],
+                                             self.ignore_index, chosen=chosen)
+            self.last_chosen = chosen
+            yield mixed, mixed_labels.unsqueeze(1)
+            n += 1
+        if n != len(self.labels):
+            raise RuntimeError(f"rtsds_amd: ClassMixLoader: the loader yielded {n} batches, "
+                               f"{len(self.labels)} were recorded")
+
+
 def kept_fraction(labels, tbin):
     """Per-class share of the predicted pixels that ``tbin`` keeps (float64 numpy [c]; NaN for a
     class nothing was predicted as), from the histogram alone -- for logging."""
@@ -192,4 +284,4 @@ def kept_fraction(labels, tbin):
     return np.where(total > 0, kept / np.maximum(total, 1), np.nan)
 
 
-__all__ = ["class_thresholds", "generate", "PseudoLabels", "PseudoLabelLoader", "kept_fraction"]
+__all__ = ["class_thresholds", "generate", "PseudoLabels", "PseudoLabelLoader", "ClassMixLoader", "kept_fraction"]
