@@ -792,11 +792,6 @@ static void with_act(int act, F f) {
   else if (act == RTSDS_ACT_RELU) f(std::integral_constant<int, RTSDS_ACT_RELU>());
   else f(std::integral_constant<int, -1>());
 }
-template <typename F>
-static void with_bool(bool b, F f) {
-  if (b) f(std::true_type());
-  else f(std::false_type());
-}
 // f(BnKind<T, VEC>) for the storage type and channel vector of (dtype, c)
 template <typename T_, int VEC_> struct BnKind {
   typedef T_ T;

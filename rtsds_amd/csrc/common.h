@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/rtsds_hip.h"
 
@@ -135,3 +136,9 @@ RT_DEV void buf_lds16(rsrc_t, void*, int, int) {}
   } while (0)
 
 static inline int rt_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// f(std::true_type / std::false_type): a runtime flag as a compile-time kernel parameter
+template <typename F>
+static void with_bool(bool b, F f) {
+  if (b) f(std::true_type());
+  else f(std::false_type());
+}

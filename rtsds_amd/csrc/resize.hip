@@ -1,5 +1,14 @@
 // Bilinear resize (align_corners=False), forward and backward, and the kernels fused onto it
 // (gfx950): resize + softmax for the discriminator input, multi-scale / flip evaluation.
+// Every output bit of the unit is pinned (tests/test_resize_bits_gpu.py), and each piece that
+// carries a bit-exactness promise exists once:
+//   bil_src / bil_mix / bil_first_ge (common.h)   taps, weights, the blend's association
+//   bil_stage_rows, BilWalk                       forward: source rows -> fp32 LDS; a dense output vector's elements
+//   bil_row_group, bil_group_store                forward: the output rows sharing a top tap, written from t0 / t1
+//   bil_adj_range, bil_weight, bil_gather         backward: which outputs an input reads, their weights, the sum's order
+//   bil_table_build, bil_table_span, BilTables    backward: the weight tables in LDS
+//   bil_bwd_h_launch                              the vertical pass (bilinear and resize + softmax backward)
+//   upsm_tile, upsm_probs                         resize + softmax: one tile's staging, one pixel's probabilities
 #include "ew_common.h"
 
 // ------------------------------------------------------------------ bilinear (align_corners=False)
@@ -47,9 +56,32 @@ __global__ void bilinear_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, 
   }
 }
 
+// Row groups (upsampling): every output row whose top tap is source row h0 blends the same two
+// horizontal blends t0 / t1 (bil_mix's inner terms), so a thread forms them once and writes all
+// of the group's rows (~ the scale factor of them) as bil_mix's outer fmaf -- bil_mix bit for bit.
+// bil_row_group: the group's output rows [oa, ob) (empty when downsampling skips h0) and bottom tap h1
+RT_DEV bool bil_row_group(int h0, float sh, int hi, int ho, int& oa, int& ob, int& h1) {
+  oa = bil_first_ge(h0, sh, hi, ho);
+  ob = bil_first_ge(h0 + 1, sh, hi, ho);
+  h1 = h0 + (h0 < hi - 1 ? 1 : 0);
+  return oa < ob;
+}
+// one 16-B vector of output row oh from its column's t0 / t1
+template <typename T>
+RT_DEV void bil_group_store(T* dst, const float (&t0)[VecT<T>::N], const float (&t1)[VecT<T>::N], int oh, float sh, int hi) {
+  constexpr int V = VecT<T>::N;
+  int i0, i1;
+  float lh0, lh1;
+  bil_src(oh, sh, hi, i0, i1, lh0, lh1);
+  typename VecT<T>::v16 r;
+#pragma unroll
+  for (int k = 0; k < V; ++k) r[k] = from_f<T>(fmaf(lh1, t1[k], lh0 * t0[k]));
+  *(typename VecT<T>::v16*)dst = r;
+}
+
 // Upsampling with 16-B channel vectors (the context-path resizes into the FFM concat): one thread
-// per (image, source row h0, output column, channel vector) loads the 4 taps once, forms bil_mix's
-// two horizontal blends and writes every output row whose top tap is h0 (bit-identical to MODE 0;
+// per (image, source row h0, output column, channel vector) loads the 4 taps once, forms the
+// two horizontal blends and writes the row group of h0 (bit-identical to MODE 0;
 // the taps are gathered once per source row instead of once per output row).  s1 / s2 (optional,
 // [n][c]): channel scales applied to each tap first, rounded to T after each as the stored
 // rtsds_chscale_fwd outputs would be (BiSeNet's attention refinement, build_bisenet.py:42-53,
@@ -65,9 +97,8 @@ __global__ void __launch_bounds__(256) bilinear_fwd_group_vec_kernel(const T* __
   // any arithmetic (U x 4 loads in flight instead of 4 per thread-lifetime).
   const int cpp = c / V, nv = wo * cpp;
   const int img = blockIdx.y / hi, h0 = blockIdx.y - img * hi;
-  const int oa = bil_first_ge(h0, sh, hi, ho), ob = bil_first_ge(h0 + 1, sh, hi, ho);
-  const int h1 = h0 + (h0 < hi - 1 ? 1 : 0);
-  if (oa >= ob) return;
+  int oa, ob, h1;
+  if (!bil_row_group(h0, sh, hi, ho, oa, ob, h1)) return;
   const int i0 = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
   const T* xb = x + (long)img * hi * wi * c;
   V16 a[U], bb[U], cc[U], dd[U], k1[U], k2[U];
@@ -103,15 +134,8 @@ __global__ void __launch_bounds__(256) bilinear_fwd_group_vec_kernel(const T* __
       t0[j] = fmaf(lw1[u], tap(bb[u][j], j), lw0[u] * tap(a[u][j], j));
       t1[j] = fmaf(lw1[u], tap(dd[u][j], j), lw0[u] * tap(cc[u][j], j));
     }
-    for (int oh = oa; oh < ob; ++oh) {
-      int i0_, i1_;
-      float lh0, lh1;
-      bil_src(oh, sh, hi, i0_, i1_, lh0, lh1);
-      V16 r;
-#pragma unroll
-      for (int j = 0; j < V; ++j) r[j] = from_f<T>(fmaf(lh1, t1[j], lh0 * t0[j]));
-      *(V16*)(y + (((long)img * ho + oh) * wo + ow) * yld + yoff + chunk * V) = r;
-    }
+    for (int oh = oa; oh < ob; ++oh)
+      bil_group_store(y + (((long)img * ho + oh) * wo + ow) * yld + yoff + chunk * V, t0, t1, oh, sh, hi);
   }
 }
 
@@ -121,6 +145,39 @@ __global__ void __launch_bounds__(256) bilinear_fwd_group_vec_kernel(const T* __
 // dense output row (a wave writes 1 KB contiguously; the whole-pixel loop wrote 38-B runs at a
 // 38-B lane stride, 1.8 TB/s) from 4 LDS taps per element.  Same taps, weights and bil_mix
 // expression as the other modes.
+// bil_stage_rows: two source rows (or a column window of them), n1 elements each -> fp32 LDS
+// [2][n1], coalesced; the caller places the barrier
+template <typename T>
+RT_DEV void bil_stage_rows(const T* __restrict__ r0, const T* __restrict__ r1, float* rows, int n1) {
+  for (int e = threadIdx.x; e < n1; e += 256) {
+    rows[e] = to_f(r0[e]);
+    rows[n1 + e] = to_f(r1[e]);
+  }
+}
+// BilWalk: a dense [wo][c] output row walked element by element from flat element e, across pixel
+// boundaries: taps() gives the element's w0 / w1 taps in the staged top row (bottom row: + wi * c),
+// leaves their weights in lw0 / lw1 and steps to the next element.  (A stepper, not a helper that
+// fills t0 / t1 or calls back per element: either form cost bilinear_fwd_rowgroup_kernel 22 - 48
+// more register moves and 5 more waits, 62.97 -> 63.75 us at the fp32 x8 19-class shape.)
+struct BilWalk {
+  int ow, ch, w0, w1;
+  float lw0, lw1;
+  RT_DEV BilWalk(int e, int c, int wi, float sw, const FastDiv& f_c) {
+    ow = (int)fdiv((uint32_t)e, f_c);
+    ch = e - ow * c;
+    bil_src(ow, sw, wi, w0, w1, lw0, lw1);
+  }
+  RT_DEV void taps(const float* rows, int c, int wi, float sw, const float*& a, const float*& b) {
+    if (ch == c) {
+      ch = 0;
+      ++ow;
+      bil_src(ow, sw, wi, w0, w1, lw0, lw1);
+    }
+    a = rows + w0 * c + ch;
+    b = rows + w1 * c + ch;
+    ++ch;
+  }
+};
 template <typename T>
 __global__ void __launch_bounds__(256) bilinear_fwd_rows_kernel(const T* __restrict__ x, T* __restrict__ y, int hi, int wi, int c,
                                                                  int ho, int wo, float sh, float sw, FastDiv f_c) {
@@ -132,62 +189,38 @@ __global__ void __launch_bounds__(256) bilinear_fwd_rows_kernel(const T* __restr
   float lh0, lh1;
   bil_src(oh, sh, hi, h0, h1, lh0, lh1);
   const int rl = wi * c;
-  const T* r0 = x + ((long)img * hi + h0) * rl;
-  const T* r1 = x + ((long)img * hi + h1) * rl;
-  for (int e = threadIdx.x; e < rl; e += 256) {
-    rows[e] = to_f(r0[e]);
-    rows[rl + e] = to_f(r1[e]);
-  }
+  bil_stage_rows(x + ((long)img * hi + h0) * rl, x + ((long)img * hi + h1) * rl, rows, rl);
   __syncthreads();
   const int nv = wo * c / V;  // (wo * c) % V == 0 (host)
   T* yo = y + (long)row * wo * c;
   for (int v = threadIdx.x; v < nv; v += 256) {
-    const int e = v * V;
-    int ow = (int)fdiv((uint32_t)e, f_c), ch = e - ow * c;
-    int w0, w1;
-    float lw0, lw1;
-    bil_src(ow, sw, wi, w0, w1, lw0, lw1);
+    BilWalk w(v * V, c, wi, sw, f_c);
     V16 r;
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      if (ch == c) {
-        ch = 0;
-        ++ow;
-        bil_src(ow, sw, wi, w0, w1, lw0, lw1);
-      }
-      const float* a = rows + w0 * c + ch;
-      const float* b = rows + w1 * c + ch;
-      r[k] = from_f<T>(bil_mix(a[0], b[0], a[rl], b[rl], lh0, lh1, lw0, lw1));
-      ++ch;
+      const float *a, *b;
+      w.taps(rows, c, wi, sw, a, b);
+      r[k] = from_f<T>(bil_mix(a[0], b[0], a[rl], b[rl], lh0, lh1, w.lw0, w.lw1));
     }
-    *(V16*)(yo + e) = r;
+    *(V16*)(yo + v * V) = r;
   }
 }
 
-// The same resize for upsampling, one workgroup per (image, source row h0, column chunk): every
-// output row whose top tap is h0 blends the same two horizontal blends t0 / t1 (bil_mix's inner
-// terms), so each thread computes them once for its J output vectors of the chunk, keeps them in
-// registers and writes all of the group's rows (~ the scale factor of them) as
-// fmaf(lh1, t1, lh0 * t0) -- bil_mix bit for bit, at 2 VALU ops per element instead of ~12 and
-// 4 LDS reads per element per group instead of per row.
+// The same resize for upsampling, one workgroup per (image, source row h0, column chunk): each
+// thread computes t0 / t1 once for its J output vectors of the chunk, keeps them in registers and
+// writes the row group of h0 -- 2 VALU ops per element instead of ~12 and 4 LDS reads per
+// element per group instead of per row.
 template <typename T, int J>
 __global__ void __launch_bounds__(256) bilinear_fwd_rowgroup_kernel(const T* __restrict__ x, T* __restrict__ y, int hi, int wi, int c,
                                                                      int ho, int wo, float sh, float sw, int nchunk, FastDiv f_c) {
-  typedef typename VecT<T>::v16 V16;
   constexpr int V = VecT<T>::N;
   extern __shared__ float rows[];  // [2][wi * c]
   const int grp = blockIdx.x / nchunk, chunk = blockIdx.x - grp * nchunk;
   const int img = grp / hi, h0 = grp - img * hi;
-  const int oa = bil_first_ge(h0, sh, hi, ho), ob = bil_first_ge(h0 + 1, sh, hi, ho);
-  if (oa >= ob) return;  // no output row starts at h0 (downsampling): whole workgroup
-  const int h1 = h0 + (h0 < hi - 1 ? 1 : 0);
+  int oa, ob, h1;
+  if (!bil_row_group(h0, sh, hi, ho, oa, ob, h1)) return;  // whole workgroup
   const int rl = wi * c;
-  const T* r0 = x + ((long)img * hi + h0) * rl;
-  const T* r1 = x + ((long)img * hi + h1) * rl;
-  for (int e = threadIdx.x; e < rl; e += 256) {
-    rows[e] = to_f(r0[e]);
-    rows[rl + e] = to_f(r1[e]);
-  }
+  bil_stage_rows(x + ((long)img * hi + h0) * rl, x + ((long)img * hi + h1) * rl, rows, rl);
   __syncthreads();
   const int nv = wo * c / V;  // (wo * c) % V == 0 (host)
   const int v0 = (int)((long)nv * chunk / nchunk), v1 = (int)((long)nv * (chunk + 1) / nchunk);
@@ -196,53 +229,39 @@ __global__ void __launch_bounds__(256) bilinear_fwd_rowgroup_kernel(const T* __r
   for (int j = 0; j < J; ++j) {
     const int v = v0 + threadIdx.x + 256 * j;
     if (v >= v1) break;
-    const int e = v * V;
-    int ow = (int)fdiv((uint32_t)e, f_c), ch = e - ow * c;
-    int w0, w1;
-    float lw0, lw1;
-    bil_src(ow, sw, wi, w0, w1, lw0, lw1);
+    BilWalk w(v * V, c, wi, sw, f_c);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      if (ch == c) {
-        ch = 0;
-        ++ow;
-        bil_src(ow, sw, wi, w0, w1, lw0, lw1);
-      }
-      const float* a = rows + w0 * c + ch;
-      const float* b = rows + w1 * c + ch;
-      t0[j][k] = fmaf(lw1, b[0], lw0 * a[0]);
-      t1[j][k] = fmaf(lw1, b[rl], lw0 * a[rl]);
-      ++ch;
+      const float *a, *b;
+      w.taps(rows, c, wi, sw, a, b);
+      t0[j][k] = fmaf(w.lw1, b[0], w.lw0 * a[0]);
+      t1[j][k] = fmaf(w.lw1, b[rl], w.lw0 * a[rl]);
     }
   }
   for (int oh = oa; oh < ob; ++oh) {
-    int i0, i1;
-    float lh0, lh1;
-    bil_src(oh, sh, hi, i0, i1, lh0, lh1);
     T* yo = y + ((long)img * ho + oh) * wo * c;
 #pragma unroll
     for (int j = 0; j < J; ++j) {
       const int v = v0 + threadIdx.x + 256 * j;
       if (v >= v1) break;
-      V16 r;
-#pragma unroll
-      for (int k = 0; k < V; ++k) r[k] = from_f<T>(fmaf(lh1, t1[j][k], lh0 * t0[j][k]));
-      *(V16*)(yo + (long)v * V) = r;
+      bil_group_store(yo + (long)v * V, t0[j], t1[j], oh, sh, hi);
     }
   }
 }
 
-static const bool kBilRowGroup = true;
 static constexpr auto kBilGroupU = 4;  // column vectors per thread of bilinear_fwd_group_vec_kernel (1 / 2 / 4: 48 / 43 / 41 us, profiles/r6f)
 static constexpr auto kBilJ = 2;  // output vectors per thread and column chunk (2, 3, 4, 6 measured: 2 best)
 
 // Backward, separable gather (deterministic, no atomics): input index i along one axis
 // receives from outputs o with i0(o) == i (weight l0) or i1(o) == i (weight l1); those o lie
 // in [(i-0.5)/s - 0.5, (i+1.5)/s - 0.5], widened by one and tested exactly with bil_src.
-RT_DEV float bil_wsum_range(int i, float s, int in, int out, int& lo, int& hi) {
-  lo = max(0, (int)floorf(((float)i - 0.5f) / s - 0.5f) - 1);
-  hi = min(out - 1, (int)ceilf(((float)i + 1.5f) / s - 0.5f) + 1);
-  return 0.f;
+// bil_adj_range: the outputs [lo, hi] that inputs [i0, i1] may receive from; the host sizes tables
+// and LDS segments with the same function, so it computes exactly what the device computes.
+__host__ __device__ inline void bil_adj_range(int i0, int i1, float s, int out, int& lo, int& hi) {
+  lo = (int)floorf(((float)i0 - 0.5f) / s - 0.5f) - 1;
+  hi = (int)ceilf(((float)i1 + 1.5f) / s - 0.5f) + 1;
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > out - 1 ? out - 1 : hi;
 }
 RT_DEV float bil_weight(int o, int i, float s, int in) {
   int a0, a1;
@@ -250,104 +269,109 @@ RT_DEV float bil_weight(int o, int i, float s, int in) {
   bil_src(o, s, in, a0, a1, l0, l1);
   return (a0 == i ? l0 : 0.f) + (a1 == i ? l1 : 0.f);
 }
-// pass 1 (W): tmp[img][oh][iw][c] = sum_ow w(ow->iw) dy[img][oh][ow][c]   (fp32)
-template <typename T>
-__global__ void bilinear_bwd_w_kernel(const T* __restrict__ dy, float* __restrict__ tmp, int n, int wi, int c, int ho, int wo, float sw,
-                                      int dyld, int dyoff) {
-  const long total = (long)n * ho * wi * c;
-  GRID_STRIDE(i, total) {
-    const int ch = (int)(i % c);
-    long q = i / c;
-    const int iw = (int)(q % wi);
-    const long row = q / wi;  // img * ho + oh
-    int lo, hi;
-    bil_wsum_range(iw, sw, wi, wo, lo, hi);
-    const T* src = dy + row * wo * dyld + dyoff + ch;
-    float acc = 0.f;
-    for (int ow = lo; ow <= hi; ++ow) {
-      const float wt = bil_weight(ow, iw, sw, wi);
-      if (wt != 0.f) acc = fmaf(wt, to_f(src[(long)ow * dyld]), acc);
-    }
-    tmp[i] = acc;
+// bil_gather: the adjoint sum of one input element over its cnt candidate outputs, src[j * stride]
+// with weight(j) -- ascending j, zero weights skipped, one fmaf per tap: the summation order of
+// every width and height pass, tabulated or not
+template <typename S, typename I, typename W>
+RT_DEV float bil_gather(const S* src, I stride, int cnt, W weight) {
+  float acc = 0.f;
+  for (int j = 0; j < cnt; ++j) {
+    const float wt = weight(j);
+    if (wt != 0.f) acc = fmaf(wt, to_f(src[j * stride]), acc);
   }
+  return acc;
 }
-// pass 2 (H): dx[img][ih][iw][c] = sum_oh w(oh->ih) tmp[img][oh][iw][c]
-template <typename T>
-__global__ void bilinear_bwd_h_kernel(const float* __restrict__ tmp, T* __restrict__ dx, int n, int hi, int wi, int c, int ho, float sh) {
-  const long total = (long)n * hi * wi * c;
-  const long plane = (long)wi * c;
-  GRID_STRIDE(i, total) {
-    const long inner = i % plane;  // iw * c + ch
-    long q = i / plane;
-    const int ih = (int)(q % hi);
-    const int img = (int)(q / hi);
-    int lo, hh;
-    bil_wsum_range(ih, sh, hi, ho, lo, hh);
-    const float* src = tmp + (long)img * ho * plane + inner;
-    float acc = 0.f;
-    for (int oh = lo; oh <= hh; ++oh) {
-      const float wt = bil_weight(oh, ih, sh, hi);
-      if (wt != 0.f) acc = fmaf(wt, src[(long)oh * plane], acc);
-    }
-    dx[i] = from_f<T>(acc);
-  }
-}
-// Table-driven variants of the two passes: the weights of one axis (per input index i: lo(i)
-// and w(lo + j -> i), zero past hi(i)) are tabulated once per block in LDS instead of being
-// re-derived (two bil_src evaluations) for every element and tap; same taps, same order, same
-// zero skipping, so the sums are bit-identical to the kernels above.
+// Weight tables: the weights of one axis (per input index i: lo(i) and w(lo + j -> i), zero past
+// hi(i)) tabulated once per block in LDS instead of being re-derived (two bil_src evaluations)
+// for every element and tap.  Rows for inputs [i0, i0 + cnt); tlo = lo(i) - origin.
 static const int kBilTabLds = 48 * 1024;
-RT_DEV void bil_table_build(float* tab, int* tlo, int in, int out, float s, int maxw) {
-  for (int e = threadIdx.x; e < in * maxw; e += blockDim.x) {
-    const int i = e / maxw, j = e - i * maxw;
+static size_t bil_tab_bytes(int in, int maxw) { return ((size_t)in * maxw + in) * 4; }
+RT_DEV void bil_table_build(float* tab, int* tlo, int i0, int cnt, int in, int out, float s, int maxw, int origin) {
+  for (int e = threadIdx.x; e < cnt * maxw; e += blockDim.x) {
+    const int il = e / maxw, j = e - il * maxw, i = i0 + il;
     int lo, hi;
-    bil_wsum_range(i, s, in, out, lo, hi);
+    bil_adj_range(i, i, s, out, lo, hi);
     tab[e] = lo + j <= hi ? bil_weight(lo + j, i, s, in) : 0.f;
-    if (j == 0) tlo[i] = lo;
+    if (j == 0) tlo[il] = lo - origin;
   }
   __syncthreads();
 }
-template <typename T>
-__global__ void bilinear_bwd_w_tab_kernel(const T* __restrict__ dy, float* __restrict__ tmp, int n, int wi, int c, int ho, int wo,
-                                          float sw, int dyld, int dyoff, int maxw, FastDiv f_c, FastDiv f_wi) {
+// The two passes, each with its weights from a table in LDS (TAB: the table fits and the index
+// math fits 32 bits) or computed per tap; bil_gather either way, so the sums are bit-identical.
+// pass 1 (W): tmp[img][oh][iw][c] = sum_ow w(ow->iw) dy[img][oh][ow][c]   (fp32)
+template <typename T, bool TAB>
+__global__ void bilinear_bwd_w_kernel(const T* __restrict__ dy, float* __restrict__ tmp, int n, int wi, int c, int ho, int wo, float sw,
+                                      int dyld, int dyoff, int maxw, FastDiv f_c, FastDiv f_wi) {
   extern __shared__ float tab[];
   int* tlo = (int*)(tab + wi * maxw);
-  bil_table_build(tab, tlo, wi, wo, sw, maxw);
-  const long total = (long)n * ho * wi * c;  // < 2^31 (host)
+  if (TAB) bil_table_build(tab, tlo, 0, wi, wi, wo, sw, maxw, 0);
+  const long total = (long)n * ho * wi * c;  // TAB: < 2^31 (host)
   GRID_STRIDE(i, total) {
-    const uint32_t q = fdiv((uint32_t)i, f_c), row = fdiv(q, f_wi);
-    const int ch = (int)((uint32_t)i - q * c), iw = (int)(q - row * wi);
-    const float* w = tab + iw * maxw;
-    const T* src = dy + ((long)row * wo + tlo[iw]) * dyld + dyoff + ch;
-    float acc = 0.f;
-    for (int j = 0; j < maxw; ++j) {
-      const float wt = w[j];
-      if (wt != 0.f) acc = fmaf(wt, to_f(src[(long)j * dyld]), acc);
+    if (TAB) {
+      const uint32_t q = fdiv((uint32_t)i, f_c), row = fdiv(q, f_wi);  // row = img * ho + oh
+      const int ch = (int)((uint32_t)i - q * c), iw = (int)(q - row * wi);
+      const float* w = tab + iw * maxw;
+      tmp[i] = bil_gather(dy + ((long)row * wo + tlo[iw]) * dyld + dyoff + ch, (long)dyld, maxw, [&](int j) { return w[j]; });
+    } else {
+      const int ch = (int)(i % c);
+      const long q = i / c, row = q / wi;
+      const int iw = (int)(q % wi);
+      int lo, hi;
+      bil_adj_range(iw, iw, sw, wo, lo, hi);
+      tmp[i] = bil_gather(dy + (row * wo + lo) * dyld + dyoff + ch, (long)dyld, hi - lo + 1,
+                          [&](int j) { return bil_weight(lo + j, iw, sw, wi); });
     }
-    tmp[i] = acc;
   }
 }
-template <typename T>
-__global__ void bilinear_bwd_h_tab_kernel(const float* __restrict__ tmp, T* __restrict__ dx, int n, int hi, int wi, int c, int ho,
-                                          float sh, int maxh, FastDiv f_plane, FastDiv f_hi) {
+// pass 2 (H): dx[img][ih][iw][c] = sum_oh w(oh->ih) tmp[img][oh][iw][c]
+template <typename T, bool TAB>
+__global__ void bilinear_bwd_h_kernel(const float* __restrict__ tmp, T* __restrict__ dx, int n, int hi, int wi, int c, int ho, float sh,
+                                      int maxh, FastDiv f_plane, FastDiv f_hi) {
   extern __shared__ float tab[];
   int* tlo = (int*)(tab + hi * maxh);
-  bil_table_build(tab, tlo, hi, ho, sh, maxh);
-  const uint32_t plane = (uint32_t)wi * c;
-  const long total = (long)n * hi * plane;  // < 2^31 (host)
+  if (TAB) bil_table_build(tab, tlo, 0, hi, hi, ho, sh, maxh, 0);
+  const long plane = (long)wi * c;
+  const long total = (long)n * hi * plane;  // TAB: < 2^31 (host)
   GRID_STRIDE(i, total) {
-    const uint32_t q = fdiv((uint32_t)i, f_plane), img = fdiv(q, f_hi);
-    const uint32_t inner = (uint32_t)i - q * plane;
-    const int ih = (int)(q - img * hi);
-    const float* w = tab + ih * maxh;
-    const float* src = tmp + ((long)img * ho + tlo[ih]) * plane + inner;
-    float acc = 0.f;
-    for (int j = 0; j < maxh; ++j) {
-      const float wt = w[j];
-      if (wt != 0.f) acc = fmaf(wt, src[(long)j * plane], acc);
+    if (TAB) {
+      const uint32_t q = fdiv((uint32_t)i, f_plane), img = fdiv(q, f_hi);
+      const uint32_t inner = (uint32_t)i - q * (uint32_t)plane;  // iw * c + ch
+      const int ih = (int)(q - img * hi);
+      const float* w = tab + ih * maxh;
+      dx[i] = from_f<T>(bil_gather(tmp + ((long)img * ho + tlo[ih]) * plane + inner, plane, maxh, [&](int j) { return w[j]; }));
+    } else {
+      const long inner = i % plane, q = i / plane;
+      const int ih = (int)(q % hi), img = (int)(q / hi);
+      int lo, hh;
+      bil_adj_range(ih, ih, sh, ho, lo, hh);
+      dx[i] = from_f<T>(bil_gather(tmp + ((long)img * ho + lo) * plane + inner, plane, hh - lo + 1,
+                                   [&](int j) { return bil_weight(lo + j, ih, sh, hi); }));
     }
-    dx[i] = from_f<T>(acc);
   }
+}
+// most outputs any input index of an axis receives from.  The + 1 dates from a host copy of the
+// range formula that might have rounded differently; it is part of every table's row length and
+// LDS byte count (and so of the routes taken), so it stays.
+static int bil_maxw(int in, int out, float s) {
+  int m = 0;
+  for (int i = 0; i < in; ++i) {
+    int lo, hi;
+    bil_adj_range(i, i, s, out, lo, hi);
+    m = std::max(m, hi - lo + 1);
+  }
+  return m + 1;
+}
+// the H pass of the bilinear backward and of the resize + softmax backward
+template <typename T>
+static void bil_bwd_h_launch(const float* tmp, T* dx, int n, int hi, int wi, int c, int ho, float sh, hipStream_t st) {
+  const long th = (long)n * hi * wi * c;
+  const int mh = bil_maxw(hi, ho, sh);
+  const size_t bh = bil_tab_bytes(hi, mh);
+  with_bool(th < (1L << 31) && bh <= (size_t)kBilTabLds, [&](auto tab) {
+    constexpr bool TAB = decltype(tab)::value;
+    hipLaunchKernelGGL((bilinear_bwd_h_kernel<T, TAB>), dim3(ew_blocks(th)), dim3(256), TAB ? bh : 0, st, tmp, dx, n, hi, wi, c, ho,
+                       sh, mh, TAB ? fastdiv_make((uint32_t)wi * c) : FastDiv{}, fastdiv_make(hi));
+  });
 }
 // [first, last] nonzero entry of each table row, packed first | (last + 1) << 16 (the tables
 // carry a one-entry margin either side, so a plain loop over maxw wastes taps)
@@ -363,175 +387,119 @@ RT_DEV void bil_table_span(const float* tab, int* span, int in, int maxw) {
   }
   __syncthreads();
 }
-// Both passes in one kernel for 16-B channel vectors: a thread owns V channels of one input
-// pixel and forms each output row's W-pass sum t (the W kernel's taps, order and zero skipping,
-// fp32) right before the H-pass FMA that consumes it -- the same two fp32 FMA chains, so dx is
-// bit-identical to the two-pass kernels, without the fp32 [ho][wi] intermediate's write and
-// re-read.  Neighbouring input pixels re-read dY rows through L2 (XCD-aware block order).
-// Only each row's nonzero span is visited, and its column taps go four at a time: the four
-// loads issued (clamped into the span) before their FMAs, a zero weight leaving t unchanged
-// exactly as the skipped tap of the two-pass kernel.
-template <typename T, int G>
-__global__ void __launch_bounds__(256) bilinear_bwd_fused_vec_kernel(const T* __restrict__ dy, T* __restrict__ dx, int hi, int wi,
-                                                                     int c, int ho, int wo, float sh, float sw, int dyld, int dyoff,
-                                                                     int maxh, int maxw, long total, FastDiv f_cv, FastDiv f_wi,
-                                                                     FastDiv f_hi) {
+// The fused backward's LDS: the W and H weight tables with their first output and nonzero span per
+// row.  bytes() is the dynamic LDS the host launches with.
+struct BilTables {
+  float *wtab, *htab;
+  int *wlo, *hlo, *wspan, *hspan;
+  static size_t bytes(int hi, int wi, int maxh, int maxw) { return bil_tab_bytes(wi, maxw) + bil_tab_bytes(hi, maxh) + (wi + hi) * 4; }
+  RT_DEV BilTables(float* lds, int hi, int wi, int ho, int wo, float sh, float sw, int maxh, int maxw) {
+    wtab = lds;
+    wlo = (int*)(wtab + wi * maxw);
+    htab = (float*)(wlo + wi);
+    hlo = (int*)(htab + hi * maxh);
+    wspan = hlo + hi;
+    hspan = wspan + wi;
+    bil_table_build(wtab, wlo, 0, wi, wi, wo, sw, maxw, 0);
+    bil_table_build(htab, hlo, 0, hi, hi, ho, sh, maxh, 0);
+    bil_table_span(wtab, wspan, wi, maxw);
+    bil_table_span(htab, hspan, hi, maxh);
+  }
+};
+// Both passes in one kernel: a thread owns W channels of one input pixel (W = the 16-B vector
+// when c, the pitch and the offset of dY allow it; else 1 with dY dense, the supervision heads'
+// 19-class logits: adjacent lanes read adjacent channels, so each tap's loads stay contiguous
+// across the wave) and forms each output row's W-pass sum t (the W kernel's taps, order and
+// zero skipping, fp32) right before the H-pass FMA that consumes it -- the same two fp32 FMA
+// chains, so dx is bit-identical to the two-pass kernels, without the fp32 [ho][wi]
+// intermediate's write and re-read.  Neighbouring input pixels re-read dY rows through L2
+// (XCD-aware block order).  Only each row's nonzero span is visited, and its column taps go G
+// at a time: the G loads issued (clamped into the span) before their FMAs, a zero weight
+// leaving t unchanged exactly as the skipped tap of the two-pass kernel.
+template <typename T, int W, int G>
+__global__ void __launch_bounds__(256) bilinear_bwd_fused_kernel(const T* __restrict__ dy, T* __restrict__ dx, int hi, int wi, int c,
+                                                                 int ho, int wo, float sh, float sw, int dyld, int dyoff, int maxh,
+                                                                 int maxw, long total, FastDiv f_cw, FastDiv f_wi, FastDiv f_hi) {
   extern __shared__ float tab[];
-  float* wtab = tab;
-  int* wlo = (int*)(wtab + wi * maxw);
-  float* htab = (float*)(wlo + wi);
-  int* hlo = (int*)(htab + hi * maxh);
-  int* wspan = hlo + hi;
-  int* hspan = wspan + wi;
-  bil_table_build(wtab, wlo, wi, wo, sw, maxw);
-  bil_table_build(htab, hlo, hi, ho, sh, maxh);
-  bil_table_span(wtab, wspan, wi, maxw);
-  bil_table_span(htab, hspan, hi, maxh);
-  typedef typename VecT<T>::v16 V16;
-  constexpr int V = VecT<T>::N;
-  const int cv = c / V;
+  const BilTables tb(tab, hi, wi, ho, wo, sh, sw, maxh, maxw);
+  typedef T VW __attribute__((ext_vector_type(W)));
+  const int cw = c / W;
   GRID_STRIDE_XCD(i, total) {  // total < 2^31 (host)
-    const uint32_t q = fdiv((uint32_t)i, f_cv), r = fdiv(q, f_wi);
-    const int ch = ((int)((uint32_t)i - q * cv)) * V, iw = (int)(q - r * wi);
+    const uint32_t q = fdiv((uint32_t)i, f_cw), r = fdiv(q, f_wi);
+    const int ch = ((int)((uint32_t)i - q * cw)) * W, iw = (int)(q - r * wi);
     const uint32_t img = fdiv(r, f_hi);
     const int ih = (int)(r - img * hi);
-    const float* wx = wtab + iw * maxw;
-    const float* wy = htab + ih * maxh;
-    const T* base = dy + ((long)img * ho + hlo[ih]) * wo * dyld + (long)wlo[iw] * dyld + dyoff + ch;
-    const int jx0 = wspan[iw] & 0xffff, jx1 = wspan[iw] >> 16;
-    const int ky0 = hspan[ih] & 0xffff, ky1 = hspan[ih] >> 16;
-    float acc[V];
+    const float* wx = tb.wtab + iw * maxw;
+    const float* wy = tb.htab + ih * maxh;
+    const T* base = dy + (((long)img * ho + tb.hlo[ih]) * wo + tb.wlo[iw]) * dyld + dyoff + ch;
+    const int jx0 = tb.wspan[iw] & 0xffff, jx1 = tb.wspan[iw] >> 16;
+    const int ky0 = tb.hspan[ih] & 0xffff, ky1 = tb.hspan[ih] >> 16;
+    float acc[W];
 #pragma unroll
-    for (int e = 0; e < V; ++e) acc[e] = 0.f;
+    for (int e = 0; e < W; ++e) acc[e] = 0.f;
     for (int k = ky0; k < ky1; ++k) {
       const float yk = wy[k];
       if (yk == 0.f) continue;
       const T* row = base + (long)k * wo * dyld;
-      float t[V];
+      float t[W];
 #pragma unroll
-      for (int e = 0; e < V; ++e) t[e] = 0.f;
+      for (int e = 0; e < W; ++e) t[e] = 0.f;
       for (int j0 = jx0; j0 < jx1; j0 += G) {
-        V16 v[G];
+        VW v[G];
         float xw[G];
 #pragma unroll
         for (int u = 0; u < G; ++u) {
           const int j = j0 + u;
           xw[u] = j < jx1 ? wx[j] : 0.f;
-          v[u] = *(const V16*)(row + (long)min(j, jx1 - 1) * dyld);
+          v[u] = *(const VW*)(row + (long)min(j, jx1 - 1) * dyld);
         }
 #pragma unroll
         for (int u = 0; u < G; ++u)
 #pragma unroll
-          for (int e = 0; e < V; ++e) t[e] = xw[u] != 0.f ? fmaf(xw[u], to_f(v[u][e]), t[e]) : t[e];
+          for (int e = 0; e < W; ++e) t[e] = xw[u] != 0.f ? fmaf(xw[u], to_f(v[u][e]), t[e]) : t[e];
       }
 #pragma unroll
-      for (int e = 0; e < V; ++e) acc[e] = fmaf(yk, t[e], acc[e]);
+      for (int e = 0; e < W; ++e) acc[e] = fmaf(yk, t[e], acc[e]);
     }
-    V16 o;
+    VW o;
 #pragma unroll
-    for (int e = 0; e < V; ++e) o[e] = from_f<T>(acc[e]);
-    *(V16*)(dx + (((long)img * hi + ih) * wi + iw) * c + ch) = o;
+    for (int e = 0; e < W; ++e) o[e] = from_f<T>(acc[e]);
+    *(VW*)(dx + i * W) = o;  // i = ((img * hi + ih) * wi + iw) * cw + ch / W
   }
 }
-// The same one-pass form for channel counts off the vector width (the supervision heads'
-// 19-class logits): a thread per (input pixel, channel), dY dense (pitch c).  Adjacent lanes
-// read adjacent channels, so each tap's loads stay contiguous across the wave.
-template <typename T, int G>
-__global__ void __launch_bounds__(256) bilinear_bwd_fused_kernel(const T* __restrict__ dy, T* __restrict__ dx, int hi, int wi, int c,
-                                                                 int ho, int wo, float sh, float sw, int maxh, int maxw, long total,
-                                                                 FastDiv f_c, FastDiv f_wi, FastDiv f_hi) {
-  extern __shared__ float tab[];
-  float* wtab = tab;
-  int* wlo = (int*)(wtab + wi * maxw);
-  float* htab = (float*)(wlo + wi);
-  int* hlo = (int*)(htab + hi * maxh);
-  int* wspan = hlo + hi;
-  int* hspan = wspan + wi;
-  bil_table_build(wtab, wlo, wi, wo, sw, maxw);
-  bil_table_build(htab, hlo, hi, ho, sh, maxh);
-  bil_table_span(wtab, wspan, wi, maxw);
-  bil_table_span(htab, hspan, hi, maxh);
-  GRID_STRIDE_XCD(i, total) {  // total < 2^31 (host)
-    const uint32_t q = fdiv((uint32_t)i, f_c), r = fdiv(q, f_wi);
-    const int ch = (int)((uint32_t)i - q * c), iw = (int)(q - r * wi);
-    const uint32_t img = fdiv(r, f_hi);
-    const int ih = (int)(r - img * hi);
-    const float* wx = wtab + iw * maxw;
-    const float* wy = htab + ih * maxh;
-    const T* base = dy + (((long)img * ho + hlo[ih]) * wo + wlo[iw]) * c + ch;
-    const int jx0 = wspan[iw] & 0xffff, jx1 = wspan[iw] >> 16;
-    const int ky0 = hspan[ih] & 0xffff, ky1 = hspan[ih] >> 16;
-    float acc = 0.f;
-    for (int k = ky0; k < ky1; ++k) {
-      const float yk = wy[k];
-      if (yk == 0.f) continue;
-      const T* row = base + (long)k * wo * c;
-      float t = 0.f;
-      for (int j0 = jx0; j0 < jx1; j0 += G) {
-        T v[G];
-        float xw[G];
-#pragma unroll
-        for (int u = 0; u < G; ++u) {
-          const int j = j0 + u;
-          xw[u] = j < jx1 ? wx[j] : 0.f;
-          v[u] = row[(long)min(j, jx1 - 1) * c];
-        }
-#pragma unroll
-        for (int u = 0; u < G; ++u) t = xw[u] != 0.f ? fmaf(xw[u], to_f(v[u]), t) : t;
-      }
-      acc = fmaf(yk, t, acc);
-    }
-    dx[i] = from_f<T>(acc);
-  }
-}
-// most outputs any input index of an axis receives from (bil_wsum_range, host float math)
-static int bil_maxw(int in, int out, float s) {
-  int m = 0;
-  for (int i = 0; i < in; ++i) {
-    int lo = (int)std::floor(((float)i - 0.5f) / s - 0.5f) - 1;
-    int hi = (int)std::ceil(((float)i + 1.5f) / s - 0.5f) + 1;
-    lo = std::max(lo, 0);
-    hi = std::min(hi, out - 1);
-    m = std::max(m, hi - lo + 1);
-  }
-  return m + 1;  // margin for the device's own rounding of the same range (zero entries)
-}
-static size_t bil_tab_bytes(int in, int maxw) { return ((size_t)in * maxw + in) * 4; }
-// launch both passes table-driven when the tables fit and the index math fits 32 bits, else the
-// per-element kernels; w pass reads dy with row pitch dyld at channel offset dyoff
+// one kernel for both passes when its tables fit and the index math fits 32 bits, else the two
+// passes; dy is read with row pitch dyld at channel offset dyoff
 template <typename T>
 static void bilinear_bwd_launch(const T* dy, float* tmp, T* dx, int n, int hi, int wi, int c, int ho, int wo, float sh, float sw,
                                 int dyld, int dyoff, hipStream_t st) {
   const long tw = (long)n * ho * wi * c, th = (long)n * hi * wi * c;
   const int mw = bil_maxw(wi, wo, sw), mh = bil_maxw(hi, ho, sh);
-  const size_t bw = bil_tab_bytes(wi, mw), bh = bil_tab_bytes(hi, mh);
+  const size_t bw = bil_tab_bytes(wi, mw), fused = BilTables::bytes(hi, wi, mh, mw);
   constexpr int V = VecT<T>::N;
-  if (c % V == 0 && dyld % V == 0 && dyoff % V == 0 && th < (1L << 31) && bw + bh + (wi + hi) * 4 <= (size_t)kBilTabLds &&
-      (long)n * ho * wo * dyld < (1L << 40)) {
-    const long tv = th / V;
+  const bool vec = c % V == 0 && dyld % V == 0 && dyoff % V == 0, scalar = c % V != 0 && dyld == c && dyoff == 0;
+  if ((vec || scalar) && th < (1L << 31) && fused <= (size_t)kBilTabLds && (long)n * ho * wo * dyld < (1L << 40)) {
     // taps per load batch: 8 when an input column reaches ~8 output columns (x4), else 4 (x2)
-    auto kern = mw >= 10 ? bilinear_bwd_fused_vec_kernel<T, 8> : bilinear_bwd_fused_vec_kernel<T, 4>;
-    hipLaunchKernelGGL(kern, dim3(ew_blocks(tv)), dim3(256), bw + bh + (wi + hi) * 4, st, dy, dx, hi, wi, c, ho, wo, sh, sw, dyld,
-                       dyoff, mh, mw, tv, fastdiv_make(c / V), fastdiv_make(wi), fastdiv_make(hi));
+    with_bool(vec, [&](auto v) {
+      with_bool(mw >= 10, [&](auto g8) {
+        constexpr int W = decltype(v)::value ? V : 1, G = decltype(g8)::value ? 8 : 4;
+        hipLaunchKernelGGL((bilinear_bwd_fused_kernel<T, W, G>), dim3(ew_blocks(th / W)), dim3(256), fused, st, dy, dx, hi, wi, c,
+                           ho, wo, sh, sw, dyld, dyoff, mh, mw, th / W, fastdiv_make(c / W), fastdiv_make(wi), fastdiv_make(hi));
+      });
+    });
     return;
   }
-  if (c % V != 0 && dyld == c && dyoff == 0 && th < (1L << 31) && bw + bh + (wi + hi) * 4 <= (size_t)kBilTabLds &&
-      (long)n * ho * wo * c < (1L << 40)) {
-    auto kern = mw >= 10 ? bilinear_bwd_fused_kernel<T, 8> : bilinear_bwd_fused_kernel<T, 4>;
-    hipLaunchKernelGGL(kern, dim3(ew_blocks(th)), dim3(256), bw + bh + (wi + hi) * 4, st, dy, dx, hi, wi, c, ho, wo, sh, sw, mh, mw,
-                       th, fastdiv_make(c), fastdiv_make(wi), fastdiv_make(hi));
-    return;
-  }
-  if (tw < (1L << 31) && bw <= (size_t)kBilTabLds)
-    hipLaunchKernelGGL(bilinear_bwd_w_tab_kernel<T>, dim3(ew_blocks(tw)), dim3(256), bw, st, dy, tmp, n, wi, c, ho, wo, sw, dyld,
-                       dyoff, mw, fastdiv_make(c), fastdiv_make(wi));
-  else
-    hipLaunchKernelGGL(bilinear_bwd_w_kernel<T>, dim3(ew_blocks(tw)), dim3(256), 0, st, dy, tmp, n, wi, c, ho, wo, sw, dyld, dyoff);
-  if (th < (1L << 31) && bh <= (size_t)kBilTabLds)
-    hipLaunchKernelGGL(bilinear_bwd_h_tab_kernel<T>, dim3(ew_blocks(th)), dim3(256), bh, st, (const float*)tmp, dx, n, hi, wi, c, ho,
-                       sh, mh, fastdiv_make((uint32_t)wi * c), fastdiv_make(hi));
-  else
-    hipLaunchKernelGGL(bilinear_bwd_h_kernel<T>, dim3(ew_blocks(th)), dim3(256), 0, st, (const float*)tmp, dx, n, hi, wi, c, ho, sh);
+  with_bool(tw < (1L << 31) && bw <= (size_t)kBilTabLds, [&](auto tab) {
+    constexpr bool TAB = decltype(tab)::value;
+    hipLaunchKernelGGL((bilinear_bwd_w_kernel<T, TAB>), dim3(ew_blocks(tw)), dim3(256), TAB ? bw : 0, st, dy, tmp, n, wi, c, ho, wo, sw,
+                       dyld, dyoff, mw, fastdiv_make(c), fastdiv_make(wi));
+  });
+  bil_bwd_h_launch(tmp, dx, n, hi, wi, c, ho, sh, st);
+}
+template <typename T>
+static void bil_group_vec_launch(const void* x, void* y, int n, int hi, int wi, int c, int ho, int wo, float sh, float sw, int y_ld,
+                                 int y_off, const void* s1, const void* s2, hipStream_t st) {
+  hipLaunchKernelGGL((bilinear_fwd_group_vec_kernel<T, kBilGroupU>), dim3(rt_cdiv(wo * (c / VecT<T>::N), 256 * kBilGroupU), n * hi),
+                     dim3(256), 0, st, (const T*)x, (T*)y, n, hi, wi, c, ho, wo, sh, sw, y_ld, y_off, (const T*)s1, (const T*)s2);
 }
 extern "C" int rtsds_bilinear_fwd(const void* x, void* y, int n, int hi, int wi, int c, int ho, int wo, float scale_h, float scale_w,
                                   int y_ld, int y_off, int dtype, void* stream) {
@@ -544,12 +512,11 @@ extern "C" int rtsds_bilinear_fwd(const void* x, void* y, int n, int hi, int wi,
     const long pix = (long)n * ho * wo;
     // grouped taps pay off from ~3 output rows per source row (x2: 24 vs 17 us at 256 ch, x4:
     // 26 vs 28 us, tools/ab_bilinear.sh)
-    if (c % V == 0 && y_ld % V == 0 && y_off % V == 0 && ho >= 3 * hi && kBilRowGroup)
-      hipLaunchKernelGGL((bilinear_fwd_group_vec_kernel<T, kBilGroupU>), dim3(rt_cdiv(wo * (c / V), 256 * kBilGroupU), n * hi),
-                         dim3(256), 0, st, (const T*)x, (T*)y, n, hi, wi, c, ho, wo, scale_h, scale_w, y_ld, y_off, nullptr, nullptr);
+    if (c % V == 0 && y_ld % V == 0 && y_off % V == 0 && ho >= 3 * hi)
+      bil_group_vec_launch<T>(x, y, n, hi, wi, c, ho, wo, scale_h, scale_w, y_ld, y_off, nullptr, nullptr, st);
     else if (c % V == 0 && y_ld % V == 0 && y_off % V == 0)
       hipLaunchKernelGGL((bilinear_fwd_kernel<T, 0>), dim3(ew_blocks(pix * (c / V))), dim3(256), 0, st, (const T*)x, (T*)y, n, hi, wi, c, ho, wo, scale_h, scale_w, y_ld, y_off);
-    else if (c >= V && y_ld == c && y_off == 0 && (wo * c) % V == 0 && 2L * wi * c * 4 <= 64 * 1024 && ho >= hi && kBilRowGroup) {
+    else if (c >= V && y_ld == c && y_off == 0 && (wo * c) % V == 0 && 2L * wi * c * 4 <= 64 * 1024 && ho >= hi) {
       // column chunks: <= 256 * kJ vectors each, and enough workgroups to fill the chip
       constexpr int kJ = kBilJ;
       const int nv = wo * c / V;
@@ -577,9 +544,7 @@ extern "C" int rtsds_bilinear_fwd_scaled(const void* x, const void* s1, const vo
   DISPATCH_T(dtype, {
     constexpr int V = VecT<T>::N;
     if (!(c % V == 0 && y_ld % V == 0 && y_off % V == 0 && ho >= hi)) return RTSDS_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((bilinear_fwd_group_vec_kernel<T, kBilGroupU>), dim3(rt_cdiv(wo * (c / V), 256 * kBilGroupU), n * hi),
-                       dim3(256), 0, st, (const T*)x, (T*)y, n, hi, wi, c, ho, wo, scale_h, scale_w, y_ld, y_off, (const T*)s1,
-                       (const T*)s2);
+    bil_group_vec_launch<T>(x, y, n, hi, wi, c, ho, wo, scale_h, scale_w, y_ld, y_off, s1, s2, st);
   });
   RET_LAUNCH();
 }
@@ -613,10 +578,10 @@ extern "C" int rtsds_bilinear_bwd(const void* dy, void* dx, int n, int hi, int w
 //   backward: one block per (row, tile of up to 64 input columns): the dy segment the tile's
 //             width adjoint reads is staged in LDS (coalesced), then thread per output pixel
 //             forms the softmax backward T(p_k (dp_k - sum_j p_j dp_j)) in place (its p row by
-//             16-B loads); the tile's bilinear
-//             weights are tabulated once in LDS; thread per (input column, class) accumulates
-//             the width adjoint in bilinear_bwd_w_kernel's order (ascending output column,
-//             zero weights skipped).  The vertical pass is bilinear_bwd_h_kernel.
+//             16-B loads); the tile's bilinear weights are tabulated once in LDS
+//             (bil_table_build); thread per (input column, class) accumulates the width adjoint
+//             with bil_gather, as bilinear_bwd_w_kernel does.  The vertical pass is
+//             bil_bwd_h_launch.
 static const int kUpsmMaxC = 32;
 static const int kUpsmPix = 256;
 static const int kUpsmLds = 48 * 1024;
@@ -653,10 +618,7 @@ RT_DEV UpsmTile<T> upsm_tile(const T* __restrict__ x, float* src, int hi, int wi
     bil_src(t.ow0 + t.np - 1, sw, wi, b0, b1, t0, t1);
     t.wlo = a0;
     t.n1 = (b1 - a0 + 1) * c;
-    for (int e = threadIdx.x; e < t.n1; e += 256) {
-      src[e] = to_f(t.r0[(long)t.wlo * c + e]);
-      src[t.n1 + e] = to_f(t.r1[(long)t.wlo * c + e]);
-    }
+    bil_stage_rows(t.r0 + (long)t.wlo * c, t.r1 + (long)t.wlo * c, src, t.n1);
   }
   return t;
 }
@@ -818,13 +780,6 @@ __global__ void __launch_bounds__(256) upsoftmax_acc_kernel(const T* __restrict_
   __syncthreads();  // every lane reaches the same barrier (no early exit)
   upsm_tile_copy<false>(dst, tbuf, nel, head);
 }
-// exact output-pixel span [lo, hi] read by input columns [iw0, iw1] (bil_wsum_range bounds)
-__host__ __device__ inline void upsm_span(int iw0, int iw1, float sw, int wi, int wo, int& lo, int& hi) {
-  lo = (int)floorf(((float)iw0 - 0.5f) / sw - 0.5f) - 1;
-  hi = (int)ceilf(((float)iw1 + 1.5f) / sw - 0.5f) + 1;
-  lo = lo < 0 ? 0 : lo;
-  hi = hi > wo - 1 ? wo - 1 : hi;
-}
 template <typename T, int CC>  // CC > 0: compile-time class count (19), 0: runtime c
 __global__ void __launch_bounds__(256) upsoftmax_bwd_w_kernel(const T* __restrict__ dy, int dyld, const T* __restrict__ y,
                                                               int yld, float* __restrict__ tmp, int wi, int c_, int wo, float sw,
@@ -839,7 +794,7 @@ __global__ void __launch_bounds__(256) upsoftmax_bwd_w_kernel(const T* __restric
   const long row = blockIdx.x / tiles;  // img * ho + oh
   const int iw0 = tile * tw, iw1 = min(wi, iw0 + tw) - 1, nw = iw1 - iw0 + 1;
   int olo, ohi;
-  upsm_span(iw0, iw1, sw, wi, wo, olo, ohi);
+  bil_adj_range(iw0, iw1, sw, wo, olo, ohi);
   const int cnt = ohi - olo + 1;  // <= cap (host: exact maximum over the tiles)
   // dy segment -> LDS as T, coalesced (rows of pitch c; contiguous in memory when dyld == c)
   const T* gseg = dy + (row * wo + olo) * dyld;
@@ -883,24 +838,11 @@ __global__ void __launch_bounds__(256) upsoftmax_bwd_w_kernel(const T* __restric
     for (int k = 0; k < kUpsmMaxC; ++k)
       if (k < c) g[k] = from_f<T>(pv[k] * (gv[k] - dot));
   }
-  for (int e = tid; e < nw * maxw; e += 256) {
-    const int il = e / maxw, j = e - il * maxw, iw = iw0 + il;
-    int lo, hi;
-    bil_wsum_range(iw, sw, wi, wo, lo, hi);
-    wt[e] = lo + j <= hi ? bil_weight(lo + j, iw, sw, wi) : 0.f;
-    if (j == 0) wlo[il] = lo - olo;
-  }
-  __syncthreads();
+  bil_table_build(wt, wlo, iw0, nw, wi, wo, sw, maxw, olo);  // wlo: relative to the staged segment
   for (int e = tid; e < nw * c; e += 256) {  // (input column, class) items, classes inner
     const int il = e / c, k = e - il * c;
     const float* w = wt + il * maxw;
-    const T* s = sgt + wlo[il] * c + k;
-    float acc = 0.f;
-    for (int j = 0; j < maxw; ++j) {
-      const float wv = w[j];
-      if (wv != 0.f) acc = fmaf(wv, to_f(s[j * c]), acc);
-    }
-    tmp[(row * wi + iw0) * c + e] = acc;
+    tmp[(row * wi + iw0) * c + e] = bil_gather(sgt + wlo[il] * c + k, c, maxw, [&](int j) { return w[j]; });
   }
 }
 // columns of the low-res rows one forward tile stages (taps monotone in ow)
@@ -917,56 +859,63 @@ static int upsm_fwd_cols(int wi, int wo, float sw) {
   }
   return cols + 2;  // margin: the device computes the tap columns with its own float rounding
 }
+// shape guard and sizing of the forward tiles (upsoftmax_fwd / upsoftmax_acc): tiles per row, grid,
+// bytes of one tile's staged taps
+struct UpsmPlan {
+  int tiles;
+  unsigned blocks;
+  size_t taps;
+};
+static int upsm_plan(int n, int hi, int wi, int c, int ho, int wo, float sw, UpsmPlan& p) {
+  if (n <= 0 || ho <= 0 || wo <= 0 || hi <= 0 || wi <= 0 || c <= 0 || c > kUpsmMaxC) return RTSDS_ERR_SHAPE;
+  p.tiles = rt_cdiv(wo, kUpsmPix);
+  const long blocks = (long)n * ho * p.tiles;
+  if (blocks > INT_MAX) return RTSDS_ERR_UNSUPPORTED;
+  p.blocks = (unsigned)blocks;
+  p.taps = (size_t)2 * upsm_fwd_cols(wi, wo, sw) * c * sizeof(float);
+  return RTSDS_OK;
+}
+// f(CC): the compile-time class count 19, else 0 (runtime c); f(STAGED, CC) for the forward tiles,
+// whose unstaged form has the runtime count only
+template <typename F>
+static void upsm_with_cc(int c, F f) {
+  if (c == 19) f(std::integral_constant<int, 19>());
+  else f(std::integral_constant<int, 0>());
+}
+template <typename F>
+static void upsm_dispatch(bool staged, int c, F f) {
+  if (staged) upsm_with_cc(c, [&](auto cc) { f(std::true_type(), cc); });
+  else f(std::false_type(), std::integral_constant<int, 0>());
+}
 extern "C" int rtsds_upsoftmax_fwd(const void* x, void* y, int n, int hi, int wi, int c, int ho, int wo, float scale_h,
                                    float scale_w, int y_ld, int dtype, void* stream) {
-  if (n <= 0 || ho <= 0 || wo <= 0 || hi <= 0 || wi <= 0 || c <= 0 || c > kUpsmMaxC || y_ld < c || y_ld > kUpsmMaxC)
-    return RTSDS_ERR_SHAPE;
-  const int tiles = rt_cdiv(wo, kUpsmPix);
-  const long blocks = (long)n * ho * tiles;
-  if (blocks > INT_MAX) return RTSDS_ERR_UNSUPPORTED;
-  const size_t taps = (size_t)2 * upsm_fwd_cols(wi, wo, scale_w) * c * sizeof(float);
-  const bool staged = taps <= (size_t)kUpsmLds;
+  if (y_ld < c || y_ld > kUpsmMaxC) return RTSDS_ERR_SHAPE;
+  UpsmPlan p;
+  if (const int rc = upsm_plan(n, hi, wi, c, ho, wo, scale_w, p)) return rc;
+  const bool staged = p.taps <= (size_t)kUpsmLds;
   const size_t outb = (size_t)kUpsmPix * y_ld * (dtype == RTSDS_BF16 ? 2 : 4);
-  const size_t lds = (staged ? taps + 16 : 0) + outb;
+  const size_t lds = (staged ? p.taps + 16 : 0) + outb;
   hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, {
-    if (staged && c == 19)
-      hipLaunchKernelGGL((upsoftmax_fwd_kernel<T, true, 19>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)x, (T*)y, hi,
-                         wi, c, ho, wo, scale_h, scale_w, y_ld, tiles);
-    else if (staged)
-      hipLaunchKernelGGL((upsoftmax_fwd_kernel<T, true, 0>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)x, (T*)y, hi,
-                         wi, c, ho, wo, scale_h, scale_w, y_ld, tiles);
-    else
-      hipLaunchKernelGGL((upsoftmax_fwd_kernel<T, false, 0>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)x, (T*)y, hi,
-                         wi, c, ho, wo, scale_h, scale_w, y_ld, tiles);
-  });
+  DISPATCH_T(dtype, upsm_dispatch(staged, c, [&](auto s, auto cc) {
+    hipLaunchKernelGGL((upsoftmax_fwd_kernel<T, decltype(s)::value, decltype(cc)::value>), dim3(p.blocks), dim3(256), lds, st,
+                       (const T*)x, (T*)y, hi, wi, c, ho, wo, scale_h, scale_w, y_ld, p.tiles);
+  }));
   RET_LAUNCH();
 }
 extern "C" int rtsds_upsoftmax_acc(const void* x, float* acc, int64_t* pred, int n, int hi, int wi, int c, int ho, int wo,
                                    float scale_h, float scale_w, int flip, int accumulate, int dtype, void* stream) {
-  if (n <= 0 || ho <= 0 || wo <= 0 || hi <= 0 || wi <= 0 || c <= 0 || c > kUpsmMaxC) return RTSDS_ERR_SHAPE;
-  if (dtype != RTSDS_F32 && dtype != RTSDS_BF16) return RTSDS_ERR_UNSUPPORTED;
+  UpsmPlan p;
+  if (const int rc = upsm_plan(n, hi, wi, c, ho, wo, scale_w, p)) return rc;
   if (x == nullptr || acc == nullptr || ((uintptr_t)acc & 3)) return RTSDS_ERR_UNSUPPORTED;
-  const int tiles = rt_cdiv(wo, kUpsmPix);
-  const long blocks = (long)n * ho * tiles;
-  if (blocks > INT_MAX) return RTSDS_ERR_UNSUPPORTED;
-  const size_t taps = (size_t)2 * upsm_fwd_cols(wi, wo, scale_w) * c * sizeof(float);
   // the fp32 tile + up to 3 floats of phase behind the (16-B rounded) staged rows
   const size_t tileb = 16 + (size_t)kUpsmPix * c * sizeof(float);
-  const bool staged = taps + 16 + tileb <= (size_t)64 * 1024;
-  const size_t lds = (staged ? taps + 16 : 0) + tileb;
+  const bool staged = p.taps + 16 + tileb <= (size_t)64 * 1024;
+  const size_t lds = (staged ? p.taps + 16 : 0) + tileb;
   hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, {
-    if (staged && c == 19)
-      hipLaunchKernelGGL((upsoftmax_acc_kernel<T, true, 19>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)x, acc, pred,
-                         hi, wi, c, ho, wo, scale_h, scale_w, flip, accumulate, tiles);
-    else if (staged)
-      hipLaunchKernelGGL((upsoftmax_acc_kernel<T, true, 0>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)x, acc, pred,
-                         hi, wi, c, ho, wo, scale_h, scale_w, flip, accumulate, tiles);
-    else
-      hipLaunchKernelGGL((upsoftmax_acc_kernel<T, false, 0>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)x, acc, pred,
-                         hi, wi, c, ho, wo, scale_h, scale_w, flip, accumulate, tiles);
-  });
+  DISPATCH_T(dtype, upsm_dispatch(staged, c, [&](auto s, auto cc) {
+    hipLaunchKernelGGL((upsoftmax_acc_kernel<T, decltype(s)::value, decltype(cc)::value>), dim3(p.blocks), dim3(256), lds, st,
+                       (const T*)x, acc, pred, hi, wi, c, ho, wo, scale_h, scale_w, flip, accumulate, p.tiles);
+  }));
   RET_LAUNCH();
 }
 extern "C" size_t rtsds_upsoftmax_bwd_workspace(int n, int hi, int wi, int c, int ho, int wo) {
@@ -978,14 +927,14 @@ static bool upsm_tiling(int wi, int wo, int c, float sw, size_t esz, int& tw, in
   maxw = 0;
   for (int iw = 0; iw < wi; ++iw) {
     int lo, hi;
-    upsm_span(iw, iw, sw, wi, wo, lo, hi);
+    bil_adj_range(iw, iw, sw, wo, lo, hi);
     maxw = std::max(maxw, hi - lo + 1);
   }
   for (tw = 64; tw >= 1; tw /= 2) {
     cap = 0;
     for (int iw0 = 0; iw0 < wi; iw0 += tw) {
       int lo, hi;
-      upsm_span(iw0, std::min(wi, iw0 + tw) - 1, sw, wi, wo, lo, hi);
+      bil_adj_range(iw0, std::min(wi, iw0 + tw) - 1, sw, wo, lo, hi);
       cap = std::max(cap, hi - lo + 1);
     }
     if ((size_t)cap * c * esz + (size_t)tw * (maxw + 1) * 4 <= (size_t)kUpsmLds) return true;
@@ -1007,20 +956,11 @@ extern "C" int rtsds_upsoftmax_bwd(const void* dy, int dy_ld, const void* y, int
     const long blocks = (long)n * ho * tiles;
     if (blocks > INT_MAX) return RTSDS_ERR_UNSUPPORTED;
     const size_t lds = (size_t)tw * (maxw + 1) * 4 + (size_t)cap * c * sizeof(T);
-    if (c == 19)
-      hipLaunchKernelGGL((upsoftmax_bwd_w_kernel<T, 19>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)dy, dy_ld,
-                         (const T*)y, y_ld, tmp, wi, c, wo, scale_w, tw, tiles, cap, maxw);
-    else
-      hipLaunchKernelGGL((upsoftmax_bwd_w_kernel<T, 0>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)dy, dy_ld,
-                         (const T*)y, y_ld, tmp, wi, c, wo, scale_w, tw, tiles, cap, maxw);
-    const int mh = bil_maxw(hi, ho, scale_h);
-    const size_t bh = bil_tab_bytes(hi, mh);
-    if (total < (1L << 31) && bh <= (size_t)kBilTabLds)
-      hipLaunchKernelGGL(bilinear_bwd_h_tab_kernel<T>, dim3(ew_blocks(total)), dim3(256), bh, st, (const float*)tmp, (T*)dx, n,
-                         hi, wi, c, ho, scale_h, mh, fastdiv_make((uint32_t)wi * c), fastdiv_make(hi));
-    else
-      hipLaunchKernelGGL(bilinear_bwd_h_kernel<T>, dim3(ew_blocks(total)), dim3(256), 0, st, (const float*)tmp, (T*)dx, n, hi,
-                         wi, c, ho, scale_h);
+    upsm_with_cc(c, [&](auto cc) {
+      hipLaunchKernelGGL((upsoftmax_bwd_w_kernel<T, decltype(cc)::value>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)dy,
+                         dy_ld, (const T*)y, y_ld, tmp, wi, c, wo, scale_w, tw, tiles, cap, maxw);
+    });
+    bil_bwd_h_launch(tmp, (T*)dx, n, hi, wi, c, ho, scale_h, st);
   });
   RET_LAUNCH();
 }

@@ -47,5 +47,23 @@ for c, hi, wi in ((256, 32, 64), (512, 16, 32)):
         out[f"{dt}_{c}"] = y.cpu()
         x2 = torch.randn(2, c, 13, 17, generator=g).to(dev, dt).contiguous(memory_format=torch.channels_last)
         out[f"{dt}_{c}_ragged"] = F.interpolate_geometry(x2, F.upsample_geometry(x2, size=(50, 61))).cpu()
+# the backward at the supervision-head shape (19 classes, scalar one-pass kernel) and at the
+# context-path shape (256 channels, vector one-pass kernel)
+for c, hi, wi, ho, wo in ((19, 64, 128, 512, 1024), (256, 32, 64, 64, 128)):
+    dt = torch.bfloat16
+    x = torch.zeros(8, c, hi, wi, device=dev, dtype=dt).contiguous(memory_format=torch.channels_last)
+    geo = F.upsample_geometry(x, size=(ho, wo))
+    dy = torch.randn(8, c, ho, wo, generator=g).to(dev, dt).contiguous(memory_format=torch.channels_last)
+    ctx = type("Ctx", (), {"geo": (8, hi, wi, c, *geo)})
+    dx = F.BilinearFn.backward(ctx, dy)[0]
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(50):
+        F.BilinearFn.backward(ctx, dy)
+    e1.record()
+    torch.cuda.synchronize()
+    print(f"{str(dt):16s} backward {c}ch {hi}x{wi} <- {ho}x{wo} bs8: {e0.elapsed_time(e1) / 50 * 1e3:.1f} us")
+    out[f"{dt}_{c}_bwd"] = dx.cpu()
 if len(sys.argv) > 1:
     torch.save(out, sys.argv[1])

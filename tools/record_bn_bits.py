@@ -1,45 +1,7 @@
-"""Records tests/pinned/bn_bits.json: one SHA-256 per output tensor per case of
-tests/bn_bits_cases.py, from the library this checkout built (or RTSDS_LIB).
-
-    python tools/record_bn_bits.py [--check] [--out FILE]
-
-The file is recorded on the parent of a commit that means to change BatchNorm's arithmetic --
-first with --check (compares, writes nothing) to show that the committed file was still green
-there -- never from the code under test.
-"""
-import argparse
-import json
-import os
+"""tools/record_bits.py bn [--check] [--out FILE]."""
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from tests.bn_bits_cases import CASES, IDS, run_case  # noqa: E402
-
-PINNED = os.path.join(ROOT, "tests", "pinned", "bn_bits.json")
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--check", action="store_true", help="compare with the recorded file instead of writing it")
-    ap.add_argument("--out", default=PINNED)
-    args = ap.parse_args()
-    got = {i: run_case(c) for i, c in zip(IDS, CASES)}
-    if args.check:
-        with open(args.out) as f:
-            want = json.load(f)
-        bad = sorted(i for i in set(got) | set(want) if got.get(i) != want.get(i))
-        for i in bad:
-            print("differs:", i)
-        print(f"{len(got) - len(bad)} of {len(got)} cases match {args.out}")
-        return 1 if bad else 0
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(got, f, indent=1, sort_keys=True)
-        f.write("\n")
-    print(f"recorded {len(got)} cases, {sum(len(v) for v in got.values())} digests -> {args.out}")
-    return 0
-
+from record_bits import main
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(main("bn"))
