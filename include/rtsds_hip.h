@@ -501,6 +501,18 @@ int rtsds_classmix(const void* src, const int64_t* slab, const void* tgt, const 
  *   Normalize on the 0-255 scale), 2: int64 label (round half-to-even, clamp to
  *   [clamp_lo, clamp_hi] when clamp_lo <= clamp_hi: IntRangeTransformer).  src_u8 selects a
  *   uint8 (else fp32) source.  dst is the image's slot in an NHWC batch.
+ * rtsds_crop_resize_aa: rtsds_resize_aa of the window src[y0 : y0 + hc, x0 : x0 + wc, :] of the
+ *   [h][w][c] image, read in place (RandomResizedCrop ahead of the Resize; flip mirrors inside
+ *   the window).  Bit-identical to rtsds_resize_aa on a contiguous copy of the window; the
+ *   workspace is rtsds_resize_aa_workspace(c, hc, wc, ho, wo).
+ * rtsds_crop_resize_nearest: the same window of a [h][w] label (uint8, or int64 when src_i64)
+ *   resampled to int64 [ho][wo] with F.interpolate(mode="nearest")'s index rule
+ *   (min((int)floorf(o * ((float)in / (float)out)), in - 1)); flip != 0 writes the horizontal
+ *   mirror of that result (interpolate, then flip); clamped to [clamp_lo, clamp_hi] when
+ *   clamp_lo <= clamp_hi.
+ *   Both: RTSDS_ERR_SHAPE for a NULL pointer, a non-positive size, a window not inside
+ *   [0, h) x [0, w) or mean / std given singly; RTSDS_ERR_UNSUPPORTED / RTSDS_ERR_WORKSPACE as
+ *   rtsds_resize_aa on the window; all before any launch.
  * rtsds_gaussian_blur: GaussianBlur((kx, ky), sigma) of a HWC image (uint8 or fp32 source),
  *   fp32 HWC out, reflect padding.
  * rtsds_gta5_decode: RGB label (HWC uint8) -> train id 0..18 (unmatched colours -> 0).
@@ -518,6 +530,11 @@ size_t rtsds_resize_aa_workspace(int c, int h, int w, int ho, int wo);
 int rtsds_resize_aa(const void* src, int src_u8, int c, int h, int w, void* dst, int kind, int ho, int wo,
                     int flip, const float* mean, const float* std, int clamp_lo, int clamp_hi, void* ws,
                     size_t ws_bytes, void* stream);
+int rtsds_crop_resize_aa(const void* src, int src_u8, int c, int h, int w, int y0, int x0, int hc, int wc,
+                         void* dst, int kind, int ho, int wo, int flip, const float* mean, const float* std,
+                         int clamp_lo, int clamp_hi, void* ws, size_t ws_bytes, void* stream);
+int rtsds_crop_resize_nearest(const void* src, int src_i64, int h, int w, int y0, int x0, int hc, int wc,
+                              int64_t* dst, int ho, int wo, int flip, int clamp_lo, int clamp_hi, void* stream);
 int rtsds_gaussian_blur(const void* src, int src_u8, float* dst, int c, int h, int w, int kx, int ky,
                         float sigma_x, float sigma_y, void* stream);
 int rtsds_gta5_decode(const uint8_t* rgb, int64_t* out, int h, int w, void* stream);
@@ -568,7 +585,7 @@ int rtsds_pooled_mlp_fwd(const void* p, const void* w1, const float* b1, const v
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 14
+#define RTSDS_ABI_VERSION 15
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSDS_LIB: alternative in-tree build of the same ABI (kernel-variant A/B measurements)
 DEFAULT_LIB_PATH = os.path.join(_HERE, "librtsds_hip.so")
-ABI_VERSION = 14  # include/rtsds_hip.h RTSDS_ABI_VERSION
+ABI_VERSION = 15  # include/rtsds_hip.h RTSDS_ABI_VERSION
 LIB_PATH = os.environ.get("RTSDS_LIB") or DEFAULT_LIB_PATH
 
 F32, BF16 = 0, 1
@@ -130,6 +130,9 @@ SIGNATURES = {
     "rtsds_resize_aa_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rtsds_resize_aa": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, c_int, c_int,
                                 P, c_size_t, P]),
+    "rtsds_crop_resize_aa": (c_int, [P] + [c_int] * 8 + [P, c_int, c_int, c_int, c_int, P, P, c_int, c_int,
+                                     P, c_size_t, P]),
+    "rtsds_crop_resize_nearest": (c_int, [P] + [c_int] * 7 + [P, c_int, c_int, c_int, c_int, c_int, P]),
     "rtsds_gaussian_blur": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P]),
     "rtsds_gta5_decode": (c_int, [P, P, c_int, c_int, P]),
     "rtsds_color_jitter_workspace": (c_size_t, [c_int, c_int]),

@@ -11,6 +11,9 @@
 //            horizontal flip (RandomHorizontalFlip: the source is read mirrored), Normalize
 //            ((v - mean) / std, on the reference's 0-255 scale), IntRangeTransformer clamp
 //            (utils.py:67-75), and the NHWC compute-dtype store the network reads.
+//   crop     RandomResizedCrop's window, drawn on the host: the resize reads the window of the
+//            source image in place (same bits as the resize of a contiguous copy); the label
+//            takes the same window through a nearest resample, so no class id is invented.
 //   blur     GaussianBlur(kernel_size, sigma): the separable Gaussian of torchvision applied as
 //            its 2-D outer-product kernel with reflect padding.
 //   jitter   ColorJitter(brightness, contrast, saturation, hue) in the permutation drawn per
@@ -57,11 +60,13 @@ __global__ void aa_weights_kernel(int in, int out, int ktaps, int* __restrict__ 
   xsize[o] = sz;
 }
 
-// horizontal pass: tmp[y][xo][c] = sum_j w[xo][j] src[y][x(xmin + j)][c], x mirrored when flip
+// horizontal pass: tmp[y][xo][c] = sum_j w[xo][j] src[y][x(xmin + j)][c], x mirrored when flip.
+// src points at the first pixel of an h x w window whose rows lie `pitch` elements apart (w * c
+// for a whole image, the source image's row for a crop read in place).
 template <typename S>
-__global__ void aa_h_kernel(const S* __restrict__ src, float* __restrict__ tmp, int h, int w, int c, int wo, int ktaps,
-                            const int* __restrict__ xmin, const int* __restrict__ xsize, const float* __restrict__ wt,
-                            int flip) {
+__global__ void aa_h_kernel(const S* __restrict__ src, long pitch, float* __restrict__ tmp, int h, int w, int c, int wo,
+                            int ktaps, const int* __restrict__ xmin, const int* __restrict__ xsize,
+                            const float* __restrict__ wt, int flip) {
   const long total = (long)h * wo * c;
   for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const int ch = (int)(e % c);
@@ -69,7 +74,7 @@ __global__ void aa_h_kernel(const S* __restrict__ src, float* __restrict__ tmp, 
     const int xo = (int)(r % wo), y = (int)(r / wo);
     const int lo = xmin[xo], sz = xsize[xo];
     const float* ww = wt + (long)xo * ktaps;
-    const S* row = src + (long)y * w * c + ch;
+    const S* row = src + (long)y * pitch + ch;
     float acc = 0.f;
     for (int j = 0; j < sz; ++j) {
       const int x = flip ? w - 1 - (lo + j) : lo + j;
@@ -124,10 +129,11 @@ extern "C" size_t rtsds_resize_aa_workspace(int c, int h, int w, int ho, int wo)
   return al256((size_t)h * wo * c * 4) + al256((size_t)(wo + ho) * 8) + al256((size_t)(wo * kx + ho * ky) * 4);
 }
 
-extern "C" int rtsds_resize_aa(const void* src, int src_u8, int c, int h, int w, void* dst, int kind, int ho, int wo,
-                               int flip, const float* mean, const float* stdv, int clamp_lo, int clamp_hi, void* ws,
-                               size_t ws_bytes, void* stream) {
-  if (c <= 0 || h <= 0 || w <= 0 || ho <= 0 || wo <= 0 || kind < 0 || kind > 2 || !src || !dst) return RTSDS_ERR_SHAPE;
+// The resize of the h x w window at `src` (row pitch in elements); both entries below validate
+// and hand over here, so a crop takes the launches, grids and arithmetic of a whole image.
+static int aa_resize_window(const void* src, int src_u8, long pitch, int c, int h, int w, void* dst, int kind, int ho, int wo,
+                            int flip, const float* mean, const float* stdv, int clamp_lo, int clamp_hi, void* ws,
+                            size_t ws_bytes, void* stream) {
   if ((mean == nullptr) != (stdv == nullptr)) return RTSDS_ERR_SHAPE;
   const int kx = aa_taps(w, wo), ky = aa_taps(h, ho);
   if (kx > kAaMaxTaps || ky > kAaMaxTaps) return RTSDS_ERR_UNSUPPORTED;
@@ -148,13 +154,73 @@ extern "C" int rtsds_resize_aa(const void* src, int src_u8, int c, int h, int w,
   const long nh = (long)h * wo * c, nv = (long)ho * wo * c;
   const int bh = (int)std::min<long>(8192, (nh + 255) / 256), bv = (int)std::min<long>(8192, (nv + 255) / 256);
   if (src_u8)
-    hipLaunchKernelGGL(aa_h_kernel<uint8_t>, dim3(bh), dim3(256), 0, st, (const uint8_t*)src, tmp, h, w, c, wo, kx, xmin,
-                       xsz, wx, flip);
+    hipLaunchKernelGGL(aa_h_kernel<uint8_t>, dim3(bh), dim3(256), 0, st, (const uint8_t*)src, pitch, tmp, h, w, c, wo, kx,
+                       xmin, xsz, wx, flip);
   else
-    hipLaunchKernelGGL(aa_h_kernel<float>, dim3(bh), dim3(256), 0, st, (const float*)src, tmp, h, w, c, wo, kx, xmin, xsz,
-                       wx, flip);
+    hipLaunchKernelGGL(aa_h_kernel<float>, dim3(bh), dim3(256), 0, st, (const float*)src, pitch, tmp, h, w, c, wo, kx, xmin,
+                       xsz, wx, flip);
   hipLaunchKernelGGL(aa_v_kernel, dim3(bv), dim3(256), 0, st, tmp, dst, h, wo, c, ho, ky, ymin, ysz, wy, kind, mean, stdv,
                      clamp_lo, clamp_hi);
+  RET_LAUNCH();
+}
+
+extern "C" int rtsds_resize_aa(const void* src, int src_u8, int c, int h, int w, void* dst, int kind, int ho, int wo,
+                               int flip, const float* mean, const float* stdv, int clamp_lo, int clamp_hi, void* ws,
+                               size_t ws_bytes, void* stream) {
+  if (c <= 0 || h <= 0 || w <= 0 || ho <= 0 || wo <= 0 || kind < 0 || kind > 2 || !src || !dst) return RTSDS_ERR_SHAPE;
+  return aa_resize_window(src, src_u8, (long)w * c, c, h, w, dst, kind, ho, wo, flip, mean, stdv, clamp_lo, clamp_hi, ws,
+                          ws_bytes, stream);
+}
+
+// a window [y0, y0 + hc) x [x0, x0 + wc) inside [0, h) x [0, w), without overflow in the sums
+static bool window_inside(int h, int w, int y0, int x0, int hc, int wc) {
+  return h > 0 && w > 0 && hc > 0 && wc > 0 && y0 >= 0 && x0 >= 0 && hc <= h && wc <= w && y0 <= h - hc && x0 <= w - wc;
+}
+
+// ---- crop + resize: the resize of src[y0 : y0 + hc, x0 : x0 + wc, :] read in place ----
+// (RandomResizedCrop ahead of Resize: the same bits as rtsds_resize_aa on a contiguous copy of
+// the window -- the weights come from (hc, wc), the kernels only see another origin and pitch)
+extern "C" int rtsds_crop_resize_aa(const void* src, int src_u8, int c, int h, int w, int y0, int x0, int hc, int wc, void* dst,
+                                    int kind, int ho, int wo, int flip, const float* mean, const float* stdv, int clamp_lo,
+                                    int clamp_hi, void* ws, size_t ws_bytes, void* stream) {
+  if (c <= 0 || ho <= 0 || wo <= 0 || kind < 0 || kind > 2 || !src || !dst) return RTSDS_ERR_SHAPE;
+  if (!window_inside(h, w, y0, x0, hc, wc)) return RTSDS_ERR_SHAPE;
+  const size_t origin = ((size_t)y0 * w + x0) * c;
+  const void* win = src_u8 ? (const void*)((const uint8_t*)src + origin) : (const void*)((const float*)src + origin);
+  return aa_resize_window(win, src_u8, (long)w * c, c, hc, wc, dst, kind, ho, wo, flip, mean, stdv, clamp_lo, clamp_hi, ws,
+                          ws_bytes, stream);
+}
+
+// nearest resample of a label window (ATen upsample_nearest2d's index rule: floor(o * in / out)
+// in fp32, capped at in - 1); flip writes the mirror of the unflipped result (output column xo
+// takes the source column of wo - 1 - xo: the floor rule is not symmetric, so mirroring the
+// window first would pick other pixels); clamped when lo <= hi
+template <typename S>
+__global__ void crop_nearest_kernel(const S* __restrict__ src, int w, int y0, int x0, int hc, int wc,
+                                    int64_t* __restrict__ dst, int ho, int wo, int flip, int clamp_lo, int clamp_hi) {
+  const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (e >= (long)ho * wo) return;
+  const int xo = (int)(e % wo), yo = (int)(e / wo);
+  const float sh = (float)hc / (float)ho, sw = (float)wc / (float)wo;
+  const int sy = std::min((int)floorf((float)yo * sh), hc - 1);
+  const int sx = std::min((int)floorf((float)(flip ? wo - 1 - xo : xo) * sw), wc - 1);
+  long v = (long)src[(long)(y0 + sy) * w + (x0 + sx)];
+  if (clamp_lo <= clamp_hi) v = std::min<long>(std::max<long>(v, clamp_lo), clamp_hi);
+  dst[e] = v;
+}
+
+extern "C" int rtsds_crop_resize_nearest(const void* src, int src_i64, int h, int w, int y0, int x0, int hc, int wc,
+                                         int64_t* dst, int ho, int wo, int flip, int clamp_lo, int clamp_hi, void* stream) {
+  if (ho <= 0 || wo <= 0 || !src || !dst) return RTSDS_ERR_SHAPE;
+  if (!window_inside(h, w, y0, x0, hc, wc)) return RTSDS_ERR_SHAPE;
+  const long n = (long)ho * wo;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (src_i64)
+    hipLaunchKernelGGL(crop_nearest_kernel<int64_t>, grid, dim3(256), 0, (hipStream_t)stream, (const int64_t*)src, w, y0, x0,
+                       hc, wc, dst, ho, wo, flip, clamp_lo, clamp_hi);
+  else
+    hipLaunchKernelGGL(crop_nearest_kernel<uint8_t>, grid, dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, w, y0, x0,
+                       hc, wc, dst, ho, wo, flip, clamp_lo, clamp_hi);
   RET_LAUNCH();
 }
 

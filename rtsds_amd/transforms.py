@@ -13,13 +13,20 @@ Reference pipelines (main.py:60-96), reproduced here per sample of a batch:
 * GTA5 label:        Resize(image_size)   (the augmentation flips the image only, as the
                      reference's pipeline does)
 
+Beyond the reference, opt-in: RandomResizedCrop in the augmentation list draws a window of the
+source image per sample; the image's resize reads that window in place (rtsds_crop_resize_aa)
+and the label takes the same window through a nearest resample (rtsds_crop_resize_nearest).
+RandomHorizontalFlip(labels=True) mirrors the label with the image.  ImagePipeline records what
+it did per sample in ``last_geometry``; DeviceLoader hands that to the LabelPipeline.
+
 The image comes out in the network's input layout (NHWC, the runtime compute dtype), so the
 model's input packing is a no-op; labels come out int64 [N, 1, H, W] as the reference's loaders
 deliver them (train.py squeezes dim 1).  Random decisions draw from torch's CPU generator in
 torchvision's call order (RandomApply's coin, then per listed transform: GaussianBlur's sigma,
-the flip coin, ColorJitter's permutation and factors).
+the flip coin, ColorJitter's permutation and factors, RandomResizedCrop's get_params).
 """
 import ctypes
+import math
 
 import torch
 
@@ -50,8 +57,55 @@ class GaussianBlur:
 
 
 class RandomHorizontalFlip:
-    def __init__(self, p=0.5):
+    """RandomHorizontalFlip(p).  The reference's pipeline mirrors the image only (main.py:86-96);
+    ``labels=True`` mirrors the label with it."""
+
+    def __init__(self, p=0.5, labels=False):
         self.p = p
+        self.labels = bool(labels)
+
+
+def _ascending_pair(name, value):
+    ok = isinstance(value, (tuple, list)) and len(value) == 2 and \
+        all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in value)
+    if not ok or not 0 < value[0] <= value[1] or not math.isfinite(value[1]):
+        raise ValueError(f"{name} should be a pair of positive numbers (min, max).")
+    return float(value[0]), float(value[1])
+
+
+class RandomResizedCrop:
+    """torchvision RandomResizedCrop's window: a share ``scale`` of the area at an aspect ratio
+    (w / h) from ``ratio``, log-uniform.  The output size is the pipeline's: the window goes to
+    the resize."""
+
+    def __init__(self, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)):
+        self.scale = _ascending_pair("scale", scale)
+        self.ratio = _ascending_pair("ratio", ratio)
+
+    def params(self, h, w):
+        """(y0, x0, hc, wc) in get_params' draw order: up to 10 tries of (area, log ratio) and,
+        for the first that fits, the two origins; else the ratio-clamped centre crop."""
+        area = h * w
+        log_ratio = (math.log(self.ratio[0]), math.log(self.ratio[1]))
+        for _ in range(10):
+            ta = area * torch.empty(1).uniform_(self.scale[0], self.scale[1]).item()
+            ar = math.exp(torch.empty(1).uniform_(log_ratio[0], log_ratio[1]).item())
+            wc = int(round(math.sqrt(ta * ar)))
+            hc = int(round(math.sqrt(ta / ar)))
+            if 0 < wc <= w and 0 < hc <= h:
+                y0 = int(torch.randint(0, h - hc + 1, size=(1,)).item())
+                x0 = int(torch.randint(0, w - wc + 1, size=(1,)).item())
+                return y0, x0, hc, wc
+        in_ratio = float(w) / float(h)
+        if in_ratio < self.ratio[0]:
+            wc = w
+            hc = int(round(wc / self.ratio[0]))
+        elif in_ratio > self.ratio[1]:
+            hc = h
+            wc = int(round(hc * self.ratio[1]))
+        else:
+            wc, hc = w, h
+        return (h - hc) // 2, (w - wc) // 2, hc, wc
 
 
 def _jitter_range(name, value, center, lo_bound, hi_bound):
@@ -117,7 +171,12 @@ def augmentation_loader(config, probability):
             out.append(GaussianBlur(kernel_size=[int(i) for i in str(c["kernel_size"]).split(",")],
                                     sigma=[float(i) for i in str(c["sigma"]).split(",")]))
         elif key == "RandomHorizontalFlip":
-            out.append(RandomHorizontalFlip(p=aug["RandomHorizontalFlip"]["p"]))
+            c = aug["RandomHorizontalFlip"]
+            out.append(RandomHorizontalFlip(p=c["p"], labels=c.get("labels", False)))
+        elif key == "RandomResizedCrop":
+            c = aug["RandomResizedCrop"] or {}
+            out.append(RandomResizedCrop(**{k: [float(i) for i in str(c[k]).split(",")]
+                                            for k in ("scale", "ratio") if k in c}))
         elif key == "ColorJitter":
             c = aug["ColorJitter"]
             out.append(ColorJitter(brightness=c["brightness"], contrast=c["contrast"], saturation=c["saturation"],
@@ -128,20 +187,45 @@ def augmentation_loader(config, probability):
     return RandomApply(out, p=probability)
 
 
-def _decisions(augment):
-    """([(transform, its draw)] for the blur / jitter in list order, flip) for one sample,
-    drawing in torchvision's order."""
+def _sample_draws(augment, h=None, w=None):
+    """([(transform, its draw)] for the blur / jitter in list order, flip, window, flip_label)
+    for one sample of source size (h, w), drawing in torchvision's order.  window is
+    RandomResizedCrop's (y0, x0, hc, wc) or None; flip_label says the flip came from a
+    RandomHorizontalFlip(labels=True).  Geometry takes effect at the resize wherever its key
+    stands (the window is uniform in x, so a flip ahead of it changes no distribution)."""
     if augment is None or not augment.transforms:
-        return [], False
+        return [], False, None, False
     if augment.p < torch.rand(1):
-        return [], False
-    ops, flip = [], False
+        return [], False, None, False
+    ops, flip, window, flip_label = [], False, None, False
     for t in augment.transforms:
         if isinstance(t, (GaussianBlur, ColorJitter)):
             ops.append((t, t.params()))
         elif isinstance(t, RandomHorizontalFlip):
             flip = bool(torch.rand(1) < t.p)
-    return ops, flip
+            flip_label = flip and t.labels
+        elif isinstance(t, RandomResizedCrop):
+            if h is None or w is None:
+                raise RuntimeError("rtsds_amd.transforms: RandomResizedCrop draws for a source size")
+            window = t.params(h, w)
+    return ops, flip, window, flip_label
+
+
+def _decisions(augment):
+    """([(transform, its draw)] for the blur / jitter in list order, flip) for one sample of a
+    list without geometry that needs the source size."""
+    return _sample_draws(augment)[:2]
+
+
+class Geometry(tuple):
+    """One sample's entry of ImagePipeline.last_geometry: (y0, x0, hc, wc, flip_label), the
+    window in the source image (the whole image without a crop) and whether the label is to be
+    mirrored; ``source`` is the source image's (h, w), which the label must share."""
+
+    def __new__(cls, y0, x0, hc, wc, flip_label, source):
+        self = super().__new__(cls, (int(y0), int(x0), int(hc), int(wc), bool(flip_label)))
+        self.source = (int(source[0]), int(source[1]))
+        return self
 
 
 def color_jitter(img, order, fb, fc, fs, fh, value_range=255.0, out=None):
@@ -184,6 +268,7 @@ class ImagePipeline:
         self.size = (int(size[0]), int(size[1]))
         self.mean, self.std = tuple(mean), tuple(std)
         self.augment = augment
+        self.last_geometry = None  # per sample of the last batch: None or a Geometry
         self._ms = {}
 
     def _mean_std(self, device):
@@ -199,11 +284,19 @@ class ImagePipeline:
         ho, wo = self.size
         out = torch.empty((len(images), 3, ho, wo), dtype=dtype, device=dev, memory_format=CL)
         ms, sd = self._mean_std(dev)
+        kind = 1 if dtype == torch.bfloat16 else 0
+        self.last_geometry = geometry = []
         for n, img in enumerate(images):
             img = _as_hwc_u8(img)
             h, w, c = img.shape
             src, src_u8 = img, 1
-            ops, flip = _decisions(self.augment)
+            ops, flip, window, flip_label = _sample_draws(self.augment, h, w)
+            if window == (0, 0, h, w):  # the whole image is no window: the plain resize, for the label too
+                window = None
+            if window is not None or flip_label:
+                geometry.append(Geometry(*(window or (0, 0, h, w)), flip_label, source=(h, w)))
+            else:
+                geometry.append(None)
             for t, drawn in ops:
                 if isinstance(t, GaussianBlur):
                     dstf = torch.empty((h, w, c), dtype=torch.float32, device=dev)
@@ -213,36 +306,66 @@ class ImagePipeline:
                     dstf = torch.empty((h, w, c), dtype=torch.float32, device=dev) if src_u8 else src
                     color_jitter(src, *drawn, value_range=t.value_range, out=dstf)
                 src, src_u8 = dstf, 0
-            ws = workspace(lib.rtsds_resize_aa_workspace(c, h, w, ho, wo), dev)
             dst = out[n].permute(1, 2, 0)  # this image's HWC slot of the NHWC batch
-            _check(lib.rtsds_resize_aa(src.data_ptr(), src_u8, c, h, w, dst.data_ptr(),
-                                       1 if dtype == torch.bfloat16 else 0, ho, wo, int(flip), ms.data_ptr(),
-                                       sd.data_ptr(), 0, -1, ws.data_ptr(), ws.numel(), stream()), "resize")
+            if window is None:
+                ws = workspace(lib.rtsds_resize_aa_workspace(c, h, w, ho, wo), dev)
+                _check(lib.rtsds_resize_aa(src.data_ptr(), src_u8, c, h, w, dst.data_ptr(), kind, ho, wo, int(flip),
+                                           ms.data_ptr(), sd.data_ptr(), 0, -1, ws.data_ptr(), ws.numel(), stream()),
+                       "resize")
+            else:  # the blurred / jittered whole image, cut where the resize reads it
+                y0, x0, hc, wc = window
+                ws = workspace(lib.rtsds_resize_aa_workspace(c, hc, wc, ho, wo), dev)
+                _check(lib.rtsds_crop_resize_aa(src.data_ptr(), src_u8, c, h, w, y0, x0, hc, wc, dst.data_ptr(), kind,
+                                                ho, wo, int(flip), ms.data_ptr(), sd.data_ptr(), 0, -1, ws.data_ptr(),
+                                                ws.numel(), stream()), "crop resize")
         return out
 
 
 class LabelPipeline:
     """Resize(size, antialias=True) of an id map (interpolated in float, rounded half-to-even)
-    -> optional IntRangeTransformer(lo, hi) clamp; int64 [N, 1, Ho, Wo]."""
+    -> optional IntRangeTransformer(lo, hi) clamp; int64 [N, 1, Ho, Wo].  With the image
+    pipeline's ``last_geometry``: a sample with a window is cut and resampled nearest (no ids
+    invented at region borders) straight from its uint8 / int64 source, mirrored when its flip
+    was paired; a paired flip without a window mirrors the antialiased resize."""
 
     def __init__(self, size, clamp=None):
         self.size = (int(size[0]), int(size[1]))
         self.clamp = clamp
 
-    def __call__(self, labels):
+    def __call__(self, labels, geometry=None):
+        if geometry is not None and len(geometry) != len(labels):
+            raise RuntimeError(f"rtsds_amd.transforms: geometry of {len(geometry)} samples for {len(labels)} labels")
         dev = labels[0].device
         ho, wo = self.size
         out = torch.empty((len(labels), 1, ho, wo), dtype=torch.int64, device=dev)
         lo, hi = self.clamp if self.clamp is not None else (0, -1)
         for n, lab in enumerate(labels):
             lab = _as_hwc_u8(lab) if lab.dtype == torch.uint8 else lab
+            geo = geometry[n] if geometry is not None else None
+            flip = 0
+            if geo is not None:
+                if lab.dtype not in (torch.uint8, torch.int64):
+                    raise RuntimeError("rtsds_amd.transforms: uint8 or int64 labels expected")
+                h, w = (lab.shape[0], lab.shape[1]) if lab.dtype == torch.uint8 else (lab.shape[-2], lab.shape[-1])
+                if lab.numel() != h * w:
+                    raise RuntimeError("rtsds_amd.transforms: single-channel labels expected")
+                y0, x0, hc, wc, flip = geo
+                if getattr(geo, "source", (h, w)) != (h, w):
+                    raise RuntimeError(f"rtsds_amd.transforms: label of {h} x {w} for a window drawn in an image of "
+                                       f"{geo.source[0]} x {geo.source[1]}")
+                if (y0, x0, hc, wc) != (0, 0, h, w):
+                    lab = lab.contiguous()
+                    _check(lib.rtsds_crop_resize_nearest(lab.data_ptr(), int(lab.dtype == torch.int64), h, w, y0, x0,
+                                                         hc, wc, out[n].data_ptr(), ho, wo, int(flip), int(lo),
+                                                         int(hi), stream()), "label crop resize")
+                    continue
             if lab.dtype == torch.int64:  # decoded GTA5 ids: interpolate from a float copy
                 src, u8 = lab.reshape(lab.shape[-2], lab.shape[-1], 1).float().contiguous(), 0
             else:
                 src, u8 = lab, 1
             h, w = src.shape[0], src.shape[1]
             ws = workspace(lib.rtsds_resize_aa_workspace(1, h, w, ho, wo), dev)
-            _check(lib.rtsds_resize_aa(src.data_ptr(), u8, 1, h, w, out[n].data_ptr(), 2, ho, wo, 0, None, None,
+            _check(lib.rtsds_resize_aa(src.data_ptr(), u8, 1, h, w, out[n].data_ptr(), 2, ho, wo, int(flip), None, None,
                                        int(lo), int(hi), ws.data_ptr(), ws.numel(), stream()), "label resize")
         return out
 
@@ -265,7 +388,8 @@ class DeviceLoader:
     """A DataLoader of raw samples -> batches ready for the network: images moved to the device
     (pinned, non-blocking) and run through ``image_pipe``, labels through ``label_pipe`` (GTA5
     colour labels decoded first when ``decode_rgb_labels``).  Same iteration / len semantics as
-    the wrapped loader, so train.train / adversarial_train consume it unchanged."""
+    the wrapped loader, so train.train / adversarial_train consume it unchanged.  An image pipe
+    that records ``last_geometry`` (crop windows, paired flips) has it handed to the label pipe."""
 
     def __init__(self, loader, image_pipe, label_pipe, device="cuda", decode_rgb_labels=False):
         self.loader = loader
@@ -295,7 +419,9 @@ class DeviceLoader:
             images, labels = self._move(images), self._move(labels)
             if self.decode:
                 labels = [decode_gta5_labels(t) for t in labels]
-            yield self.image_pipe(images), self.label_pipe(labels)
+            x = self.image_pipe(images)
+            geometry = getattr(self.image_pipe, "last_geometry", None)
+            yield x, (self.label_pipe(labels) if geometry is None else self.label_pipe(labels, geometry))
 
 
 def parse_size(s):
@@ -303,4 +429,5 @@ def parse_size(s):
 
 
 __all__ = ["ImagePipeline", "LabelPipeline", "DeviceLoader", "GaussianBlur", "RandomHorizontalFlip", "ColorJitter",
-           "RandomApply", "augmentation_loader", "color_jitter", "decode_gta5_labels", "collate_raw", "parse_size"]
+           "RandomResizedCrop", "RandomApply", "Geometry", "augmentation_loader", "color_jitter", "decode_gta5_labels",
+           "collate_raw", "parse_size"]
