@@ -362,6 +362,19 @@ int rtsds_sgd_step(float* param, const void* grad, float* momentum_buf, void* bf
                    long n, const float* hyper, float lr, float momentum, float dampening,
                    float weight_decay, int nesterov, int first, float grad_scale, int grad_dtype, void* stream);
 
+/* Mean-teacher (EMA) update over a flat fp32 arena (no counterpart in the reference): per
+ * element t = t + w * (s - t) as three separately rounded fp32 operations (subtract, multiply,
+ * add; never an FMA), so it can be restated exactly; w = float32(1 - decay) from the host.
+ * teacher_bf16_shadow (may be NULL) receives bf16(t), round to nearest even, in the same pass.
+ * 16-byte accesses when the three pointers are 16-byte aligned, element by element otherwise.
+ * rtsds_ema_many: the same update (no shadow) in one launch over count segments outside an arena
+ * (BatchNorm running statistics); teacher / student / numel are DEVICE tables of count entries.
+ * Neither synchronises, allocates or touches the host.                                      */
+int rtsds_ema_step(float* teacher, const float* student, void* teacher_bf16_shadow, long n, float w,
+                   void* stream);
+int rtsds_ema_many(int count, float* const* teacher, const float* const* student, const long* numel,
+                   float w, void* stream);
+
 /* ---------------------------------------------------------------- metrics
  * argmax over channels, first maximum wins (train.py:102-106,272-275; validation.py:51).
  * out (int64 [n*hw]) may be NULL; if target and correct are given, *correct += #matches.
@@ -451,6 +464,18 @@ int rtsds_conf_hist(const float* acc, unsigned long long* hist, uint8_t* pred, u
                     long total, int c, int bins, float inv, void* stream);
 int rtsds_pseudo_select(const uint8_t* pred, const uint16_t* cbin, const int* tbin, int64_t* out,
                         long total, int c, int ignore_index, void* stream);
+
+/* rtsds_upsample_pseudo: the three entries rtsds_upsoftmax_acc (accumulate = 0, flip = 0) ->
+ *   rtsds_conf_hist (inv = 1, no histogram) -> rtsds_pseudo_select in one pass over the
+ *   low-resolution head x (NHWC [n][hi][wi][c], geometry as rtsds_upsoftmax_acc): per output
+ *   pixel the probabilities stay in registers, pred[p] = k (uint8) and cbin[p] = b (uint16) by
+ *   rtsds_conf_hist's rule, labels[p] (int64) = b >= tbin[k] ? k : ignore_index.  Each output
+ *   may be NULL, not all three; labels needs tbin (c device ints).  2 <= c <= 32, bins a power
+ *   of two in [16, 1024].  Equal to the chain bit for bit; the fp32 probability tensor is never
+ *   written.  For the online (mean-teacher) labels of selftrain.TeacherLoader.               */
+int rtsds_upsample_pseudo(const void* x, uint8_t* pred, uint16_t* cbin, const int* tbin, int64_t* labels,
+                          int n, int hi, int wi, int c, int ho, int wo, float scale_h, float scale_w,
+                          int bins, int ignore_index, int dtype, void* stream);
 
 /* ---------------------------------------------------------------- ClassMix (self-training)
  * No counterpart in the reference.  ClassMix (DACS, DAFormer) pastes the pixels of half of the
@@ -585,7 +610,7 @@ int rtsds_pooled_mlp_fwd(const void* p, const void* w1, const float* b1, const v
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 15
+#define RTSDS_ABI_VERSION 16
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

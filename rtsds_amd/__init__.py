@@ -7,5 +7,6 @@ include/rtsds_hip.h); PyTorch supplies device memory, streams, autograd plumbing
 torch.distributed (RCCL).
 """
 from .runtime import compute_dtype, precision, set_compute_dtype  # noqa: F401
+from .ema import EMATeacher  # noqa: F401,E402
 
-__all__ = ["compute_dtype", "precision", "set_compute_dtype"]
+__all__ = ["compute_dtype", "precision", "set_compute_dtype", "EMATeacher"]

@@ -115,3 +115,82 @@ extern "C" int rtsds_sgd_step(float* param, const void* grad, float* momentum_bu
                                                dampening, weight_decay, nesterov, first, grad_scale));
   RET_LAUNCH();
 }
+
+// ------------------------------------------------------------------ EMA teacher (flat, fused)
+// Mean-teacher update t += w (s - t) over a flat arena (ema.EMATeacher; no reference
+// counterpart), the bf16 shadow written in the same pass as adam_kernel does.  Three separately
+// rounded fp32 operations, never an FMA, so the update can be restated exactly on the host or
+// with three torch ops; w = float32(1 - decay) comes from the host.
+// (__fadd_rn(t, __fmul_rn(w, __fsub_rn(s, t))): the header intrinsics are plain operators the
+// compiler may still contract into an FMA, so the three operations are written out with
+// contraction switched off for this function.)
+RT_DEV float ema_update(float t, float s, float w) {
+#pragma clang fp contract(off)
+  const float d = s - t;
+  const float m = w * d;
+  return t + m;
+}
+// VEC: 8 elements per thread and trip as two 16-B loads of t and of s, two 16-B stores of t and
+// one 16-B store of the shadow (the host checked the three pointers); the tail, and everything
+// when a pointer is not 16-B aligned, goes element by element.
+template <bool VEC>
+__global__ void __launch_bounds__(256) ema_kernel(float* __restrict__ t, const float* __restrict__ s, bf16* __restrict__ shadow,
+                                                  long n, float w) {
+  const long nv = VEC ? n >> 3 : 0;
+  GRID_STRIDE(i, nv) {
+    f32x4 ta = ((const f32x4*)t)[2 * i], tb = ((const f32x4*)t)[2 * i + 1];
+    const f32x4 sa = ((const f32x4*)s)[2 * i], sb = ((const f32x4*)s)[2 * i + 1];
+    bf16x8 h;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      ta[j] = ema_update(ta[j], sa[j], w);
+      tb[j] = ema_update(tb[j], sb[j], w);
+      h[j] = (bf16)ta[j];
+      h[4 + j] = (bf16)tb[j];
+    }
+    ((f32x4*)t)[2 * i] = ta;
+    ((f32x4*)t)[2 * i + 1] = tb;
+    if (shadow) ((bf16x8*)shadow)[i] = h;
+  }
+  const long done = nv << 3;
+  GRID_STRIDE(r, n - done) {
+    const long i = done + r;
+    const float ti = ema_update(t[i], s[i], w);
+    t[i] = ti;
+    if (shadow) shadow[i] = (bf16)ti;
+  }
+}
+extern "C" int rtsds_ema_step(float* teacher, const float* student, void* teacher_bf16_shadow, long n, float w, void* stream) {
+  if (n <= 0) return RTSDS_ERR_SHAPE;
+  if (teacher == nullptr || student == nullptr || ((uintptr_t)teacher & 3) || ((uintptr_t)student & 3) ||
+      ((uintptr_t)teacher_bf16_shadow & 1))
+    return RTSDS_ERR_UNSUPPORTED;
+  const bool vec = (((uintptr_t)teacher | (uintptr_t)student | (uintptr_t)teacher_bf16_shadow) & 15) == 0 && n >= 8;
+  with_bool(vec, [&](auto v) {
+    constexpr bool VEC = decltype(v)::value;
+    hipLaunchKernelGGL(ema_kernel<VEC>, dim3(ew_blocks(VEC ? (n + 7) / 8 : n, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       teacher, student, (bf16*)teacher_bf16_shadow, n, w);
+  });
+  RET_LAUNCH();
+}
+
+// The same update for state outside an arena (the BatchNorm running statistics): count segments,
+// one workgroup row (blockIdx.y) each, described by three device tables; no shadow.
+static const int kEmaManyBlocks = 4;  // workgroups per segment: a BatchNorm statistic is <= 2048 floats
+__global__ void __launch_bounds__(256) ema_many_kernel(float* const* __restrict__ teacher, const float* const* __restrict__ student,
+                                                       const long* __restrict__ numel, float w) {
+  const int seg = blockIdx.y;
+  float* t = teacher[seg];
+  const float* s = student[seg];
+  const long n = numel[seg];
+  GRID_STRIDE(i, n) t[i] = ema_update(t[i], s[i], w);
+}
+extern "C" int rtsds_ema_many(int count, float* const* teacher, const float* const* student, const long* numel, float w,
+                              void* stream) {
+  if (count <= 0) return RTSDS_ERR_SHAPE;
+  if (teacher == nullptr || student == nullptr || numel == nullptr || (((uintptr_t)teacher | (uintptr_t)student | (uintptr_t)numel) & 7) ||
+      count > 65535)
+    return RTSDS_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(ema_many_kernel, dim3(kEmaManyBlocks, count), dim3(256), 0, (hipStream_t)stream, teacher, student, numel, w);
+  RET_LAUNCH();
+}

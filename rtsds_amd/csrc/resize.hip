@@ -1,5 +1,6 @@
 // Bilinear resize (align_corners=False), forward and backward, and the kernels fused onto it
-// (gfx950): resize + softmax for the discriminator input, multi-scale / flip evaluation.
+// (gfx950): resize + softmax for the discriminator input, multi-scale / flip evaluation, the
+// online teacher's pseudo-labels.
 // Every output bit of the unit is pinned (tests/test_resize_bits_gpu.py), and each piece that
 // carries a bit-exactness promise exists once:
 //   bil_src / bil_mix / bil_first_ge (common.h)   taps, weights, the blend's association
@@ -780,6 +781,53 @@ __global__ void __launch_bounds__(256) upsoftmax_acc_kernel(const T* __restrict_
   __syncthreads();  // every lane reaches the same barrier (no early exit)
   upsm_tile_copy<false>(dst, tbuf, nel, head);
 }
+// ------------------------------------------------------------------ low-resolution head -> pseudo-labels
+// The online teacher's labels (selftrain.TeacherLoader): upsoftmax_acc_kernel's tile and
+// probabilities (accumulate = 0, flip = 0: v[k] = __fmul_rn(z[k], iz)), reduced in registers by
+// conf_hist_tile's rule (pseudo.hip: first maximum wins, a NaN beats every number and the first
+// NaN wins, conf = best * 1.0f, bin = floor(conf * bins) clamped to [0, bins - 1], a conf that is
+// not > 0 in bin 0) and thresholded by pseudo_select_kernel's: pred / cbin / labels equal the
+// chain rtsds_upsoftmax_acc -> rtsds_conf_hist (inv = 1) -> rtsds_pseudo_select bit for bit, and
+// the fp32 probability tensor (c x 4 B written and read again per pixel) never exists.  LDS holds
+// the staged source rows only; a tile's pixels are lane-consecutive, so each output leaves as
+// contiguous 1 / 2 / 8-B stores of a wave.
+template <typename T, bool STAGED, int CC>  // CC > 0: compile-time class count (19), 0: runtime c
+__global__ void __launch_bounds__(256) upsample_pseudo_kernel(const T* __restrict__ x, uint8_t* __restrict__ pred,
+                                                              uint16_t* __restrict__ cbin, const int* __restrict__ tbin,
+                                                              int64_t* __restrict__ labels, int hi, int wi, int c_, int ho, int wo,
+                                                              float sh, float sw, int bins, int ignore, int tiles) {
+  const int c = CC > 0 ? CC : c_;
+  extern __shared__ __attribute__((aligned(16))) float src[];  // STAGED: [2][ncols][c]
+  const int tid = threadIdx.x;
+  const UpsmTile<T> tl = upsm_tile<T, STAGED>(x, src, hi, wi, c, ho, wo, sh, sw, tiles);
+  if (STAGED) __syncthreads();
+  if (tid >= tl.np) return;  // no barrier below
+  float z[kUpsmMaxC];
+  float iz;
+  upsm_probs<T, STAGED, CC>(tl.r0, tl.r1, src, tl.wlo, tl.n1, c, tl.ow0 + tid, sw, wi, tl.lh0, tl.lh1, z, iz);
+  float best = 0.f;
+  int bi = 0;
+#pragma unroll
+  for (int k = 0; k < kUpsmMaxC; ++k)
+    if (k < c) {
+      const float v = __fmul_rn(z[k], iz);
+      if (k == 0 || v > best || (v != v && best == best)) {
+        best = v;
+        bi = k;
+      }
+    }
+  const float fb = (float)bins;
+  const float conf = best * 1.0f;
+  int b = 0;
+  if (conf > 0.f) {
+    const float t = floorf(conf * fb);
+    b = t >= fb ? bins - 1 : (int)t;
+  }
+  const long p = tl.row * wo + tl.ow0 + tid;
+  if (pred) pred[p] = (uint8_t)bi;
+  if (cbin) cbin[p] = (uint16_t)b;
+  if (labels) labels[p] = b >= tbin[bi] ? bi : ignore;
+}
 template <typename T, int CC>  // CC > 0: compile-time class count (19), 0: runtime c
 __global__ void __launch_bounds__(256) upsoftmax_bwd_w_kernel(const T* __restrict__ dy, int dyld, const T* __restrict__ y,
                                                               int yld, float* __restrict__ tmp, int wi, int c_, int wo, float sw,
@@ -915,6 +963,27 @@ extern "C" int rtsds_upsoftmax_acc(const void* x, float* acc, int64_t* pred, int
   DISPATCH_T(dtype, upsm_dispatch(staged, c, [&](auto s, auto cc) {
     hipLaunchKernelGGL((upsoftmax_acc_kernel<T, decltype(s)::value, decltype(cc)::value>), dim3(p.blocks), dim3(256), lds, st,
                        (const T*)x, acc, pred, hi, wi, c, ho, wo, scale_h, scale_w, flip, accumulate, p.tiles);
+  }));
+  RET_LAUNCH();
+}
+extern "C" int rtsds_upsample_pseudo(const void* x, uint8_t* pred, uint16_t* cbin, const int* tbin, int64_t* labels, int n, int hi,
+                                     int wi, int c, int ho, int wo, float scale_h, float scale_w, int bins, int ignore_index,
+                                     int dtype, void* stream) {
+  if (c < 2) return RTSDS_ERR_SHAPE;  // (c > 32: upsm_plan)
+  if (bins < 16 || bins > 1024 || (bins & (bins - 1))) return RTSDS_ERR_SHAPE;
+  UpsmPlan p;
+  if (const int rc = upsm_plan(n, hi, wi, c, ho, wo, scale_w, p)) return rc;
+  if (x == nullptr || (pred == nullptr && cbin == nullptr && labels == nullptr) || (labels != nullptr && tbin == nullptr) ||
+      ((uintptr_t)cbin & 1) || ((uintptr_t)tbin & 3) || ((uintptr_t)labels & 7))
+    return RTSDS_ERR_UNSUPPORTED;
+  // LDS holds the staged source rows and nothing else (no output tile): staged whenever they fit
+  // the 64 KiB a workgroup gets without opting in to more
+  const bool staged = p.taps + 16 <= (size_t)64 * 1024;
+  const size_t lds = staged ? p.taps + 16 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_T(dtype, upsm_dispatch(staged, c, [&](auto s, auto cc) {
+    hipLaunchKernelGGL((upsample_pseudo_kernel<T, decltype(s)::value, decltype(cc)::value>), dim3(p.blocks), dim3(256), lds, st,
+                       (const T*)x, pred, cbin, tbin, labels, hi, wi, c, ho, wo, scale_h, scale_w, bins, ignore_index, p.tiles);
   }));
   RET_LAUNCH();
 }

@@ -1603,6 +1603,105 @@ def pseudo_select(pred, cbin, tbin, ignore_index, out=None):
     return out
 
 
+def upsample_pseudo(x, geo, bins=1024, tbin=None, ignore_index=None, pred=None, cbin=None, labels=None):
+    """Pseudo-labels straight from a low-resolution head (rtsds_upsample_pseudo): the chain
+    upsample_softmax_accumulate(accumulate=False) -> confidence_histogram(passes=1, pred, cbin)
+    -> pseudo_select in one pass, bit for bit, without the fp32 probability tensor.  ``x``: the
+    head [n, c, hi, wi] (2..32 classes), ``geo`` from upsample_geometry(); ``bins`` a power of two
+    in [16, 1024].  With ``tbin`` (int32 [c] on the device) and ``ignore_index`` the int64 label
+    map [n, H, W] is produced (allocated unless ``labels`` is given); without ``tbin`` the
+    uint8 ``pred`` and uint16 ``cbin`` maps are (allocated unless given).  Outputs passed in are
+    filled whichever mode.  Inference only, no host sync.  Returns (pred, cbin, labels), None for
+    an output not produced."""
+    fn = "upsample_pseudo"
+    if not x.is_cuda or (tbin is not None and not tbin.is_cuda):
+        raise RuntimeError(f"rtsds_amd: {fn}: x and tbin must be HIP tensors; there is no CPU fallback")
+    if x.dim() != 4 or x.numel() == 0 or not 2 <= x.shape[1] <= 32:
+        raise RuntimeError(f"rtsds_amd: {fn}: x must be [n, c, hi, wi] with 2..32 classes, got {tuple(x.shape)}")
+    bins = int(bins)
+    if bins < 16 or bins > 1024 or bins & (bins - 1):
+        raise RuntimeError(f"rtsds_amd: {fn}: bins must be a power of two in [16, 1024], got {bins}")
+    x = nhwc(x.detach())
+    n, c, hi, wi = x.shape
+    ho, wo, sh, sw = geo
+    dev = x.device
+    if labels is not None and tbin is None:
+        raise RuntimeError(f"rtsds_amd: {fn}: labels need the thresholds tbin")
+    if tbin is not None:
+        if ignore_index is None:
+            raise RuntimeError(f"rtsds_amd: {fn}: tbin needs ignore_index")
+        _pseudo_arg(fn, "tbin", tbin, torch.int32, (c,), dev)
+        if labels is None:
+            labels = torch.empty((n, ho, wo), dtype=torch.int64, device=dev)
+    else:
+        if pred is None:
+            pred = torch.empty((n, ho, wo), dtype=torch.uint8, device=dev)
+        if cbin is None:
+            cbin = torch.empty((n, ho, wo), dtype=torch.uint16, device=dev)
+    for name, t, dt in (("pred", pred, torch.uint8), ("cbin", cbin, torch.uint16), ("labels", labels, torch.int64)):
+        if t is not None:
+            _pseudo_arg(fn, name, t, dt, (n, ho, wo), dev)
+    lib.rtsds_upsample_pseudo(_P(x), _P(pred), _P(cbin), _P(tbin), _P(labels), n, hi, wi, c, ho, wo, sh, sw, bins,
+                              int(ignore_index) if ignore_index is not None else 0, dcode(x), stream())
+    return pred, cbin, labels
+
+
+def ema_step(teacher, student, w, shadow=None):
+    """Mean-teacher update of one flat fp32 buffer (rtsds_ema_step): teacher += w * (student -
+    teacher) as three separately rounded fp32 operations, ``w`` rounded to fp32 here; ``shadow``
+    (bf16, same length) receives the updated values rounded to nearest even in the same pass.
+    All tensors 1-D contiguous on one HIP device.  No host sync.  Returns ``teacher``."""
+    fn = "ema_step"
+    if not (teacher.is_cuda and student.is_cuda and (shadow is None or shadow.is_cuda)):
+        raise RuntimeError(f"rtsds_amd: {fn}: teacher, student and shadow must be HIP tensors; there is no CPU fallback")
+    if teacher.dim() != 1 or teacher.numel() == 0:
+        raise RuntimeError(f"rtsds_amd: {fn}: teacher must be a non-empty flat tensor, got {tuple(teacher.shape)}")
+    _pseudo_arg(fn, "teacher", teacher, torch.float32, teacher.shape, teacher.device)
+    _pseudo_arg(fn, "student", student, torch.float32, teacher.shape, teacher.device)
+    if shadow is not None:
+        _pseudo_arg(fn, "shadow", shadow, torch.bfloat16, teacher.shape, teacher.device)
+    lib.rtsds_ema_step(_P(teacher), _P(student), _P(shadow), teacher.numel(), float(np.float32(w)), stream())
+    return teacher
+
+
+class EmaTable:
+    """The device tables of rtsds_ema_many for (teacher, student) pairs of contiguous fp32 HIP
+    tensors of equal size; ``stale()`` tells (on the host, no sync) whether a tensor has moved."""
+
+    def __init__(self, pairs):
+        fn = "EmaTable"
+        if not pairs:
+            raise RuntimeError(f"rtsds_amd: {fn}: no segments")
+        dev = pairs[0][0].device
+        for t, s in pairs:
+            if not (t.is_cuda and s.is_cuda):
+                raise RuntimeError(f"rtsds_amd: {fn}: segments must be HIP tensors; there is no CPU fallback")
+            _pseudo_arg(fn, "teacher segment", t, torch.float32, t.shape, dev)
+            _pseudo_arg(fn, "student segment", s, torch.float32, t.shape, dev)
+        self.pairs = [(t, s) for t, s in pairs if t.numel() > 0]
+        self.count = len(self.pairs)
+        self.ptrs = self._ptrs()
+        rows = [[p[0] for p in self.ptrs], [p[1] for p in self.ptrs], [t.numel() for t, _ in self.pairs]]
+        self.table = torch.tensor(rows, dtype=torch.int64).to(dev)  # [3, count]: teacher, student, numel
+
+    def _ptrs(self):
+        return [(t.data_ptr(), s.data_ptr()) for t, s in self.pairs]
+
+    def stale(self):
+        return self._ptrs() != self.ptrs
+
+
+def ema_many(table, w):
+    """The ema_step update over every segment of an EmaTable in one launch (rtsds_ema_many)."""
+    if not isinstance(table, EmaTable):
+        raise RuntimeError("rtsds_amd: ema_many: table must be a functional.EmaTable")
+    if table.stale():
+        raise RuntimeError("rtsds_amd: ema_many: a segment has moved since the table was built; rebuild it")
+    if table.count:
+        t = table.table
+        lib.rtsds_ema_many(table.count, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), float(np.float32(w)), stream())
+
+
 _U32 = getattr(torch, "uint32", torch.int32)  # a torch without uint32: int32 holding the same bits
 
 

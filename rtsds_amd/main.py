@@ -181,6 +181,8 @@ def ordered_target_loader(config, train_dl):
 
 
 SELF_TRAINING_KEYS = ("rounds", "epochs", "portion", "portion_step", "cap", "bins", "lr_scale", "scales", "flip")
+SELF_TRAINING_MODES = ("offline", "online")
+ONLINE_SELF_TRAINING_KEYS = ("epochs", "lr_scale", "ema_decay", "threshold")  # with mode: online
 
 
 def self_training_config(config):
@@ -188,8 +190,13 @@ def self_training_config(config):
     st = config.training.get("self_training")
     if st is None:
         raise RuntimeError("rtsds_amd: --self_training needs the config block training.self_training "
-                           f"(keys: {', '.join(SELF_TRAINING_KEYS)}); config.yaml ships it commented out")
-    missing = [k for k in SELF_TRAINING_KEYS if k not in st]
+                           f"(keys: {', '.join(SELF_TRAINING_KEYS)}; or mode: online with "
+                           f"{', '.join(ONLINE_SELF_TRAINING_KEYS)}); config.yaml ships it commented out")
+    mode = st.get("mode", "offline")  # optional: absent = the offline, class-balanced form
+    if mode not in SELF_TRAINING_MODES:
+        raise RuntimeError(f"rtsds_amd: training.self_training.mode must be one of "
+                           f"{', '.join(repr(m) for m in SELF_TRAINING_MODES)}, got {mode!r}")
+    missing = [k for k in (ONLINE_SELF_TRAINING_KEYS if mode == "online" else SELF_TRAINING_KEYS) if k not in st]
     if missing:
         raise RuntimeError(f"rtsds_amd: training.self_training lacks {', '.join(missing)}")
     if st.get("mix") not in (None, "classmix"):  # optional: absent = pseudo-labels alone
@@ -197,15 +204,44 @@ def self_training_config(config):
     return st
 
 
+def self_train_online(config, st, model, optimizer, criterion, init_lr, power, lr_decay_iter, target_dl, validate,
+                      callbacks, source_dl, model_name):
+    """Online (mean-teacher) self-training, ``mode: online``: a second model of the branch's
+    architecture becomes the EMA teacher of ``model`` (ema.EMATeacher, decay ``ema_decay``), the
+    target loader -- in whatever order, shuffled and augmented included -- is wrapped in
+    selftrain.TeacherLoader (labels made per batch by the teacher above the confidence
+    ``threshold``; with ``mix: classmix`` mixed with the labelled ``source_dl``), and ``epochs``
+    epochs of train.train run on it, the teacher updated after every step; lr as in the offline
+    form.  ``validate(epoch)`` validates the student after every epoch.  Returns the teacher."""
+    from . import selftrain
+    from .ema import EMATeacher
+    ignore_index = getattr(criterion, "ignore_index", None)
+    teacher = EMATeacher(model, model_loader(config, False, model_name)[0], optimizer, decay=st["ema_decay"])
+    loader = selftrain.TeacherLoader(target_dl, teacher, threshold=st["threshold"], ignore_index=ignore_index,
+                                     bins=st.get("bins", 1024), source_loader=source_dl if st.get("mix") else None)
+    max_iter = st["epochs"] * len(loader)
+    for epoch in range(st["epochs"]):
+        train(model=model, optimizer=optimizer, criterion=criterion, train_loader=loader, epoch=epoch,
+              init_lr=init_lr * st["lr_scale"], lr_decay_iter=lr_decay_iter, power=power, max_iter=max_iter,
+              callbacks=callbacks, device=config.device)
+        kept = float(loader.kept_sum) / max(1, loader.pixels) if loader.kept_sum is not None else 0.0
+        print(f"Self-training (online) epoch {epoch + 1}: threshold {loader.tbin_value / loader.bins:.4f}, "
+              f"labelled share {kept:.3f}, teacher updates {teacher.updates}")
+        validate(epoch)
+    return teacher
+
+
 def self_train(config, st, model, optimizer, criterion, init_lr, power, lr_decay_iter, num_classes, target_dl,
-               validate, callbacks, source_dl=None):
+               validate, callbacks, source_dl=None, model_name="bisenet"):
     """Class-balanced self-training after the normal run (rtsds_amd.selftrain): per round one
     sweep over the ordered target loader (generate), global per-class thresholds for the round's
     portion (class_thresholds), then ``epochs`` epochs of train.train on the thresholded labels
     with the branch's model, optimizer and criterion; lr = init_lr * lr_scale, poly-decayed over
     all self-training iterations.  ``validate(epoch)`` runs after every epoch.  With the optional
     key ``mix: classmix`` every batch is mixed with the next batch of the labelled ``source_dl``
-    (selftrain.ClassMixLoader) instead of carrying pseudo-labels alone."""
+    (selftrain.ClassMixLoader) instead of carrying pseudo-labels alone.  With ``mode: online``
+    none of that runs: self_train_online (``model_name``: the architecture of ``model``, for the
+    teacher) labels every batch with an EMA teacher instead."""
     from . import selftrain
     ignore_index = getattr(criterion, "ignore_index", None)
     if ignore_index is None:
@@ -213,6 +249,9 @@ def self_train(config, st, model, optimizer, criterion, init_lr, power, lr_decay
     mix = st.get("mix")  # self_training_config: None or "classmix"
     if mix is not None and source_dl is None:
         raise RuntimeError("rtsds_amd: training.self_training.mix: classmix needs the labelled source loader")
+    if st.get("mode") == "online":
+        return self_train_online(config, st, model, optimizer, criterion, init_lr, power, lr_decay_iter, target_dl,
+                                 validate, callbacks, source_dl, model_name)
     loader = ordered_target_loader(config, target_dl)
     max_iter = st["rounds"] * st["epochs"] * len(loader)
     for rnd in range(st["rounds"]):
@@ -245,8 +284,8 @@ def argumnet_parser(argv=None):
     p.add_argument("--wandb", action="store_true")
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--self_training", action="store_true",
-                   help="class-balanced self-training on the target set after the normal run "
-                        "(config block training.self_training)")
+                   help="self-training on the target set after the normal run: class-balanced sweeps, or "
+                        "with mode: online an EMA teacher per batch (config block training.self_training)")
     return p.parse_args(argv)
 
 
@@ -288,7 +327,8 @@ def main(argv=None):
             self_train(config, st, g, g_opt, g_loss, g_hp["gen_init_lr"], g_hp["gen_power"], t["lr_decay_iter"],
                        t["num_classes"], target_dl,
                        lambda epoch: val_GTA5(epoch, g, val_dl, t["num_classes"], config.meta["class_names"],
-                                              callbacks, device=config.device), callbacks, source_dl=gta_dl)
+                                              callbacks, device=config.device), callbacks, source_dl=gta_dl,
+                       model_name=config.model["adversarial_model"]["generator"]["name"])
     else:
         if args.dataset == "gta5":
             train_dl = gta_dl
@@ -308,7 +348,8 @@ def main(argv=None):
                        lambda epoch: val(epoch=epoch, model=model, val_loader=val_dl, num_classes=t["num_classes"],
                                          class_names=config.meta["class_names"], detailed_report=True,
                                          device=config.device, callbacks=callbacks, scales=t.get("eval_scales"),
-                                         flip=bool(t.get("eval_flip", False))), callbacks, source_dl=gta_dl)
+                                         flip=bool(t.get("eval_flip", False))), callbacks, source_dl=gta_dl,
+                       model_name=args.model)
 
 
 if __name__ == "__main__":

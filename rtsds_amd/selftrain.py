@@ -32,6 +32,12 @@ every batch carries the pixels of half of the classes of a labelled source image
 target context, with their true labels (the HIP kernels rtsds_class_presence and
 rtsds_classmix; the pseudo-label map of the target side is formed inside the mix and never
 materialised).
+
+Online form.  ``TeacherLoader(target_loader, teacher, threshold, ignore_index)`` needs none of the
+above: an EMA teacher (ema.EMATeacher) labels every batch on the fly -- its low-resolution head
+through one rtsds_upsample_pseudo launch -- so the target loader may be shuffled and augmented,
+no sweep is run and nothing is stored (config key training.self_training.mode: online; ``mix:
+classmix`` applies to it as well).
 """
 import math
 
@@ -215,14 +221,7 @@ class ClassMixLoader(PseudoLabelLoader):
         self.last_chosen = None
 
     def _next_source(self):
-        for fresh in (False, True):
-            if self._source_iter is None or fresh:
-                self._source_iter = iter(self.source_loader)
-            try:
-                return next(self._source_iter)
-            except StopIteration:
-                continue
-        raise RuntimeError("rtsds_amd: ClassMixLoader: the source loader yielded no batch")
+        return _next_source(self)
 
     @staticmethod
     def draw(n, c, hs, ws, h, w):
@@ -235,7 +234,6 @@ class ClassMixLoader(PseudoLabelLoader):
         return blk
 
     def __iter__(self):
-        from .runtime import compute_dtype
         n, c = 0, self.labels.num_classes
         for inputs, _ in self.loader:
             if n >= len(self.labels):
@@ -246,31 +244,135 @@ class ClassMixLoader(PseudoLabelLoader):
             if tuple(pred.shape) != (nt, h, w):
                 raise RuntimeError(f"rtsds_amd: ClassMixLoader: batch {n} has shape {(nt, h, w)}, "
                                    f"{tuple(pred.shape)} was recorded")
-            simg, slab = self._next_source()
-            if simg.shape[0] < nt or simg.shape[2] < h or simg.shape[3] < w:
-                raise RuntimeError(f"rtsds_amd: ClassMixLoader: the source batch {tuple(simg.shape)} is smaller than "
-                                   f"the target batch {tuple(inputs.shape)} (samples, H or W)")
-            if slab.shape[0] != simg.shape[0] or tuple(slab.shape[-2:]) != tuple(simg.shape[-2:]):
-                raise RuntimeError(f"rtsds_amd: ClassMixLoader: source labels {tuple(slab.shape)} do not match the "
-                                   f"source images {tuple(simg.shape)}")
             dev = pred.device if pred.is_cuda else self.labels.hist.device
-            if not pred.is_cuda:  # store="cpu": back to the device of the sweep
-                pred, cbin = pred.to(dev, non_blocking=True), cbin.to(dev, non_blocking=True)
-            hs, ws = simg.shape[2], simg.shape[3]
-            blk = self.draw(nt, c, hs, ws, h, w).to(dev, non_blocking=True)
-            dtype = compute_dtype()
-            tgt = F.pack_input(inputs.to(dev), dtype)
-            src = F.pack_input(simg[:nt].to(dev), dtype)
-            slab = slab[:nt].to(dev).long().contiguous()
-            chosen = torch.empty(nt, dtype=F._U32, device=dev)
-            mixed, mixed_labels = F.classmix(src, slab, tgt, pred, cbin, self._tbin_on(dev), blk[:, 2:], blk[:, :2],
-                                             self.ignore_index, chosen=chosen)
-            self.last_chosen = chosen
+            mixed, mixed_labels = _mix_batch(self, inputs, pred, cbin, self._tbin_on(dev), c, dev)
             yield mixed, mixed_labels.unsqueeze(1)
             n += 1
         if n != len(self.labels):
             raise RuntimeError(f"rtsds_amd: ClassMixLoader: the loader yielded {n} batches, "
                                f"{len(self.labels)} were recorded")
+
+
+def _next_source(ld):
+    """The next batch of ``ld.source_loader``, restarted with a fresh iter() when exhausted."""
+    for fresh in (False, True):
+        if ld._source_iter is None or fresh:
+            ld._source_iter = iter(ld.source_loader)
+        try:
+            return next(ld._source_iter)
+        except StopIteration:
+            continue
+    raise RuntimeError(f"rtsds_amd: {type(ld).__name__}: the source loader yielded no batch")
+
+
+def _mix_batch(ld, inputs, pred, cbin, tbin, c, dev):
+    """One ClassMix batch, shared by ClassMixLoader (recorded pred / cbin) and TeacherLoader (the
+    teacher's): draws the next source batch of ``ld`` and the per-sample window origins and class
+    permutations (ClassMixLoader.draw), packs both images and runs functional.classmix with the
+    target's ``pred`` / ``cbin`` thresholded by ``tbin``.  Sets ``ld.last_chosen``; returns
+    (mixed inputs, mixed int64 labels [N, H, W])."""
+    from .runtime import compute_dtype
+    who = type(ld).__name__
+    nt, h, w = inputs.shape[0], inputs.shape[2], inputs.shape[3]
+    simg, slab = _next_source(ld)
+    if simg.shape[0] < nt or simg.shape[2] < h or simg.shape[3] < w:
+        raise RuntimeError(f"rtsds_amd: {who}: the source batch {tuple(simg.shape)} is smaller than "
+                           f"the target batch {tuple(inputs.shape)} (samples, H or W)")
+    if slab.shape[0] != simg.shape[0] or tuple(slab.shape[-2:]) != tuple(simg.shape[-2:]):
+        raise RuntimeError(f"rtsds_amd: {who}: source labels {tuple(slab.shape)} do not match the "
+                           f"source images {tuple(simg.shape)}")
+    if not pred.is_cuda:  # store="cpu": back to the device of the sweep
+        pred, cbin = pred.to(dev, non_blocking=True), cbin.to(dev, non_blocking=True)
+    hs, ws = simg.shape[2], simg.shape[3]
+    blk = ClassMixLoader.draw(nt, c, hs, ws, h, w).to(dev, non_blocking=True)
+    dtype = compute_dtype()
+    tgt = F.pack_input(inputs.to(dev), dtype)
+    src = F.pack_input(simg[:nt].to(dev), dtype)
+    slab = slab[:nt].to(dev).long().contiguous()
+    chosen = torch.empty(nt, dtype=F._U32, device=dev)
+    mixed, mixed_labels = F.classmix(src, slab, tgt, pred, cbin, tbin, blk[:, 2:], blk[:, :2], ld.ignore_index,
+                                     chosen=chosen)
+    ld.last_chosen = chosen
+    return mixed, mixed_labels
+
+
+class TeacherLoader:
+    """Online (mean-teacher) pseudo-labels: iterates ``loader`` -- which may be shuffled and
+    augmented, its own labels are ignored -- and labels every batch on the fly with ``teacher``
+    (an ema.EMATeacher).  Per batch, under no_grad, the teacher's low-resolution main head
+    (``teacher.model.forward_lowres(x, main_only=True)``) goes through ONE
+    functional.upsample_pseudo launch to the input size, with the uniform threshold
+    ``tbin = ceil(threshold * bins)`` for every class (a pixel is kept iff its confidence bin
+    reaches it, i.e. conf >= tbin / bins).  Nothing is stored between batches and no sweep over
+    the target set is needed.
+
+    Without ``source_loader`` it yields ``(inputs, labels.unsqueeze(1))``, labels int64 with
+    ``ignore_index`` -- the format train.train expects.  With ``source_loader`` (ClassMix) the
+    kernel writes pred / cbin instead and the batch is mixed exactly as ClassMixLoader does (same
+    draws from torch's default CPU generator, same functional.classmix call; ``last_chosen``).
+
+    Update timing.  When iteration resumes after a ``yield`` the consumer has taken the
+    student's step on that batch, so ``teacher.update()`` is called there: one update per yielded
+    batch.  A consumer that abandons the iterator early (break) skips the update of its last
+    batch.
+
+    ``len()`` is the loader's.  ``last_kept`` is a device int64 scalar: the pixels of the last
+    batch that were not ignored (for logging; reading it synchronises).  ``kept_sum`` (device
+    int64) and ``pixels`` (host int) accumulate the same over the current iteration."""
+
+    def __init__(self, loader, teacher, threshold=0.968, ignore_index=None, bins=1024, source_loader=None):
+        if ignore_index is None:
+            raise RuntimeError("rtsds_amd: TeacherLoader: ignore_index is required")
+        bins = int(bins)
+        if bins < 16 or bins > 1024 or bins & (bins - 1):
+            raise RuntimeError(f"rtsds_amd: TeacherLoader: bins must be a power of two in [16, 1024], got {bins}")
+        if not 0.0 <= float(threshold) <= 1.0:
+            raise RuntimeError(f"rtsds_amd: TeacherLoader: threshold must be in [0, 1], got {threshold}")
+        self.loader, self.teacher, self.ignore_index, self.bins = loader, teacher, int(ignore_index), bins
+        self.threshold = float(threshold)
+        self.tbin_value = int(math.ceil(self.threshold * bins))
+        self.source_loader = source_loader
+        self._source_iter = None
+        self._tbin_dev = {}
+        self.last_chosen = None
+        self.last_kept = None
+        self.kept_sum, self.pixels = None, 0
+
+    def __len__(self):
+        return len(self.loader)
+
+    def _tbin_on(self, device, c):
+        if (device, c) not in self._tbin_dev:
+            self._tbin_dev[(device, c)] = torch.full((c,), self.tbin_value, dtype=torch.int32, device=device)
+        return self._tbin_dev[(device, c)]
+
+    def label(self, inputs):
+        """(low, geo, tbin) of one batch: the teacher's low-resolution head, the geometry of its
+        resize to the input size, and the thresholds on its device."""
+        model = self.teacher.model
+        if model.training:
+            model.eval()
+        dev = next(model.parameters()).device
+        with torch.no_grad():
+            (low, _), = model.forward_lowres(inputs.to(dev), main_only=True)
+        return low, F.upsample_geometry(low, size=tuple(inputs.shape[-2:])), self._tbin_on(low.device, low.shape[1])
+
+    def __iter__(self):
+        self.kept_sum, self.pixels = None, 0
+        for inputs, _ in self.loader:
+            low, geo, tbin = self.label(inputs)
+            with torch.no_grad():
+                if self.source_loader is None:
+                    _, _, labels = F.upsample_pseudo(low, geo, self.bins, tbin=tbin, ignore_index=self.ignore_index)
+                    out = inputs
+                else:
+                    pred, cbin, _ = F.upsample_pseudo(low, geo, self.bins)
+                    out, labels = _mix_batch(self, inputs, pred, cbin, tbin, low.shape[1], low.device)
+                self.last_kept = (labels != self.ignore_index).sum()
+                self.kept_sum = self.last_kept if self.kept_sum is None else self.kept_sum + self.last_kept
+                self.pixels += labels.numel()
+            yield out, labels.unsqueeze(1)
+            self.teacher.update()  # the student's step on this batch has been taken
 
 
 def kept_fraction(labels, tbin):
@@ -284,4 +386,4 @@ def kept_fraction(labels, tbin):
     return np.where(total > 0, kept / np.maximum(total, 1), np.nan)
 
 
-__all__ = ["class_thresholds", "generate", "PseudoLabels", "PseudoLabelLoader", "ClassMixLoader", "kept_fraction"]
+__all__ = ["class_thresholds", "generate", "PseudoLabels", "PseudoLabelLoader", "ClassMixLoader", "TeacherLoader", "kept_fraction"]
