@@ -150,6 +150,23 @@ int rtsds_conv2d_wgrad_deferred(const rtsds_conv_desc* d, const void* x, const v
                                 float* dbias, int accumulate, void* ws, size_t ws_bytes,
                                 rtsds_split_reduce_desc* pending, void* stream);
 int rtsds_split_reduce_many(int n, const rtsds_split_reduce_desc* descs, void* stream);
+/* Weight gradient of a 3-channel stride-2 image conv (bf16, c = 3, k = 64, 7x7 or 3x3, even w,
+ * odd pw; no bias gradient) whose output feeds a train-mode BatchNorm, with that BatchNorm's
+ * backward apply fused in: dx = A*g + B*(bn_x - mean) + C (g = bn_dy masked by the activation,
+ * rounded to bf16 exactly as rtsds_bn_bwd stores it) is formed per output tile on the way into
+ * the MFMA and never written.  bn_dy: the BatchNorm's incoming gradient, bn_x: its input (this
+ * conv's output), both NHWC [n][ho][wo][64]; coef: rtsds_bn_bwd_coef's rows.  x: the image
+ * (RTSDS_INPUT_PADDED in accumulate: already the 4-channel padded copy).  One fp32 slab per
+ * workgroup in ws, summed in workgroup order by the split reduce (deterministic); the deferred
+ * form leaves that reduction to rtsds_split_reduce_many.  workspace == 0 / RTSDS_ERR_UNSUPPORTED:
+ * geometry not taken, nothing launched -- use rtsds_bn_bwd + rtsds_conv2d_wgrad.              */
+size_t rtsds_imgconv_bn_wgrad_workspace(const rtsds_conv_desc* d);
+int rtsds_imgconv_bn_wgrad(const rtsds_conv_desc* d, const void* x, const void* bn_dy, const void* bn_x,
+                           const float* coef, int act, float* dw, int accumulate, void* ws, size_t ws_bytes,
+                           void* stream);
+int rtsds_imgconv_bn_wgrad_deferred(const rtsds_conv_desc* d, const void* x, const void* bn_dy, const void* bn_x,
+                                    const float* coef, int act, float* dw, int accumulate, void* ws,
+                                    size_t ws_bytes, rtsds_split_reduce_desc* pending, void* stream);
 
 /* ---------------------------------------------------------------- batch norm (train/eval)
  * Replaces nn.BatchNorm2d at build_bisenet.py:13,39; torchvision ResNet bn*; deeplabv2.py:14-27,
@@ -198,6 +215,15 @@ int rtsds_bn_bwd_ld(const void* dy, long ldy, const void* x, const void* y, void
                     float* dgamma, float* dbeta, long rows, int c, const float* gamma,
                     const float* beta, const float* save_mean, const float* save_invstd, int training,
                     int act, int accumulate_params, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* rtsds_bn_bwd's statistics and finalize passes only (no residual, act NONE/RELU/LEAKY, mask
+ * from x): dgamma / dbeta exactly as rtsds_bn_bwd, and the coefficient rows of its apply pass,
+ * coef = [A | B | C | mean | scale | shift] x c floats (16-byte aligned, caller-owned), with
+ * dx = A*g + B*(x - mean) + C and g = dy * act'(x*scale + shift) -- for a consumer that applies
+ * them itself (rtsds_imgconv_bn_wgrad).  Workspace as rtsds_bn_bwd.                        */
+int rtsds_bn_bwd_coef(const void* dy, const void* x, float* dgamma, float* dbeta, float* coef, long rows, int c,
+                      const float* gamma, const float* beta, const float* save_mean, const float* save_invstd,
+                      int training, int act, int accumulate_params, int dtype, void* ws, size_t ws_bytes,
+                      void* stream);
 /* rtsds_bn_bwd without its statistics pass: part / nrb = the channel-major (sum g,
  * sum g (x - mean)) partials of rtsds_conv2d_dgrad_bnstats (bf16, c % 8 == 0, no residual).  */
 int rtsds_bn_bwd_part(const void* dy, const void* x, void* dx, float* dgamma, float* dbeta, long rows, int c,
@@ -610,7 +636,7 @@ int rtsds_pooled_mlp_fwd(const void* p, const void* w1, const float* b1, const v
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 16
+#define RTSDS_ABI_VERSION 17
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSDS_LIB: alternative in-tree build of the same ABI (kernel-variant A/B measurements)
 DEFAULT_LIB_PATH = os.path.join(_HERE, "librtsds_hip.so")
-ABI_VERSION = 16  # include/rtsds_hip.h RTSDS_ABI_VERSION
+ABI_VERSION = 17  # include/rtsds_hip.h RTSDS_ABI_VERSION
 LIB_PATH = os.environ.get("RTSDS_LIB") or DEFAULT_LIB_PATH
 
 F32, BF16 = 0, 1
@@ -62,7 +62,12 @@ SIGNATURES = {
     "rtsds_conv2d_wgrad_deferred": (c_int, [ctypes.POINTER(ConvDesc), P, P, P, P, c_int, P, c_size_t,
                                             ctypes.POINTER(SplitReduceDesc), P]),
     "rtsds_split_reduce_many": (c_int, [c_int, ctypes.POINTER(SplitReduceDesc), P]),
+    "rtsds_imgconv_bn_wgrad_workspace": (c_size_t, [ctypes.POINTER(ConvDesc)]),
+    "rtsds_imgconv_bn_wgrad": (c_int, [ctypes.POINTER(ConvDesc), P, P, P, P, c_int, P, c_int, P, c_size_t, P]),
+    "rtsds_imgconv_bn_wgrad_deferred": (c_int, [ctypes.POINTER(ConvDesc), P, P, P, P, c_int, P, c_int, P, c_size_t,
+                                                ctypes.POINTER(SplitReduceDesc), P]),
     "rtsds_bn_workspace": (c_size_t, [c_long, c_int]),
+    "rtsds_bn_bwd_coef": (c_int, [P, P, P, P, P, c_long, c_int, P, P, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     "rtsds_bn_fwd": (c_int, [P, P, P, c_long, c_int, P, P, P, P, P, P, P, c_float, c_float, c_int,
                              c_int, P, c_int, c_int, P, c_size_t, P]),
     "rtsds_bn_fwd_ld": (c_int, [P, P, P, c_long, c_long, c_int, P, P, P, P, P, P, P, c_float, c_float, c_int,

@@ -6,7 +6,7 @@
 // large-mean conv outputs (the reference feeds 0-255-scale normalised images,
 // main.py:69-72) do not cancel catastrophically.  Three launches per direction:
 // partial statistics (grid over row chunks) -> per-channel finalize -> vectorised apply.
-#include "common.h"
+#include "bn_dev.h"
 #include <type_traits>
 #include <algorithm>
 
@@ -41,31 +41,6 @@ template <int VEC> struct BnTile : BnLayout<VEC> {
   RT_DEV long row0() const { return (long)blockIdx.x * this->rpi + rg; }
   RT_DEV long step() const { return (long)gridDim.x * this->rpi; }
 };
-
-// VEC is either the 16-B vector width (dispatched only when c % VEC == 0, so an active thread's
-// channel vector is always complete) or 1.
-template <typename T, int VEC>
-RT_DEV void load_vec(const T* p, float* v, int cvalid) {
-  static_assert(VEC == 1 || VEC == VecT<T>::N, "VEC");
-  if constexpr (VEC == VecT<T>::N) {
-    typename VecT<T>::v16 t = *(const typename VecT<T>::v16*)p;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) v[j] = to_f(t[j]);
-  } else {
-    v[0] = cvalid > 0 ? to_f(p[0]) : 0.f;
-  }
-}
-template <typename T, int VEC>
-RT_DEV void store_vec(T* p, const float* v, int cvalid) {
-  if constexpr (VEC == VecT<T>::N) {
-    typename VecT<T>::v16 t;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) t[j] = from_f<T>(v[j]);
-    *(typename VecT<T>::v16*)p = t;
-  } else {
-    if (cvalid > 0) p[0] = from_f<T>(v[0]);
-  }
-}
 
 // scale/shift of y = x*scale + shift.  Written with explicit fma so the backward can
 // recompute exactly the forward's pre-activation (ReLU mask without reading y).
@@ -226,13 +201,6 @@ RT_DEV float act_f(float v, int act) {
   if (act == RTSDS_ACT_SIGMOID) return 1.f / (1.f + expf(-v));
   return v;
 }
-RT_DEV float act_grad(float y, int act) {
-  if (act == RTSDS_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-  if (act == RTSDS_ACT_LEAKY) return y > 0.f ? 1.f : 0.2f;
-  if (act == RTSDS_ACT_SIGMOID) return y * (1.f - y);
-  return 1.f;
-}
-
 // Per-channel coefficients for a thread's VEC channels.  Coefficient arrays live in the
 // 256-B aligned workspace and VEC > 1 only when c % VEC == 0, so VEC % 4 == 0 loads are 16 B.
 template <int VEC>
@@ -329,20 +297,6 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const T* __restrict__ x, 
   }
 }
 
-// g *= act'(.): the activation derivative from the saved output's values yv (HAS_Y), or -- when y
-// is not kept (no residual, monotone activation with act'(v) determined by sign(v)) -- from the
-// sign of the recomputed pre-activation x*scale+shift, which is bit-identical to the forward's.
-// The one mask of the statistics loop and the apply passes.
-template <int VEC, bool HAS_Y>
-RT_DEV void bn_mask(float* g, const float* yv, const float* xv, const float* sc, const float* sh, int act) {
-  if (!act) return;
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    if constexpr (HAS_Y) g[j] *= act_grad(yv[j], act);
-    else g[j] = fmaf(xv[j], sc[j], sh[j]) > 0.f ? g[j] : (act == RTSDS_ACT_LEAKY ? 0.2f * g[j] : 0.f);
-  }
-}
-
 // Where the backward passes read g (before the activation mask): the stored dY, or -- for a
 // BatchNorm + ReLU feeding a 3x3 stride-2 max pool (the ResNet stem, fused forward in
 // bn_relu_pool_fwd_kernel) -- a gather of the pooled gradient: input pixel r of channel vector
@@ -392,11 +346,6 @@ struct GradPool {
   }
 };
 
-// A thread's per-channel backward coefficients: dx = a*g + b*(x - mu) + k, and the forward's
-// sc / sh for the mask recomputed from x.
-template <int VEC> struct BnDx {
-  float a[VEC], b[VEC], k[VEC], mu[VEC], sc[VEC], sh[VEC];
-};
 template <int VEC>
 RT_DEV void bn_bwd_coef(int ch0, int c, const float* gamma, const float* beta, const float* mean, const float* sinv,
                         BnDx<VEC>& k) {
@@ -535,21 +484,6 @@ RT_DEV void bn_bwd_coef_rows(const BnBwdOps& o, float sg, float sgx, int ch, int
   bn_coef(o.g, o.bt, o.mu, o.inv, coef[4 * c + ch], coef[5 * c + ch]);
 }
 
-// The backward apply's row pieces: dx = a*g + b*(x - mu) + k, dres = g.
-// The mask of one row; y: the row of the stored output (null: recomputed from x).
-template <typename T, int VEC>
-RT_DEV void bn_row_mask(float* g, const T* __restrict__ y, const float* xv, const BnDx<VEC>& k, int act, int cvalid) {
-  if (!act) return;
-  if (y) {
-    float yv[VEC];
-    load_vec<T, VEC>(y, yv, cvalid);
-    bn_mask<VEC, true>(g, yv, xv, k.sc, k.sh, act);
-  } else {
-    bn_mask<VEC, false>(g, nullptr, xv, k.sc, k.sh, act);
-  }
-}
-template <int VEC>
-RT_DEV float bn_bwd_dx(const BnDx<VEC>& k, int j, float g, float x) { return fmaf(k.a[j], g, fmaf(k.b[j], x - k.mu[j], k.k[j])); }
 // dx (in place of xv) and dres of one row from its masked g and x; off = r * c + ch0
 template <typename T, int VEC>
 RT_DEV void bn_bwd_row_store(T* __restrict__ dx, T* __restrict__ dres, long off, const BnDx<VEC>& k, int cvalid, const float* g,
@@ -881,6 +815,7 @@ struct BnArgs {
   float momentum = 0.f, eps = 0.f;
   const float* pre = nullptr;  // partial statistics a conv epilogue already produced, pre_nrb per channel
   int pre_nrb = 0;
+  bool coef_only = false;  // backward: statistics + finalize only, w.coef is the caller's buffer
   BnWs w = {nullptr, nullptr};
   hipStream_t st = nullptr;
   BnArgs(long rows_, int c_, void* ws, void* stream)
@@ -979,7 +914,9 @@ static void bn_bwd_launch(const GS& gs, const BnArgs& a) {
   // g = dy * relu'(y) as dres, and the apply pass reads g and x (not dy, y) -- one full read
   // less; g is exactly dy or 0, so the arithmetic is unchanged
   const bool g_out = !a.pre && y && act == RTSDS_ACT_RELU && dres && dx && GS::kDirect;
-  if (!a.pre && rb == 1 && GS::kDirect && !g_out) {  // one row block: the three passes in one launch
+  // (coef_only: the one-launch form keeps its coefficients in LDS; the separate passes give the
+  // same dgamma / dbeta bit for bit)
+  if (!a.pre && rb == 1 && GS::kDirect && !g_out && !a.coef_only) {  // one row block: the three passes in one launch
     with_bool(y && act, [&](auto hy) {
       with_act(act, [&](auto av) {
         hipLaunchKernelGGL((bn_bwd_tiny_kernel<T, VEC, decltype(hy)::value, GS, decltype(av)::value>), bn_grid<VEC>(1, c), dim3(256),
@@ -1055,6 +992,22 @@ extern "C" int rtsds_bn_bwd_ld(const void* dy, long ldy, const void* x, const vo
   BnArgs a(rows, c, ws, stream);
   bn_bwd_args(a, x, dx, dgamma, dbeta, gamma, beta, save_mean, save_invstd, training, act, accumulate_params);
   a.dy = dy, a.ldy = ldy, a.ykept = y, a.dres = dres;
+  if (int rc = bn_dispatch(dtype, c, [&](auto k) { bn_bwd_launch<typename decltype(k)::T, decltype(k)::VEC>(a); })) return rc;
+  RET_LAUNCH();
+}
+// Statistics + finalize only: dgamma / dbeta as rtsds_bn_bwd, and the apply pass's coefficient rows
+// [A | B | C | mean | scale | shift] x c into the caller's coef instead of the workspace -- for a
+// consumer that applies dx = A*g + B*(x - mean) + C itself (rtsds_imgconv_bn_wgrad).
+extern "C" int rtsds_bn_bwd_coef(const void* dy, const void* x, float* dgamma, float* dbeta, float* coef, long rows, int c,
+                                 const float* gamma, const float* beta, const float* save_mean, const float* save_invstd,
+                                 int training, int act, int accumulate_params, int dtype, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  if (rows <= 0 || c <= 0 || !coef || ((size_t)coef & 15)) return RTSDS_ERR_SHAPE;
+  if (ws_bytes < rtsds_bn_workspace(rows, c)) return RTSDS_ERR_WORKSPACE;
+  if (!(act == RTSDS_ACT_NONE || act == RTSDS_ACT_RELU || act == RTSDS_ACT_LEAKY)) return RTSDS_ERR_UNSUPPORTED;
+  BnArgs a(rows, c, ws, stream);
+  bn_bwd_args(a, x, nullptr, dgamma, dbeta, gamma, beta, save_mean, save_invstd, training, act, accumulate_params);
+  a.dy = dy, a.w.coef = coef, a.coef_only = true;
   if (int rc = bn_dispatch(dtype, c, [&](auto k) { bn_bwd_launch<typename decltype(k)::T, decltype(k)::VEC>(a); })) return rc;
   RET_LAUNCH();
 }

@@ -1,7 +1,9 @@
 // Direct MFMA convolution for the 3-channel stride-2 image convs: the ResNet stem 7x7 s2 p3
 // (build_contextpath.py via torchvision conv1; deeplabv2.py:106) and the spatial path's first
 // ConvBlock 3x3 s2 p1 (build_bisenet.py:9-14, 21), 64 output channels, forward only (the image
-// needs no data gradient; the weight gradient stays on the implicit GEMM's superpixel path).
+// needs no data gradient; the weight gradient stays on the implicit GEMM's superpixel path, or --
+// when the conv feeds a train-mode BatchNorm -- runs here with that BatchNorm's backward apply
+// fused in: imgconv_bn_wgrad_kernel, below).
 //
 // These convs are epilogue-bound, not MFMA-bound: 2 x 3.6-13 GFLOP against a 134 MB output at bs 8
 // 1024x512.  As an implicit GEMM each 128-row tile ran 2-7 K-steps behind a register-staged
@@ -26,6 +28,7 @@
 // Inference also has a variant with the stem's 3x3 stride-2 max pool in the epilogue
 // (imgconv_pool_kernel): the full-resolution activation is never written.
 #include "conv_host.h"
+#include "bn_dev.h"
 
 template <int N> RT_DEV void wait_vmcnt_img() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // Sum over the 16 lanes of a DPP row (every lane of the row ends with the total): quad_perm
@@ -619,4 +622,312 @@ static constexpr auto kImgPoolPH = 2;
   const int grid = (a.tiles + a.per - 1) / a.per;
   void* args[] = {&a};
   (void)hipLaunchKernel(k, dim3(grid), dim3(256), args, 0, st);
+}
+
+// ---- weight gradient with the following BatchNorm's backward apply fused in -----------------
+// dW[co][r][s][ch] = sum_px dx[px][co] X[px + tap (r, s)][ch] where dx is the BatchNorm's data
+// gradient, dx = A*g + B*(x - mean) + C (g = dy masked by the activation).  The image needs no
+// data gradient, so dx had exactly one reader -- this sum -- and bn_bwd_apply wrote 134 MB per
+// layer at bs 8 1024x512 for the GEMM to read back.  Here a workgroup walks the forward kernel's
+// 4 x 64-pixel tiles; per tile
+//  * every thread loads 8 x 16 B of g and of x (pixel tid / 8 + 32 u, channels 8 (tid % 8) ..),
+//    one tile ahead of its use, forms dx with bn.hip's own expressions (bn_dev.h), rounds it to
+//    bf16 as the apply pass stores it and writes it to LDS pixel-major (128-B rows; the 32-B
+//    chunk c of pixel q at slot c ^ ((q >> 1) & 3): the 8 pixels a 32-lane half reads cover all
+//    64 banks); pixels outside the output get dx = 0;
+//  * the input rows are staged as superpixels by LDS-DMA exactly as the forward stages them
+//    (double-buffered, one tile ahead);
+//  * K = the tile's 256 pixels in 8 MFMA steps of 32; both operands are pixel-major in LDS and
+//    read with ds_read_b64_tr_b16 (lane 16 g + 4 q + p: pixel 4 g + q, then + 16; 8-byte run p of
+//    its 32-byte row -- EXEC is all ones here, every address 8-byte aligned).  An image fragment
+//    is the 16 elements (two superpixels) at superpixel column + 2 j of row tap r: N block (r, j)
+//    holds taps s = 4 j - 1 .. 4 j + 2; wave (wm, wn) keeps 4 / WM blocks of 16 output channels x
+//    NB / WN of the N blocks in fp32 accumulators across its whole run of tiles.
+// Each workgroup writes one slab already in dW's [64][kh][kw][3] order (the padding channel and
+// the taps outside the kernel are simply not stored: the superpixel unpack is the store's index
+// map), and the weight-gradient split reduce sums the slabs in workgroup order into dw --
+// deterministic, no atomics, immediate or deferred.
+struct ImgWgArgs {
+  const bf16* x4;     // [n][h][w][4], channel 3 zero
+  const bf16* g;      // [n][ho][wo][64] the BatchNorm's incoming gradient (before the mask)
+  const bf16* xb;     // [n][ho][wo][64] the BatchNorm's input
+  const float* coef;  // [A | B | C | mean | scale | shift] x 64
+  float* slab;        // [workgroups][64 * kh * kw * 3]
+  int n, h, w, ho, wo, ph, pw, act;
+  int tiles, per;
+};
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4_img;
+RT_DEV u32x4_img img_load16(rsrc_t r, int off) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
+#else
+  return u32x4_img{};
+#endif
+}
+RT_DEV bf16x8 img_tr_frag(const unsigned char* p0, const unsigned char* p1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p0);
+  const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p1);
+  typedef __attribute__((ext_vector_type(8))) short s16x8;
+  const s16x8 r = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
+  return __builtin_bit_cast(bf16x8, r);
+#else
+  return bf16x8{};
+#endif
+}
+
+template <int KH, int KW, int WN, int ACT>
+__global__ void __launch_bounds__(256, 2) imgconv_bn_wgrad_kernel(const ImgWgArgs P) {
+  constexpr int KWP = (KW + 1) / 2, NJ = KWP / 2, NB = KH * NJ;  // N blocks of 16 (two superpixel slots)
+  static_assert(KWP % 2 == 0 && NB % WN == 0 && 4 % WN == 0, "wave layout");
+  constexpr int WM = 4 / WN, CB = 4 / WM, NBW = NB / WN;
+  constexpr int NR = 2 * kTH + KH - 2, NC = kTW + KWP - 1, NP = NR * NC;
+  constexpr int NI = (NP + 63) / 64, NIW = (NI + 3) / 4, A_BYTES = NI * 1024;
+  constexpr int DX_BYTES = kTH * kTW * kCo * 2, CF_BYTES = 6 * kCo * 4;
+  constexpr int W_EL = kCo * KH * KW * 3;
+  constexpr int U = kTH * kTW / 32;          // pixels per thread and tile
+  // (separate arrays, and the image buffer of a tile fixed at compile time below: a transposed
+  // read then provably does not alias the LDS-DMA in flight into the other image buffer, and the
+  // compiler does not make it wait for that DMA)
+  __shared__ __attribute__((aligned(16))) float cf[CF_BYTES / 4];
+  __shared__ __attribute__((aligned(16))) unsigned char dxs[DX_BYTES];
+  __shared__ __attribute__((aligned(16))) unsigned char abuf0[A_BYTES];
+  __shared__ __attribute__((aligned(16))) unsigned char abuf1[A_BYTES];
+
+  // (wave: uniform, so the per-wave tile pieces and N blocks are scalar)
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int bid;
+  {  // XCD-aware bijective remap, as the forward
+    const int nwg = gridDim.x, b = blockIdx.x;
+    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+  }
+  const int t0 = bid * P.per, t1 = min(P.tiles, t0 + P.per);
+  const int tw_n = (P.wo + kTW - 1) / kTW, th_n = (P.ho + kTH - 1) / kTH;
+  const int spw = P.w >> 1, pwp = (P.pw + 1) >> 1;
+  const int ybytes = P.n * P.ho * P.wo * kCo * 2;
+  const rsrc_t rx = make_rsrc(P.x4, P.n * P.h * P.w * 8);
+  const rsrc_t rg = make_rsrc(P.g, ybytes), rb = make_rsrc(P.xb, ybytes);
+  auto tile_xy = [&](int t, int& img, int& oh0, int& ow0) {
+    img = t / (th_n * tw_n);
+    const int rem = t - img * th_n * tw_n, trow = rem / tw_n;
+    oh0 = trow * kTH;
+    ow0 = (rem - trow * tw_n) * kTW;
+  };
+  // input rows of tile t (zero outside the image) -> image buffer dst: imgconv_fwd_kernel's staging
+  auto issue = [&](int t, unsigned char* dst) {
+    int img, oh0, ow0;
+    tile_xy(t, img, oh0, ow0);
+    const int ih0 = 2 * oh0 - P.ph, j0 = ow0 - pwp;
+#pragma unroll
+    for (int i = 0; i < NIW; ++i) {
+      const int ins = wave + 4 * i;
+      if (ins < NI) {
+        const int piece = ins * 64 + lane;
+        const int row = piece / NC, col = piece - row * NC;
+        const int ih = ih0 + row, j = j0 + col;
+        const bool ok = piece < NP && (unsigned)ih < (unsigned)P.h && (unsigned)j < (unsigned)spw;
+        buf_lds16(rx, dst + ins * 1024, ok ? ((img * P.h + ih) * spw + j) * 16 : (int)0x80000000, 0);
+      }
+    }
+  };
+  // this thread's 8 channels of pixels (tid >> 3) + 32 u of tile t: g and x, 16 B each (an offset
+  // past num_records reads zeros; such pixels are zeroed again after the BatchNorm expression)
+  const int cg = tid & 7, pq = tid >> 3;
+  u32x4_img gv[U], xv[U];
+  auto fetch = [&](int t) {
+    int img, oh0, ow0;
+    tile_xy(t, img, oh0, ow0);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int px = pq + 32 * u, oh = oh0 + (px >> 6), ow = ow0 + (px & 63);
+      const int off = (oh < P.ho && ow < P.wo) ? (((img * P.ho + oh) * P.wo + ow) * kCo + 8 * cg) * 2 : (int)0x80000000;
+      gv[u] = img_load16(rg, off);
+      xv[u] = img_load16(rb, off);
+    }
+  };
+
+  for (int i = tid; i < 6 * kCo; i += 256) cf[i] = P.coef[i];
+  issue(t0, abuf0);
+  fetch(t0);
+
+  // per-lane bases of the transposed reads: pixel rows L and L + 16 of a K step
+  const int g4 = lane >> 4, L = 4 * g4 + ((lane >> 2) & 3), p8 = (lane & 3) * 8;
+  const int wm = wave / WN, wn = wave % WN;
+  const int aoff = L * 16 + p8;
+  const unsigned char* dbase[CB];
+#pragma unroll
+  for (int cb = 0; cb < CB; ++cb) dbase[cb] = dxs + L * 128 + (((wm * CB + cb) ^ ((L >> 1) & 3)) << 5) + p8;
+  f32x4 acc[CB][NBW];
+#pragma unroll
+  for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+    for (int j = 0; j < NBW; ++j) acc[cb][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int act = ACT >= 0 ? ACT : P.act;
+
+  // tile t, its image rows in buffer B (0 / 1: even / odd tiles of the run)
+  auto tile = [&](int t, auto bc) {
+    constexpr int B = decltype(bc)::value;
+    int img, oh0, ow0;
+    tile_xy(t, img, oh0, ow0);
+    // tile t's g, x and image rows have landed (this wave's); every wave is done reading dx of
+    // tile t - 1
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    {
+      BnDx<8> k;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const f32x4 va = *(const f32x4*)(cf + 8 * cg + 4 * q), vb = *(const f32x4*)(cf + kCo + 8 * cg + 4 * q);
+        const f32x4 vk = *(const f32x4*)(cf + 2 * kCo + 8 * cg + 4 * q), vm = *(const f32x4*)(cf + 3 * kCo + 8 * cg + 4 * q);
+        const f32x4 vs = *(const f32x4*)(cf + 4 * kCo + 8 * cg + 4 * q), vh = *(const f32x4*)(cf + 5 * kCo + 8 * cg + 4 * q);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          k.a[4 * q + e] = va[e]; k.b[4 * q + e] = vb[e]; k.k[4 * q + e] = vk[e];
+          k.mu[4 * q + e] = vm[e]; k.sc[4 * q + e] = vs[e]; k.sh[4 * q + e] = vh[e];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int px = pq + 32 * u;
+        const bool ok = oh0 + (px >> 6) < P.ho && ow0 + (px & 63) < P.wo;
+        const bf16x8 gb = __builtin_bit_cast(bf16x8, gv[u]), xb = __builtin_bit_cast(bf16x8, xv[u]);
+        float gf[8], xf[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { gf[j] = to_f(gb[j]); xf[j] = to_f(xb[j]); }
+        bn_row_mask<bf16, 8>(gf, (const bf16*)nullptr, xf, k, act, 8);
+        bf16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = ok ? from_f<bf16>(bn_bwd_dx<8>(k, j, gf[j], xf[j])) : (bf16)0.f;
+        *(bf16x8*)(dxs + px * 128 + ((((cg >> 1) ^ ((px >> 1) & 3))) << 5) + (cg & 1) * 16) = o;
+        __builtin_amdgcn_sched_barrier(0);  // pixel by pixel: one pixel's fp32 values live at a time
+      }
+    }
+    __syncthreads();  // dx of tile t complete; all waves' image rows of tile t landed
+    if (t + 1 < t1) {
+      issue(t + 1, B ? abuf0 : abuf1);
+      fetch(t + 1);
+    }
+    const unsigned char* ab = (B ? abuf1 : abuf0) + aoff;
+#pragma unroll
+    for (int kk = 0; kk < 2 * kTH; ++kk) {  // 32 pixels: tile row kk >> 1, columns 32 (kk & 1) ..
+      bf16x8 fd[CB], fa[NBW];
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb) fd[cb] = img_tr_frag(dbase[cb] + 32 * kk * 128, dbase[cb] + (32 * kk + 16) * 128);
+#pragma unroll
+      for (int j = 0; j < NBW; ++j) {
+        const int nb = wn * NBW + j, r = nb / NJ, jj = nb - r * NJ;
+        const unsigned char* a0 = ab + ((2 * (kk >> 1) + r) * NC + 32 * (kk & 1) + 2 * jj) * 16;
+        fa[j] = img_tr_frag(a0, a0 + 256);
+      }
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+        for (int j = 0; j < NBW; ++j) acc[cb][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[j], fd[cb], acc[cb][j], 0, 0, 0);
+    }
+  };
+  for (int t = t0; t < t1; t += 2) {
+    tile(t, std::integral_constant<int, 0>());
+    if (t + 1 < t1) tile(t + 1, std::integral_constant<int, 1>());
+  }
+  // acc[cb][j][e] = dW'[co = 16 (wm CB + cb) + (lane & 15)][row tap r][slot 2 jj + (g4 >> 1)][4 (g4 & 1) + e]:
+  // tap s = 2 slot - 1 + (g4 & 1), channel e (e = 3: the padding channel)
+  float* out = P.slab + (long)bid * W_EL;
+#pragma unroll
+  for (int cb = 0; cb < CB; ++cb) {
+    const int co = 16 * (wm * CB + cb) + (lane & 15);
+#pragma unroll
+    for (int j = 0; j < NBW; ++j) {
+      const int nb = wn * NBW + j, r = nb / NJ, jj = nb - r * NJ;
+      const int s = 2 * (2 * jj + (g4 >> 1)) - 1 + (g4 & 1);
+      if (s >= 0 && s < KW) {
+        float* o = out + ((co * KH + r) * KW + s) * 3;
+        o[0] = acc[cb][j][0];
+        o[1] = acc[cb][j][1];
+        o[2] = acc[cb][j][2];
+      }
+    }
+  }
+}
+
+template <int ACT>
+static const void* img_wg_kernel_act(int kh) {
+  return kh == 7 ? (const void*)imgconv_bn_wgrad_kernel<7, 7, 2, ACT> : (const void*)imgconv_bn_wgrad_kernel<3, 3, 1, ACT>;
+}
+static const void* img_wg_kernel(int kh, int act) {
+  const int v = img_act_variant(act);
+  return v == 0 ? img_wg_kernel_act<0>(kh) : v == 1 ? img_wg_kernel_act<1>(kh) : img_wg_kernel_act<-1>(kh);
+}
+// Persistent grid as img_grid: one contiguous run of tiles per resident workgroup slot; every
+// workgroup gets >= 1 tile and writes one slab.
+static void img_wg_grid(const rtsds_conv_desc* d, int& grid, int& per) {
+  static int occ[2] = {0, 0}, cus = 0;
+  const int v = d->kh == 7;
+  if (!occ[v] && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ[v], img_wg_kernel(d->kh, RTSDS_ACT_RELU), 256, 0) != hipSuccess ||
+                  occ[v] < 1))
+    occ[v] = 1;
+  if (!cus && (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0) != hipSuccess || cus < 1)) cus = 256;
+  const int tiles = img_tiles(d), slots = cus * occ[v];
+  per = (tiles + slots - 1) / slots;
+  grid = (tiles + per - 1) / per;
+}
+static bool img_wg_ok(const rtsds_conv_desc* d) { return check_desc(d) == RTSDS_OK && imgconv_ok(d); }
+static size_t img_wg_slab_bytes(const rtsds_conv_desc* d) {
+  int grid, per;
+  img_wg_grid(d, grid, per);
+  return al256((size_t)grid * d->k * d->kh * d->kw * 3 * 4);
+}
+extern "C" size_t rtsds_imgconv_bn_wgrad_workspace(const rtsds_conv_desc* d) {
+  return img_wg_ok(d) ? img_wg_slab_bytes(d) + sp_x4_bytes(d) : 0;
+}
+static int img_wg_impl(const rtsds_conv_desc* d, const void* x, const void* bn_dy, const void* bn_x, const float* coef, int act,
+                       float* dw, int accumulate, void* ws, size_t ws_bytes, rtsds_split_reduce_desc* pending, void* stream) {
+  if (!img_wg_ok(d)) return check_desc(d) ? check_desc(d) : RTSDS_ERR_UNSUPPORTED;
+  if (!(act == RTSDS_ACT_NONE || act == RTSDS_ACT_RELU || act == RTSDS_ACT_LEAKY)) return RTSDS_ERR_UNSUPPORTED;
+  if (!x || !bn_dy || !bn_x || !coef || !dw) return RTSDS_ERR_SHAPE;
+  const bool x_padded = (accumulate & RTSDS_INPUT_PADDED) != 0;
+  accumulate &= ~RTSDS_INPUT_PADDED;
+  if (ws_bytes < rtsds_imgconv_bn_wgrad_workspace(d)) return RTSDS_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t slab_bytes = img_wg_slab_bytes(d);
+  if (!x_padded) {
+    void* x4 = (char*)ws + slab_bytes;
+    sp_pad4(d, x, x4, st);
+    x = x4;
+  }
+  ImgWgArgs a;
+  a.x4 = (const bf16*)x; a.g = (const bf16*)bn_dy; a.xb = (const bf16*)bn_x; a.coef = coef; a.slab = (float*)ws;
+  a.n = d->n; a.h = d->h; a.w = d->w; a.ho = d->ho; a.wo = d->wo; a.ph = d->ph; a.pw = d->pw; a.act = act;
+  a.tiles = img_tiles(d);
+  int grid;
+  img_wg_grid(d, grid, a.per);
+  void* args[] = {&a};
+  (void)hipLaunchKernel(img_wg_kernel(d->kh, act), dim3(grid), dim3(256), args, 0, st);
+  // the slabs are already in dw's order: c = 4 "channels" per float4 output
+  rtsds_split_reduce_desc q;
+  q.slab = (const float*)ws;
+  q.dw = dw;
+  q.slab_stride = (long)d->k * d->kh * d->kw * 3;
+  q.nv = d->k * d->kh * d->kw * 3 / 4;
+  q.cv = 1;
+  q.cp = 4;
+  q.splits = grid;
+  q.accumulate = accumulate ? 1 : 0;
+  if (pending) {
+    *pending = q;
+    RET_LAUNCH();
+  }
+  return rtsds_split_reduce_many(1, &q, stream);
+}
+extern "C" int rtsds_imgconv_bn_wgrad(const rtsds_conv_desc* d, const void* x, const void* bn_dy, const void* bn_x,
+                                      const float* coef, int act, float* dw, int accumulate, void* ws, size_t ws_bytes,
+                                      void* stream) {
+  return img_wg_impl(d, x, bn_dy, bn_x, coef, act, dw, accumulate, ws, ws_bytes, nullptr, stream);
+}
+extern "C" int rtsds_imgconv_bn_wgrad_deferred(const rtsds_conv_desc* d, const void* x, const void* bn_dy, const void* bn_x,
+                                               const float* coef, int act, float* dw, int accumulate, void* ws,
+                                               size_t ws_bytes, rtsds_split_reduce_desc* pending, void* stream) {
+  if (!pending) return RTSDS_ERR_SHAPE;
+  pending->nv = 0;
+  return img_wg_impl(d, x, bn_dy, bn_x, coef, act, dw, accumulate, ws, ws_bytes, pending, stream);
 }

@@ -265,7 +265,7 @@ class ConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, wq, stride, padding, dilation, act, stats, join=None, fold=(0, False),
-                bn_link=None):
+                bn_link=None, wg_link=None):
         """``fold = (in_act, out_folded)``: ``in_act`` -- x is the output of a ReLU / LeakyReLU
         whose backward this conv's data gradient applies in its epilogue
         (rtsds_conv2d_dgrad_act); ``out_folded`` -- the single consumer of y does that for this
@@ -290,6 +290,19 @@ class ConvFn(torch.autograd.Function):
             raise RuntimeError("rtsds_amd: a conv whose input gradient is masked cannot join other readers")
         ctx.d, ctx.act, ctx.has_bias = d, act, bias is not None
         ctx.params = (weight, bias)
+        # the following BatchNorm's backward apply fused into this conv's weight gradient
+        # (ImgWgradLink): the input needs no gradient, no bias, no activation of our own, and the
+        # geometry the kernel takes.  (With side-stream weight gradients on, this one still runs
+        # on the backward's own stream, behind the BatchNorm statistics it depends on: the conv has
+        # no data-gradient chain to overlap, and both schedules keep computing the same bits.)
+        ctx.wg_link = None
+        if wg_link is not None:
+            wg_link.conv_ok = bool(
+                IMG_WGRAD_LINK and not ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and bias is None and not act
+                and not fold[0] and not fold[1]
+                and lib.rtsds_imgconv_bn_wgrad_workspace(ctypes.byref(d)) > 0)
+            if wg_link.conv_ok:
+                ctx.wg_link = wg_link
         ctx.join = join
         ctx.save_for_backward(x, wq, y if act else None)
         return y
@@ -301,6 +314,11 @@ class ConvFn(torch.autograd.Function):
         dy = nhwc(dy)
         if dy.dtype != x.dtype:
             dy = cast(dy, x.dtype)
+        link = ctx.wg_link
+        if link is not None and link.bn is not None:
+            # dy is the BatchNorm's incoming gradient: its dx is formed inside the weight gradient
+            (bx, coef, bact), link.bn = link.bn, None
+            return (None, _img_bn_wgrad(d, x, dy, bx, coef, bact, ctx.params[0], ctx.xflag)) + (None,) * 11
         if ctx.act and not ctx.out_folded:
             g = torch.empty_like(dy)
             lib.rtsds_act_bwd(_P(dy), _P(y), _P(g), dy.numel(), ctx.act, 1.0, dcode(dy), stream())
@@ -361,11 +379,31 @@ class ConvFn(torch.autograd.Function):
                                                   ws.numel(), stream())
                 if not ctx.needs_input_grad[1]:
                     dw = None
-        return dx, dw, db, None, None, None, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None, None, None, None
+
+
+def _img_bn_wgrad(d, x, g, bx, coef, act, weight, xflag):
+    """rtsds_imgconv_bn_wgrad into the optimizer arena (None returned; reduction deferred to the
+    end of the backward pass when allowed) or into a fresh dw."""
+    ws = workspace(lib.rtsds_imgconv_bn_wgrad_workspace(ctypes.byref(d)), x.device)
+    sinks = _sinks(weight)
+    if sinks is not None and DEFER_WGRAD_REDUCE and CONV_PROFILE is None:
+        pend = SplitReduceDesc()
+        lib.rtsds_imgconv_bn_wgrad_deferred(ctypes.byref(d), _P(x), _P(g), _P(bx), _P(coef), act, _P(sinks[0]),
+                                            1 | xflag, _P(ws), ws.numel(), ctypes.byref(pend), stream())
+        _deferred.append((pend, ws, torch.cuda.current_stream(ws.device)))
+        torch.autograd.Variable._execution_engine.queue_callback(flush_wgrad_reduce)
+        return None
+    dw = sinks[0] if sinks is not None else torch.empty((d.k, d.c, d.kh, d.kw), dtype=torch.float32,
+                                                         device=x.device, memory_format=CL)
+    with _Timed(d, "wgrad"):
+        lib.rtsds_imgconv_bn_wgrad(ctypes.byref(d), _P(x), _P(g), _P(bx), _P(coef), act, _P(dw),
+                                   (1 if sinks is not None else 0) | xflag, _P(ws), ws.numel(), stream())
+    return None if sinks is not None else dw
 
 
 def conv2d(x, weight, bias, wq, stride=(1, 1), padding=(0, 0), dilation=(1, 1), act=0, bn_stats=False,
-           join=None, in_act=0, fold_out=False, bn_link=None):
+           join=None, in_act=0, fold_out=False, bn_link=None, wg_link=None):
     """bn_stats=True: the conv epilogue also emits the following BatchNorm's per-tile batch
     statistics, attached to the output as ``_rt_bn_stats`` and consumed by batch_norm().
     ``join``: GradJoin shared with the other readers of ``x``."""
@@ -377,7 +415,7 @@ def conv2d(x, weight, bias, wq, stride=(1, 1), padding=(0, 0), dilation=(1, 1), 
         nrb = lib.rtsds_conv2d_fwd_stats_tiles(ctypes.byref(d))
         stats = torch.empty(nrb * k * 4, dtype=torch.float32, device=x.device)  # [k][nrb][4]
     y = ConvFn.apply(x, weight, bias, wq, tuple(stride), tuple(padding), tuple(dilation), act, stats, join,
-                     (in_act, bool(fold_out and act in (1, 2))), bn_link)
+                     (in_act, bool(fold_out and act in (1, 2))), bn_link, wg_link)
     if stats is not None:
         y._rt_bn_stats = (stats, nrb)
     return y
@@ -568,12 +606,49 @@ class BnBwdLink:
         self.nrb = 0
 
 
+IMG_WGRAD_LINK = True  # False: the image convs' BatchNorms write dx and the conv reads it back (A/B tests)
+
+
+class ImgWgradLink:
+    """Joins a train-mode BatchNorm's backward to the weight gradient of the 3-channel image
+    conv that produced its input (ResNet stem, spatial path's first block): the conv input needs
+    no gradient, so the BatchNorm's dx has that weight gradient as its only reader.  The
+    BatchNorm backward then runs its statistics and finalize only (rtsds_bn_bwd_coef), leaves
+    ``(x, coef, act)`` here and returns its incoming gradient in place of dx; the conv backward
+    forms dx per tile inside the weight-gradient kernel (rtsds_imgconv_bn_wgrad).  Created by
+    nn.conv_bn / nn.conv_bn_relu_maxpool, whose conv output has the BatchNorm as its only
+    reader; the conv forward arms it when its geometry and situation qualify, the BatchNorm
+    forward accepts it when its own do.  Everything else runs the separate passes."""
+
+    __slots__ = ("conv_ok", "bn")
+
+    def __init__(self):
+        self.conv_ok = False  # set by the conv forward
+        self.bn = None        # (bn input x, coef, act), set by the BatchNorm backward
+
+    def take(self, x, training, act):
+        """The link, if armed and the BatchNorm on ``x`` qualifies (BatchNorm forward)."""
+        if IMG_WGRAD_LINK and self.conv_ok and training and act in (0, 1, 2) and x.dtype == torch.bfloat16 \
+                and not getattr(x, "_backward_hooks", None):
+            return self
+        return None
+
+
+def _bn_bwd_coef(ctx_link, dy, x, dg, db, rows, c, gamma, beta, sm, si, training, act, acc):
+    """Statistics + finalize of a linked BatchNorm backward; the coefficients go to the link."""
+    coef = torch.empty(6 * c, dtype=torch.float32, device=x.device)
+    ws = workspace(lib.rtsds_bn_workspace(rows, c), x.device)
+    lib.rtsds_bn_bwd_coef(_P(dy), _P(x), _P(dg), _P(db), _P(coef), rows, c, _P(gamma), _P(beta), _P(sm), _P(si),
+                          training, act, acc, dcode(x), _P(ws), ws.numel(), stream())
+    ctx_link.bn = (x, coef, act)
+
+
 class BatchNormFn(torch.autograd.Function):
     """BatchNorm2d (+ residual add) (+ ReLU/LeakyReLU) fused, train or eval statistics."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, res, running_mean, running_var, training, momentum, eps, act,
-                stats, stats_nrb, nbt, res_join=None, link=None, out=None):
+                stats, stats_nrb, nbt, res_join=None, link=None, out=None, wg_link=None):
         require_hip(x)
         x = nhwc(x)
         if res is not None:
@@ -608,6 +683,7 @@ class BatchNormFn(torch.autograd.Function):
                 and x.dtype == torch.bfloat16 and c % 8 == 0:
             link.src, link.part = (x, sm, si, gamma, beta, act), None
             ctx.link = link
+        ctx.wg_link = wg_link if res is None else None
         return y
 
     @staticmethod
@@ -619,6 +695,13 @@ class BatchNormFn(torch.autograd.Function):
             dy = nhwc(dy)
             ldy = c
         need_dx, need_r = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        if ctx.wg_link is not None and need_dx and ldy == c and dy.dtype == x.dtype:
+            # dx is formed inside the image conv's weight gradient: hand it our incoming gradient
+            dg, db, acc = _bn_param_grads(ctx, c, x.device)
+            _bn_bwd_coef(ctx.wg_link, dy, x, dg, db, rows, c, gamma, beta, sm, si, training, act, acc)
+            if acc:
+                dg = db = None
+            return (dy, dg, db) + (None,) * 14
         dx = torch.empty_like(x, memory_format=CL) if need_dx else None
         dres = torch.empty_like(x, memory_format=CL) if (has_res and need_r) else None
         dg, db, acc = _bn_param_grads(ctx, c, x.device)
@@ -639,7 +722,7 @@ class BatchNormFn(torch.autograd.Function):
             dg = db = None
         if dres is not None:
             dres = _join_add(ctx.res_join, dres)
-        return dx, dg, db, dres, None, None, None, None, None, None, None, None, None, None, None, None
+        return dx, dg, db, dres, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 def _nhwc_pitch(t):
@@ -691,13 +774,16 @@ def _bn_epilogue_stats(x, training, running_mean):
 
 
 def batch_norm(x, gamma, beta, running_mean, running_var, training, momentum, eps, act=0,
-               residual=None, num_batches_tracked=None, res_join=None, link=None, out=None):
+               residual=None, num_batches_tracked=None, res_join=None, link=None, out=None, wg_link=None):
     """``num_batches_tracked`` (int64, optional) is incremented by the finalize kernel.
     ``res_join``: GradJoin shared with the other readers of ``residual``.  ``out``: (NHWC
-    buffer, channel offset) to write y into (a view of it is returned; bf16 without residual)."""
+    buffer, channel offset) to write y into (a view of it is returned; bf16 without residual).
+    ``wg_link``: ImgWgradLink of the image conv that produced ``x``."""
     stats, nrb = _bn_epilogue_stats(x, training, running_mean)
+    if wg_link is not None:
+        wg_link = wg_link.take(x, training and residual is None, act)
     return BatchNormFn.apply(x, gamma, beta, residual, running_mean, running_var, training,
-                             momentum, eps, act, stats, nrb, num_batches_tracked, res_join, link, out)
+                             momentum, eps, act, stats, nrb, num_batches_tracked, res_join, link, out, wg_link)
 
 
 # ----------------------------------------------------------------------------- layout / dtype
@@ -1036,7 +1122,7 @@ class BnReluMaxPoolFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, stats, stats_nrb, nbt,
-                p, ceil_mode):
+                p, ceil_mode, wg_link=None):
         require_hip(x)
         x = nhwc(x)
         n, c, h, w = x.shape
@@ -1053,6 +1139,7 @@ class BnReluMaxPoolFn(torch.autograd.Function):
         ctx.meta = (n, c, h, w, ho, wo, p, int(training))
         ctx.gamma, ctx.beta = gamma, beta
         ctx.save_for_backward(x, idx, gamma, beta, sm, si)
+        ctx.wg_link = wg_link
         return y
 
     @staticmethod
@@ -1070,12 +1157,17 @@ class BnReluMaxPoolFn(torch.autograd.Function):
         # vs 66 + 45 + 60 us at the BiSeNet stem, the gather's 4-window compare is VALU-bound)
         g = empty_nhwc(n, c, h, w, dy.dtype, dy.device)
         lib.rtsds_maxpool_bwd(_P(dy), _P(idx), _P(g), n, h, w, c, ho, wo, 3, 2, p, dcode(dy), stream())
-        ws = workspace(lib.rtsds_bn_workspace(n * h * w, c), x.device)
-        lib.rtsds_bn_bwd(_P(g), _P(x), None, _P(dx), None, _P(dg), _P(db), n * h * w, c, _P(gamma), _P(beta),
-                         _P(sm), _P(si), training, ACT_RELU, acc, dcode(x), _P(ws), ws.numel(), stream())
+        if ctx.wg_link is not None and dx is not None:
+            # dx is formed inside the stem conv's weight gradient, from the pool gradient g
+            _bn_bwd_coef(ctx.wg_link, g, x, dg, db, n * h * w, c, gamma, beta, sm, si, training, ACT_RELU, acc)
+            dx = g
+        else:
+            ws = workspace(lib.rtsds_bn_workspace(n * h * w, c), x.device)
+            lib.rtsds_bn_bwd(_P(g), _P(x), None, _P(dx), None, _P(dg), _P(db), n * h * w, c, _P(gamma), _P(beta),
+                             _P(sm), _P(si), training, ACT_RELU, acc, dcode(x), _P(ws), ws.numel(), stream())
         if acc:
             dg = db = None
-        return dx, dg, db, None, None, None, None, None, None, None, None, None, None
+        return dx, dg, db, None, None, None, None, None, None, None, None, None, None, None
 
 
 def bn_relu_maxpool_ok(x, k, s, p):
@@ -1084,10 +1176,12 @@ def bn_relu_maxpool_ok(x, k, s, p):
 
 
 def bn_relu_maxpool(x, gamma, beta, running_mean, running_var, training, momentum, eps, p, ceil_mode,
-                    num_batches_tracked=None):
+                    num_batches_tracked=None, wg_link=None):
     stats, nrb = _bn_epilogue_stats(x, training, running_mean)
+    if wg_link is not None:
+        wg_link = wg_link.take(x, training, ACT_RELU)
     return BnReluMaxPoolFn.apply(x, gamma, beta, running_mean, running_var, training, momentum, eps, stats, nrb,
-                                 num_batches_tracked, p, ceil_mode)
+                                 num_batches_tracked, p, ceil_mode, wg_link)
 
 
 class PooledMlpFn(torch.autograd.Function):

@@ -48,18 +48,18 @@ class Conv2d(nn.Conv2d):
             self.weight.data = self.weight.data.contiguous(memory_format=CL)
         return out
 
-    def forward(self, x, act=None, bn_stats=False, join=None, in_act=None, fold_out=False, bn_link=None):
+    def forward(self, x, act=None, bn_stats=False, join=None, in_act=None, fold_out=False, bn_link=None, wg_link=None):
         """``bn_stats``: also emit the batch statistics of a directly following train-mode
         BatchNorm from the conv epilogue (see functional.conv2d).  ``join``: a
         functional.GradJoin shared with the other readers of ``x``.  ``in_act`` / ``fold_out``:
         activation-backward folding between chained convs (functional.ConvFn)."""
         wq = _shadow(self.weight, x.dtype)
         return F.conv2d(x, self.weight, self.bias, wq, self.stride, self.padding, self.dilation,
-                        ACT[act], bn_stats, join, ACT[in_act], fold_out, bn_link)
+                        ACT[act], bn_stats, join, ACT[in_act], fold_out, bn_link, wg_link)
 
 
 class BatchNorm2d(nn.BatchNorm2d):
-    def forward(self, x, act=None, residual=None, res_join=None, link=None, out=None):
+    def forward(self, x, act=None, residual=None, res_join=None, link=None, out=None, wg_link=None):
         training = self.training or not self.track_running_stats
         if training and x.shape[0] * x.shape[2] * x.shape[3] == 1:
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
@@ -70,7 +70,7 @@ class BatchNorm2d(nn.BatchNorm2d):
         # num_batches_tracked.add_(1) happens inside the statistics-finalize kernel
         nbt = self.num_batches_tracked if (self.training and self.track_running_stats) else None
         return F.batch_norm(x, self.weight, self.bias, rm, rv, training, self.momentum, self.eps,
-                            ACT[act], residual, nbt, res_join, link, out)
+                            ACT[act], residual, nbt, res_join, link, out, wg_link)
 
 
 class ReLU(nn.Module):
@@ -127,6 +127,16 @@ def _no_grad_needed(conv, bn, x, residual):
     return not any(t is not None and t.requires_grad for t in ts)
 
 
+def _img_wgrad_link(conv, x):
+    """A functional.ImgWgradLink for a 3-channel image conv whose input needs no gradient (the conv
+    and BatchNorm forwards check the rest), else None.  Only for a conv output read by the
+    BatchNorm alone, as in the helpers below."""
+    if conv.in_channels == 3 and conv.bias is None and torch.is_grad_enabled() and not x.requires_grad \
+            and conv.weight.requires_grad:
+        return F.ImgWgradLink()
+    return None
+
+
 def conv_bn(conv, bn, x, act=None, residual=None, join=None, res_join=None, in_link=None, out_link=None, out=None):
     """bn(conv(x)) with the BatchNorm's batch statistics produced by the conv epilogue
     (train mode) instead of a separate pass over the conv output.  Eval mode without
@@ -143,8 +153,9 @@ def conv_bn(conv, bn, x, act=None, residual=None, join=None, res_join=None, in_l
         wq = _shadow(conv.weight, x.dtype)
         return F.conv_bn_eval(x, conv.weight, conv.bias, wq, conv.stride, conv.padding, conv.dilation,
                               bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, ACT[act], residual, out=out)
-    return bn(conv(x, bn_stats=use_batch, join=join, bn_link=in_link), act=act, residual=residual, res_join=res_join,
-              link=out_link, out=out)
+    wg = _img_wgrad_link(conv, x) if use_batch and residual is None and join is None else None
+    return bn(conv(x, bn_stats=use_batch, join=join, bn_link=in_link, wg_link=wg), act=act, residual=residual,
+              res_join=res_join, link=out_link, out=out, wg_link=wg)
 
 
 def conv_bn_relu_maxpool(conv, bn, pool, x):
@@ -158,13 +169,15 @@ def conv_bn_relu_maxpool(conv, bn, pool, x):
     p = pool.padding if isinstance(pool.padding, int) else pool.padding[0]
     if use_batch and bn.momentum is not None and x.dtype == torch.bfloat16 and conv.out_channels % 8 == 0 \
             and k == 3 and s == 2 and p in (0, 1):
-        y = conv(x, bn_stats=True)
+        wg = _img_wgrad_link(conv, x)
+        y = conv(x, bn_stats=True, wg_link=wg)
         if F.bn_relu_maxpool_ok(y, k, s, p):
             rm = bn.running_mean if bn.track_running_stats else None
             rv = bn.running_var if bn.track_running_stats else None
             nbt = bn.num_batches_tracked if (bn.training and bn.track_running_stats) else None
-            return F.bn_relu_maxpool(y, bn.weight, bn.bias, rm, rv, True, bn.momentum, bn.eps, p, pool.ceil_mode, nbt)
-        return pool(bn(y, act="relu"))
+            return F.bn_relu_maxpool(y, bn.weight, bn.bias, rm, rv, True, bn.momentum, bn.eps, p, pool.ceil_mode, nbt,
+                                     wg_link=wg)
+        return pool(bn(y, act="relu", wg_link=wg))
     if not use_batch and bn.momentum is not None and _no_grad_needed(conv, bn, x, None) and k == 3 and s == 2:
         # inference: the pool runs in the folded conv's epilogue (rtsds_conv2d_fwd_bn_maxpool)
         y = F.conv_bn_maxpool_eval(x, conv.weight, conv.bias, _shadow(conv.weight, x.dtype), conv.stride, conv.padding,
