@@ -594,6 +594,28 @@ int rtsds_color_jitter(const void* src, int src_u8, float* dst, int c, int h, in
                        int mask, float fb, float fc, float fs, float fh, float bound, void* ws,
                        size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- histogram matching
+ * Per-channel histogram matching of a decoded HWC RGB uint8 image to a reference image's
+ * statistics (Abramov et al. 2020; no reference counterpart), integers only.  For one channel
+ * with source counts hs, reference counts hr, inclusive prefix sums Cs, Cr and totals Ns, Nr:
+ *   m[v]   = min { t in 0..255 : Cr[t] * Ns >= Cs[v] * Nr }   (64-bit products; v when Ns or Nr is 0)
+ *   lut[v] = (v * (256 - A) + m[v] * A + 128) >> 8            A = strength_q8: 0 identity, 256 full
+ *   out    = lut[channel][in]
+ * rtsds_hist_u8: hist[ch][v] (uint32 [3][256]) = the number of pixels of img ([h][w][3]) whose
+ *   channel ch equals v.  hist is zeroed on the stream first (a memset node under capture), then
+ *   one launch adds into it with integer atomics: the result does not depend on arrival order.
+ * rtsds_hist_match: dst = the matched src in one launch, from the histogram of src and that of
+ *   the reference image (which may have another size); every block rebuilds the 768-byte LUT in
+ *   LDS, nothing is synchronised with the host.  dst may be src.  lut_out ([3][256] bytes, or
+ *   NULL) receives the LUT.  The totals of both histograms must be pixel counts (<= 2^32 - 1).
+ * Both: RTSDS_ERR_SHAPE for a NULL pointer (lut_out aside), a non-positive size, h * w above
+ *   2^32 - 1 or strength_q8 outside [0, 256]; RTSDS_ERR_UNSUPPORTED for c != 3 or a histogram
+ *   pointer that is not 4-B aligned; all before any HIP call.  A 16-B aligned image base takes
+ *   the vector path, any other the byte path.                                                   */
+int rtsds_hist_u8(const uint8_t* img, int c, int h, int w, unsigned int* hist, void* stream);
+int rtsds_hist_match(const uint8_t* src, uint8_t* dst, int c, int h, int w, const unsigned int* hist_src,
+                     const unsigned int* hist_ref, int strength_q8, uint8_t* lut_out, void* stream);
+
 /* ---------------------------------------------------------------- graph replay
  * Replaces hipGraphLaunch of a captured multi-stream iteration (runtime.GraphedStep /
  * GraphedForward; the reference has no graphs: its train.py:65-113 / 172-284 loop bodies
@@ -636,7 +658,7 @@ int rtsds_pooled_mlp_fwd(const void* p, const void* w1, const float* b1, const v
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 17
+#define RTSDS_ABI_VERSION 18
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

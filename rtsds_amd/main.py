@@ -104,6 +104,20 @@ class SyntheticLoader:
         return iter(self.data)
 
 
+HISTOGRAM_BANK_CAPACITY = 64  # augmentation.HistogramMatching.bank, when absent
+
+
+def build_histogram_bank(dataset, capacity, device="cuda"):
+    """The target histograms augmentation HistogramMatching draws from: the raw images
+    ``dataset[i][0]`` at transforms.bank_indices(len(dataset), capacity) -- an even spread, the
+    same on every rank -- moved to the device and counted there (3 KB kept per image)."""
+    from . import transforms as T
+    bank = T.HistogramBank(capacity, device)
+    for i in T.bank_indices(len(dataset), capacity):
+        bank.add([dataset[i][0].to(device)])
+    return bank
+
+
 def real_datasets_loader(config, is_augmented, device="cuda"):
     """main.py:60-108 on the device pipeline: the reference's readers (PNG decode on CPU
     DataLoader workers) deliver raw uint8 samples, batches go to HBM and through the
@@ -127,9 +141,13 @@ def real_datasets_loader(config, is_augmented, device="cuda"):
 
     city_img = T.ImagePipeline(cs_size)
     city_lbl = T.LabelPipeline(cs_size, clamp=(0, cs["num_classes"]))
-    gta_img = T.ImagePipeline(gta_size, augment=T.augmentation_loader(config, 0.5) if is_augmented else None)
-    gta_lbl = T.LabelPipeline(gta_size)
     train_ds = CityScapes(cs["segmentation_train_dir"], cs["images_train_dir"])
+    bank = None
+    if is_augmented and "HistogramMatching" in config.augmentation:  # GTA5 colours towards Cityscapes train
+        capacity = (config.augmentation["HistogramMatching"] or {}).get("bank", HISTOGRAM_BANK_CAPACITY)
+        bank = build_histogram_bank(train_ds, capacity, device)
+    gta_img = T.ImagePipeline(gta_size, augment=T.augmentation_loader(config, 0.5, bank=bank) if is_augmented else None)
+    gta_lbl = T.LabelPipeline(gta_size)
     val_ds = CityScapes(cs["segmentation_val_dir"], cs["images_val_dir"])
     gta_ds = GTA5(gta["images_dir"], gta["segmentation_dir"], None, None)
     return (T.DeviceLoader(loader(train_ds, cs["batch_size"], cs["num_workers"], True), city_img, city_lbl, device),

@@ -18,12 +18,16 @@ source image per sample; the image's resize reads that window in place (rtsds_cr
 and the label takes the same window through a nearest resample (rtsds_crop_resize_nearest).
 RandomHorizontalFlip(labels=True) mirrors the label with the image.  ImagePipeline records what
 it did per sample in ``last_geometry``; DeviceLoader hands that to the LabelPipeline.
+HistogramMatching matches each channel's histogram of the decoded uint8 image to that of a target
+image drawn from a HistogramBank (csrc/histmatch.hip: rtsds_hist_u8, rtsds_hist_match), ahead of
+the blur and the jitter; ``last_style`` records the draw per sample.
 
 The image comes out in the network's input layout (NHWC, the runtime compute dtype), so the
 model's input packing is a no-op; labels come out int64 [N, 1, H, W] as the reference's loaders
 deliver them (train.py squeezes dim 1).  Random decisions draw from torch's CPU generator in
 torchvision's call order (RandomApply's coin, then per listed transform: GaussianBlur's sigma,
-the flip coin, ColorJitter's permutation and factors, RandomResizedCrop's get_params).
+the flip coin, ColorJitter's permutation and factors, RandomResizedCrop's get_params,
+HistogramMatching's coin and -- if taken -- bank entry and strength).
 """
 import ctypes
 import math
@@ -31,7 +35,8 @@ import math
 import torch
 
 from ._lib import lib
-from .runtime import CL, compute_dtype, stream, workspace
+from .functional import _U32
+from .runtime import CL, compute_dtype, require_hip, stream, workspace
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -153,6 +158,37 @@ class ColorJitter:
         return (order,) + fs
 
 
+class HistogramMatching:
+    """Per-channel histogram matching of the decoded image to a target image drawn from ``bank``
+    (anything with ``len()`` and ``hist(k)``: HistogramBank), with probability ``p`` and a blend
+    strength ~ U(strength) in [0, 1] (1 = full matching).  Not in the reference."""
+
+    def __init__(self, bank, p=0.5, strength=(1.0, 1.0)):
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+            raise ValueError("p should be a number in [0, 1].")
+        if isinstance(strength, (int, float)) and not isinstance(strength, bool):
+            strength = (strength, strength)
+        ok = isinstance(strength, (tuple, list)) and len(strength) == 2 and \
+            all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in strength)
+        if not ok or not 0.0 <= strength[0] <= strength[1] <= 1.0:
+            raise ValueError("strength should be a pair of numbers ordered within [0, 1].")
+        self.bank = bank
+        self.p = float(p)
+        self.strength = (float(strength[0]), float(strength[1]))
+
+    def params(self):
+        """None, or (k, A): the bank entry and the strength in Q8.  Draws: the coin, then -- only
+        if it is taken -- the entry and the strength."""
+        if not bool(torch.rand(1) < self.p):
+            return None
+        n = len(self.bank)
+        if n == 0:
+            raise RuntimeError("rtsds_amd.transforms: HistogramMatching drew from an empty bank")
+        k = int(torch.randint(0, n, (1,)).item())
+        s = float(torch.empty(1).uniform_(self.strength[0], self.strength[1]).item())
+        return k, _strength_q8(s)
+
+
 class RandomApply:
     """RandomApply(transforms, p): the listed transforms all run with probability p."""
 
@@ -161,8 +197,9 @@ class RandomApply:
         self.p = p
 
 
-def augmentation_loader(config, probability):
-    """main.py:46-58 / 25-44: RandomApply over the configured augmentations."""
+def augmentation_loader(config, probability, bank=None):
+    """main.py:46-58 / 25-44: RandomApply over the configured augmentations.  ``bank``: the
+    target histograms the key HistogramMatching draws from (main.build_histogram_bank)."""
     aug = config.augmentation
     out = []
     for key in aug.keys():
@@ -181,6 +218,13 @@ def augmentation_loader(config, probability):
             c = aug["ColorJitter"]
             out.append(ColorJitter(brightness=c["brightness"], contrast=c["contrast"], saturation=c["saturation"],
                                    hue=c["hue"]))
+        elif key == "HistogramMatching":
+            c = aug["HistogramMatching"]
+            if bank is None:
+                raise RuntimeError("rtsds_amd.transforms: the augmentation HistogramMatching needs a bank of "
+                                   "target histograms (augmentation_loader(config, p, bank=...))")
+            strength = [float(i) for i in str(c["strength"]).split(",")] if "strength" in c else [1.0, 1.0]
+            out.append(HistogramMatching(bank, p=c["p"], strength=strength * 2 if len(strength) == 1 else strength))
         elif key == "ColorJitterWithRandomBrightness":
             raise NotImplementedError("rtsds_amd.transforms: ColorJitterWithRandomBrightness is not implemented "
                                       "(the reference config has it commented out, config.yaml:118-123)")
@@ -193,11 +237,18 @@ def _sample_draws(augment, h=None, w=None):
     RandomResizedCrop's (y0, x0, hc, wc) or None; flip_label says the flip came from a
     RandomHorizontalFlip(labels=True).  Geometry takes effect at the resize wherever its key
     stands (the window is uniform in x, so a flip ahead of it changes no distribution)."""
+    return _sample_draws_styled(augment, h, w)[:4]
+
+
+def _sample_draws_styled(augment, h=None, w=None):
+    """_sample_draws' four and, fifth, HistogramMatching's draw (None, or (its bank, k, A)), taken
+    at the transform's position in the list; the matching itself acts on the decoded image,
+    ahead of the blur and the jitter, wherever its key stands."""
     if augment is None or not augment.transforms:
-        return [], False, None, False
+        return [], False, None, False, None
     if augment.p < torch.rand(1):
-        return [], False, None, False
-    ops, flip, window, flip_label = [], False, None, False
+        return [], False, None, False, None
+    ops, flip, window, flip_label, style = [], False, None, False, None
     for t in augment.transforms:
         if isinstance(t, (GaussianBlur, ColorJitter)):
             ops.append((t, t.params()))
@@ -208,7 +259,10 @@ def _sample_draws(augment, h=None, w=None):
             if h is None or w is None:
                 raise RuntimeError("rtsds_amd.transforms: RandomResizedCrop draws for a source size")
             window = t.params(h, w)
-    return ops, flip, window, flip_label
+        elif isinstance(t, HistogramMatching):
+            drawn = t.params()
+            style = None if drawn is None else (t.bank,) + drawn
+    return ops, flip, window, flip_label, style
 
 
 def _decisions(augment):
@@ -252,6 +306,101 @@ def color_jitter(img, order, fb, fc, fs, fh, value_range=255.0, out=None):
     return out
 
 
+def _strength_q8(strength):
+    """A = floor(strength * 256 + 0.5): the blend weight of rtsds_hist_match, 0..256."""
+    if not 0.0 <= strength <= 1.0:
+        raise RuntimeError(f"rtsds_amd.transforms: a matching strength in [0, 1] expected, got {strength}")
+    return int(math.floor(strength * 256 + 0.5))
+
+
+def _check_rgb_u8(img, what):
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or \
+            not img.is_contiguous():
+        raise RuntimeError(f"rtsds_amd.transforms: {what} takes a contiguous HWC uint8 [H, W, 3] image")
+    require_hip(img)
+
+
+def _check_hist(hist, device, what):
+    if not isinstance(hist, torch.Tensor) or hist.dtype != _U32 or tuple(hist.shape) != (3, 256) or \
+            not hist.is_contiguous() or hist.device != device:
+        raise RuntimeError(f"rtsds_amd.transforms: {what} must be a contiguous {_U32} [3, 256] tensor on the image's "
+                           "device")
+
+
+def image_histogram(img, out=None):
+    """The per-channel histogram of a uint8 HWC [H, W, 3] device image: uint32 [3, 256] on its
+    device (rtsds_hist_u8; ``out`` is overwritten, not added to)."""
+    _check_rgb_u8(img, "image_histogram")
+    if out is None:
+        out = torch.empty((3, 256), dtype=_U32, device=img.device)
+    else:
+        _check_hist(out, img.device, "image_histogram: out")
+    h, w, c = img.shape
+    _check(lib.rtsds_hist_u8(img.data_ptr(), c, h, w, out.data_ptr(), stream()), "image histogram")
+    return out
+
+
+def _hist_match_q8(img, hist_src, hist_ref, a, out=None, lut=None):
+    _check_rgb_u8(img, "histogram_match")
+    _check_hist(hist_src, img.device, "histogram_match: hist_src")
+    _check_hist(hist_ref, img.device, "histogram_match: hist_ref")
+    if out is None:
+        out = torch.empty_like(img)
+    elif out is not img:
+        _check_rgb_u8(out, "histogram_match: out")
+        if out.shape != img.shape or out.device != img.device:
+            raise RuntimeError("rtsds_amd.transforms: histogram_match writes an image of the source's shape and device")
+    if lut is not None and (not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or
+                            tuple(lut.shape) != (3, 256) or not lut.is_contiguous() or lut.device != img.device):
+        raise RuntimeError("rtsds_amd.transforms: histogram_match: lut must be a contiguous uint8 [3, 256] tensor on "
+                           "the image's device")
+    h, w, c = img.shape
+    _check(lib.rtsds_hist_match(img.data_ptr(), out.data_ptr(), c, h, w, hist_src.data_ptr(), hist_ref.data_ptr(),
+                                int(a), lut.data_ptr() if lut is not None else None, stream()), "histogram match")
+    return out
+
+
+def histogram_match(img, hist_src, hist_ref, strength=1.0, out=None, lut=None):
+    """``img`` (uint8 HWC [H, W, 3], device) with each channel's histogram ``hist_src`` matched to
+    ``hist_ref`` (both uint32 [3, 256]: image_histogram of the image and of the reference image),
+    blended with the source by ``strength`` in [0, 1] in Q8.  uint8 HWC out; ``out`` may be
+    ``img``.  ``lut`` (uint8 [3, 256]) receives the per-channel value map."""
+    return _hist_match_q8(img, hist_src, hist_ref, _strength_q8(float(strength)), out, lut)
+
+
+class HistogramBank:
+    """The histograms of up to ``capacity`` target images on the device (uint32
+    [capacity, 3, 256], 3 KB each): a ring, the oldest entry is overwritten when full."""
+
+    def __init__(self, capacity, device="cuda"):
+        if int(capacity) < 1:
+            raise ValueError("capacity should be positive.")
+        self.data = torch.zeros((int(capacity), 3, 256), dtype=torch.int32, device=device).view(_U32)
+        self._next = 0
+        self._filled = 0
+
+    def add(self, images):
+        """One histogram per uint8 HWC device image, each written straight into its slot."""
+        for img in images:
+            image_histogram(img, out=self.data[self._next])
+            self._next = (self._next + 1) % self.data.shape[0]
+            self._filled = min(self._filled + 1, self.data.shape[0])
+
+    def __len__(self):
+        return self._filled
+
+    def hist(self, k):
+        if not 0 <= k < self._filled:
+            raise IndexError(f"histogram {k} of a bank of {self._filled}")
+        return self.data[k]
+
+
+def bank_indices(n, k):
+    """The min(n, k) dataset indices floor(i * n / min(n, k)): an even spread over n samples."""
+    m = min(int(n), int(k))
+    return [i * int(n) // m for i in range(m)] if m > 0 else []
+
+
 def _as_hwc_u8(img):
     if img.dtype != torch.uint8:
         raise RuntimeError("rtsds_amd.transforms: decoded uint8 images expected")
@@ -269,6 +418,7 @@ class ImagePipeline:
         self.mean, self.std = tuple(mean), tuple(std)
         self.augment = augment
         self.last_geometry = None  # per sample of the last batch: None or a Geometry
+        self.last_style = None  # per sample of the last batch: None or HistogramMatching's (k, A)
         self._ms = {}
 
     def _mean_std(self, device):
@@ -286,11 +436,16 @@ class ImagePipeline:
         ms, sd = self._mean_std(dev)
         kind = 1 if dtype == torch.bfloat16 else 0
         self.last_geometry = geometry = []
+        self.last_style = styles = []
         for n, img in enumerate(images):
             img = _as_hwc_u8(img)
             h, w, c = img.shape
+            ops, flip, window, flip_label, style = _sample_draws_styled(self.augment, h, w)
+            styles.append(style and style[1:])
+            if style is not None:  # matched into a fresh image: the caller's stays as it is
+                bank, k, a = style
+                img = _hist_match_q8(img, image_histogram(img), bank.hist(k), a)
             src, src_u8 = img, 1
-            ops, flip, window, flip_label = _sample_draws(self.augment, h, w)
             if window == (0, 0, h, w):  # the whole image is no window: the plain resize, for the label too
                 window = None
             if window is not None or flip_label:
@@ -429,5 +584,6 @@ def parse_size(s):
 
 
 __all__ = ["ImagePipeline", "LabelPipeline", "DeviceLoader", "GaussianBlur", "RandomHorizontalFlip", "ColorJitter",
-           "RandomResizedCrop", "RandomApply", "Geometry", "augmentation_loader", "color_jitter", "decode_gta5_labels",
-           "collate_raw", "parse_size"]
+           "RandomResizedCrop", "HistogramMatching", "HistogramBank", "RandomApply", "Geometry", "augmentation_loader",
+           "color_jitter", "image_histogram", "histogram_match", "bank_indices", "decode_gta5_labels", "collate_raw",
+           "parse_size"]
