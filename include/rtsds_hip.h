@@ -616,6 +616,39 @@ int rtsds_hist_u8(const uint8_t* img, int c, int h, int w, unsigned int* hist, v
 int rtsds_hist_match(const uint8_t* src, uint8_t* dst, int c, int h, int w, const unsigned int* hist_src,
                      const unsigned int* hist_ref, int strength_q8, uint8_t* lut_out, void* stream);
 
+/* ---------------------------------------------------------------- Fourier domain adaptation
+ * FDA (Yang & Soatto, CVPR 2020; no reference counterpart) of a decoded HWC RGB uint8 image: the
+ * amplitude of the (2b+1) x (2b+1) lowest frequencies of the source's 2-D spectrum is replaced by a
+ * target image's, the phase is kept.  Only the band changes, so with F the source's DFT
+ *   out(y,x) = src(y,x) + 1/(hw) * sum_{|u|,|v| <= b} D(u,v) e^{2 pi i (uy/h + vx/w)}
+ *   D = strength * (A_t - A_s) * F / A_s      A_s = |F|, A_t = amp_ref_norm * (hw);
+ *                                             D = strength * A_t (zero phase) where A_s == 0
+ * and no full-frame transform is made.  Band layout, everywhere: fp32 spec[ch][iu][v][2] (re, im),
+ * iu = u + b for u = -b..b, v = 0..b; the other half follows from F(-u,-v) = conj F(u,v).  The
+ * amplitude arrays have the same layout without the last axis.
+ * rtsds_fda_spectrum: spec (or NULL) = F(u,v) = sum_y sum_x img[y][x][ch] e^{-2 pi i (uy/h + vx/w)}
+ *   over the band, amp_norm (or NULL, not both) = |F| / (hw), the size-independent form a bank of
+ *   target images stores.  Two launches: every row reduced over x for v = 0..b into the workspace
+ *   (rtsds_fda_workspace bytes), those reduced over y for u = -b..b.  No floating-point atomics,
+ *   every sum has a fixed order: two runs give the same bits.
+ * rtsds_fda_apply: dst = the adapted src in one launch from the source's band spec_src and the
+ *   target's normalised amplitudes amp_ref_norm (the target image may have another size).  Per
+ *   pixel and channel out = src + (G(y,0).re + 2 sum_{v=1..b} Re(G(y,v) e^{2 pi i vx/w})) / (hw) with
+ *   G(y,v) = sum_u D(u,v) e^{2 pi i uy/h}; every block forms the D and G of its rows in its prologue.
+ *   dst_u8 == 0: fp32 HWC, clamped to [0, 255]; else uint8 (rintf, then the clamp), and dst may be src.
+ * Every twiddle's phase is reduced in integers (u y mod h, v x mod w) before cos / sin are formed.
+ * All: c == 3 (else RTSDS_ERR_UNSUPPORTED, as for an fp32 pointer that is not 4-B aligned);
+ *   RTSDS_ERR_SHAPE for a NULL image or spectrum pointer, a non-positive size, b outside [1, 64],
+ *   2b + 1 > min(h, w), h * w > 2^24, strength outside [0, 1] or NaN; RTSDS_ERR_WORKSPACE for a
+ *   NULL or short workspace (rtsds_fda_workspace returns 0 for a shape it refuses); all before any
+ *   HIP call.  A 16-B aligned image base with w % 4 == 0 takes the dword path (12 bytes per lane),
+ *   anything else the byte path, with the same bits.                                              */
+size_t rtsds_fda_workspace(int h, int w, int b);
+int rtsds_fda_spectrum(const uint8_t* img, int c, int h, int w, int b, float* spec, float* amp_norm, void* ws,
+                       size_t ws_bytes, void* stream);
+int rtsds_fda_apply(const uint8_t* src, void* dst, int dst_u8, int c, int h, int w, int b, const float* spec_src,
+                    const float* amp_ref_norm, float strength, void* stream);
+
 /* ---------------------------------------------------------------- graph replay
  * Replaces hipGraphLaunch of a captured multi-stream iteration (runtime.GraphedStep /
  * GraphedForward; the reference has no graphs: its train.py:65-113 / 172-284 loop bodies
@@ -658,7 +691,7 @@ int rtsds_pooled_mlp_fwd(const void* p, const void* w1, const float* b1, const v
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 18
+#define RTSDS_ABI_VERSION 19
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

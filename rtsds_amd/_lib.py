@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSDS_LIB: alternative in-tree build of the same ABI (kernel-variant A/B measurements)
 DEFAULT_LIB_PATH = os.path.join(_HERE, "librtsds_hip.so")
-ABI_VERSION = 18  # include/rtsds_hip.h RTSDS_ABI_VERSION
+ABI_VERSION = 19  # include/rtsds_hip.h RTSDS_ABI_VERSION
 LIB_PATH = os.environ.get("RTSDS_LIB") or DEFAULT_LIB_PATH
 
 F32, BF16 = 0, 1
@@ -148,6 +148,9 @@ SIGNATURES = {
                                    c_float, c_float, c_float, P, c_size_t, P]),
     "rtsds_hist_u8": (c_int, [P, c_int, c_int, c_int, P, P]),
     "rtsds_hist_match": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, P, P]),
+    "rtsds_fda_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "rtsds_fda_spectrum": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "rtsds_fda_apply": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, P]),
     "rtsds_sgd_step": (c_int, [P, P, P, P, c_long, P, c_float, c_float, c_float, c_float, c_int, c_int,
                                c_float, c_int, P]),
     "rtsds_adam_step": (c_int, [P, P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float,

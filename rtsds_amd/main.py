@@ -118,6 +118,21 @@ def build_histogram_bank(dataset, capacity, device="cuda"):
     return bank
 
 
+SPECTRUM_BANK_CAPACITY = 64  # augmentation.FourierAdaptation.bank, when absent
+
+
+def build_spectrum_bank(dataset, capacity=SPECTRUM_BANK_CAPACITY, b=7, device="cuda"):
+    """The target amplitudes augmentation FourierAdaptation draws from: the band |u|, |v| <= b of
+    the raw images ``dataset[i][0]`` at transforms.bank_indices(len(dataset), capacity), the same
+    spread as build_histogram_bank's.  The images keep their own size: an entry is |F| / (h w) at
+    the image's own integer frequencies (cycles per image), 12 (2b+1)(b+1) bytes each."""
+    from . import transforms as T
+    bank = T.SpectrumBank(capacity, b, device)
+    for i in T.bank_indices(len(dataset), capacity):
+        bank.add([dataset[i][0].to(device)])
+    return bank
+
+
 def real_datasets_loader(config, is_augmented, device="cuda"):
     """main.py:60-108 on the device pipeline: the reference's readers (PNG decode on CPU
     DataLoader workers) deliver raw uint8 samples, batches go to HBM and through the
@@ -146,7 +161,14 @@ def real_datasets_loader(config, is_augmented, device="cuda"):
     if is_augmented and "HistogramMatching" in config.augmentation:  # GTA5 colours towards Cityscapes train
         capacity = (config.augmentation["HistogramMatching"] or {}).get("bank", HISTOGRAM_BANK_CAPACITY)
         bank = build_histogram_bank(train_ds, capacity, device)
-    gta_img = T.ImagePipeline(gta_size, augment=T.augmentation_loader(config, 0.5, bank=bank) if is_augmented else None)
+    spectrum_bank = None
+    if is_augmented and "FourierAdaptation" in config.augmentation:  # GTA5 low frequencies towards Cityscapes train
+        c = config.augmentation["FourierAdaptation"] or {}
+        # the band of the configured GTA5 frame; the transform checks every decoded image against it
+        b = T.FourierAdaptation(None, beta=c.get("beta", 0.01)).band(*gta_size)
+        spectrum_bank = build_spectrum_bank(train_ds, c.get("bank", SPECTRUM_BANK_CAPACITY), b, device)
+    gta_img = T.ImagePipeline(gta_size, augment=T.augmentation_loader(config, 0.5, bank=bank, spectrum_bank=spectrum_bank)
+                              if is_augmented else None)
     gta_lbl = T.LabelPipeline(gta_size)
     val_ds = CityScapes(cs["segmentation_val_dir"], cs["images_val_dir"])
     gta_ds = GTA5(gta["images_dir"], gta["segmentation_dir"], None, None)

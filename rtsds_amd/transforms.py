@@ -21,13 +21,17 @@ it did per sample in ``last_geometry``; DeviceLoader hands that to the LabelPipe
 HistogramMatching matches each channel's histogram of the decoded uint8 image to that of a target
 image drawn from a HistogramBank (csrc/histmatch.hip: rtsds_hist_u8, rtsds_hist_match), ahead of
 the blur and the jitter; ``last_style`` records the draw per sample.
+FourierAdaptation (FDA, Yang & Soatto 2020) replaces the low-frequency amplitudes of the decoded
+image's spectrum by those of a target image drawn from a SpectrumBank (csrc/fda.hip:
+rtsds_fda_spectrum, rtsds_fda_apply), in uint8, after the histogram matching and ahead of the
+blur and the jitter; ``last_spectral`` records the draw per sample.
 
 The image comes out in the network's input layout (NHWC, the runtime compute dtype), so the
 model's input packing is a no-op; labels come out int64 [N, 1, H, W] as the reference's loaders
 deliver them (train.py squeezes dim 1).  Random decisions draw from torch's CPU generator in
 torchvision's call order (RandomApply's coin, then per listed transform: GaussianBlur's sigma,
 the flip coin, ColorJitter's permutation and factors, RandomResizedCrop's get_params,
-HistogramMatching's coin and -- if taken -- bank entry and strength).
+HistogramMatching's and FourierAdaptation's coin and -- if taken -- bank entry and strength).
 """
 import ctypes
 import math
@@ -189,6 +193,63 @@ class HistogramMatching:
         return k, _strength_q8(s)
 
 
+FDA_MAX_BAND = 64  # rtsds_fda_*: 1 <= b <= 64, 2b + 1 <= min(h, w), h * w <= 2^24
+FDA_MAX_PIXELS = 1 << 24
+
+
+def _check_band(h, w, b):
+    if not 1 <= b <= FDA_MAX_BAND or 2 * b + 1 > min(h, w) or h * w > FDA_MAX_PIXELS:
+        raise ValueError(f"rtsds_amd.transforms: a Fourier band of b = {b} on a {h} x {w} image is outside the kernels' "
+                         f"limits (1 <= b <= {FDA_MAX_BAND}, 2b + 1 <= min(h, w), h * w <= 2^24)")
+
+
+class FourierAdaptation:
+    """Fourier Domain Adaptation (Yang & Soatto, CVPR 2020): with probability ``p`` the amplitudes
+    of the (2b+1) x (2b+1) lowest frequencies of the decoded image, b = max(1, floor(min(h, w) *
+    beta)), are blended by a strength ~ U(strength) in [0, 1] (1 = replaced) towards those of a
+    target image drawn from ``bank`` (anything with ``len()``, ``b`` and ``amp(k)``: SpectrumBank);
+    the phase is kept.  Not in the reference."""
+
+    def __init__(self, bank, p=0.5, beta=0.01, strength=(1.0, 1.0)):
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+            raise ValueError("p should be a number in [0, 1].")
+        if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not 0.0 < beta < 0.5:
+            raise ValueError("beta should be a number in (0, 0.5).")
+        if isinstance(strength, (int, float)) and not isinstance(strength, bool):
+            strength = (strength, strength)
+        ok = isinstance(strength, (tuple, list)) and len(strength) == 2 and \
+            all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in strength)
+        if not ok or not 0.0 <= strength[0] <= strength[1] <= 1.0:
+            raise ValueError("strength should be a pair of numbers ordered within [0, 1].")
+        self.bank = bank
+        self.p = float(p)
+        self.beta = float(beta)
+        self.strength = (float(strength[0]), float(strength[1]))
+
+    def band(self, h, w):
+        """b for an h x w image; raises where the kernels' limits are broken or the bank was built
+        for another band."""
+        b = max(1, int(math.floor(min(h, w) * self.beta)))
+        _check_band(h, w, b)
+        have = getattr(self.bank, "b", None)
+        if have is not None and have != b:
+            raise ValueError(f"rtsds_amd.transforms: FourierAdaptation(beta={self.beta}) needs a band of b = {b} on a "
+                             f"{h} x {w} image, the bank holds b = {have}")
+        return b
+
+    def params(self):
+        """None, or (k, strength): the bank entry and the blend.  Draws: the coin, then -- only if
+        it is taken -- the entry and the strength (HistogramMatching's order)."""
+        if not bool(torch.rand(1) < self.p):
+            return None
+        n = len(self.bank)
+        if n == 0:
+            raise RuntimeError("rtsds_amd.transforms: FourierAdaptation drew from an empty bank")
+        k = int(torch.randint(0, n, (1,)).item())
+        s = float(torch.empty(1).uniform_(self.strength[0], self.strength[1]).item())
+        return k, s
+
+
 class RandomApply:
     """RandomApply(transforms, p): the listed transforms all run with probability p."""
 
@@ -197,9 +258,11 @@ class RandomApply:
         self.p = p
 
 
-def augmentation_loader(config, probability, bank=None):
+def augmentation_loader(config, probability, bank=None, *, spectrum_bank=None):
     """main.py:46-58 / 25-44: RandomApply over the configured augmentations.  ``bank``: the
-    target histograms the key HistogramMatching draws from (main.build_histogram_bank)."""
+    target histograms the key HistogramMatching draws from (main.build_histogram_bank);
+    ``spectrum_bank``: the target amplitudes of the key FourierAdaptation
+    (main.build_spectrum_bank)."""
     aug = config.augmentation
     out = []
     for key in aug.keys():
@@ -225,6 +288,14 @@ def augmentation_loader(config, probability, bank=None):
                                    "target histograms (augmentation_loader(config, p, bank=...))")
             strength = [float(i) for i in str(c["strength"]).split(",")] if "strength" in c else [1.0, 1.0]
             out.append(HistogramMatching(bank, p=c["p"], strength=strength * 2 if len(strength) == 1 else strength))
+        elif key == "FourierAdaptation":
+            c = aug["FourierAdaptation"] or {}
+            if spectrum_bank is None:
+                raise RuntimeError("rtsds_amd.transforms: the augmentation FourierAdaptation needs a bank of target "
+                                   "amplitudes (augmentation_loader(config, p, spectrum_bank=...))")
+            strength = [float(i) for i in str(c["strength"]).split(",")] if "strength" in c else [1.0, 1.0]
+            out.append(FourierAdaptation(spectrum_bank, p=c.get("p", 0.5), beta=c.get("beta", 0.01),
+                                         strength=strength * 2 if len(strength) == 1 else strength))
         elif key == "ColorJitterWithRandomBrightness":
             raise NotImplementedError("rtsds_amd.transforms: ColorJitterWithRandomBrightness is not implemented "
                                       "(the reference config has it commented out, config.yaml:118-123)")
@@ -244,11 +315,18 @@ def _sample_draws_styled(augment, h=None, w=None):
     """_sample_draws' four and, fifth, HistogramMatching's draw (None, or (its bank, k, A)), taken
     at the transform's position in the list; the matching itself acts on the decoded image,
     ahead of the blur and the jitter, wherever its key stands."""
+    return _sample_draws_all(augment, h, w)[:5]
+
+
+def _sample_draws_all(augment, h=None, w=None):
+    """_sample_draws_styled's five and, sixth, FourierAdaptation's draw (None, or (its bank, k,
+    strength)), taken at the transform's position in the list like the others; a list without
+    the transform draws nothing for it."""
     if augment is None or not augment.transforms:
-        return [], False, None, False, None
+        return [], False, None, False, None, None
     if augment.p < torch.rand(1):
-        return [], False, None, False, None
-    ops, flip, window, flip_label, style = [], False, None, False, None
+        return [], False, None, False, None, None
+    ops, flip, window, flip_label, style, spectral = [], False, None, False, None, None
     for t in augment.transforms:
         if isinstance(t, (GaussianBlur, ColorJitter)):
             ops.append((t, t.params()))
@@ -262,7 +340,10 @@ def _sample_draws_styled(augment, h=None, w=None):
         elif isinstance(t, HistogramMatching):
             drawn = t.params()
             style = None if drawn is None else (t.bank,) + drawn
-    return ops, flip, window, flip_label, style
+        elif isinstance(t, FourierAdaptation):
+            drawn = t.params()
+            spectral = None if drawn is None else (t,) + drawn
+    return ops, flip, window, flip_label, style, spectral
 
 
 def _decisions(augment):
@@ -395,6 +476,107 @@ class HistogramBank:
         return self.data[k]
 
 
+def _check_band_tensor(t, b, last, device, what):
+    shape = (3, 2 * b + 1, b + 1) + last
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or \
+            t.device != device:
+        raise RuntimeError(f"rtsds_amd.transforms: {what} must be a contiguous fp32 {list(shape)} tensor on the image's "
+                           "device")
+
+
+def _fda_spectrum(img, b, spec, amp):
+    h, w, c = img.shape
+    ws = workspace(lib.rtsds_fda_workspace(h, w, b), img.device)  # the row-stage partials
+    _check(lib.rtsds_fda_spectrum(img.data_ptr(), c, h, w, b, spec.data_ptr() if spec is not None else None,
+                                  amp.data_ptr() if amp is not None else None, ws.data_ptr(), ws.numel(), stream()),
+           "band spectrum")
+
+
+def band_spectrum(img, b, spec=None, amp=None):
+    """(spec, amp_norm) of a uint8 HWC [H, W, 3] device image: the DFT coefficients F(u, v) of the
+    band u = -b..b, v = 0..b as fp32 [3, 2b+1, b+1, 2] (re, im; the other half is the conjugate
+    mirror) and |F| / (H W) as fp32 [3, 2b+1, b+1], the size-independent form a SpectrumBank keeps
+    (rtsds_fda_spectrum; ``spec`` / ``amp`` are overwritten)."""
+    _check_rgb_u8(img, "band_spectrum")
+    b = int(b)
+    _check_band(img.shape[0], img.shape[1], b)
+    if spec is None:
+        spec = torch.empty((3, 2 * b + 1, b + 1, 2), dtype=torch.float32, device=img.device)
+    else:
+        _check_band_tensor(spec, b, (2,), img.device, "band_spectrum: spec")
+    if amp is None:
+        amp = torch.empty((3, 2 * b + 1, b + 1), dtype=torch.float32, device=img.device)
+    else:
+        _check_band_tensor(amp, b, (), img.device, "band_spectrum: amp")
+    _fda_spectrum(img, b, spec, amp)
+    return spec, amp
+
+
+def fourier_adapt(img, spec_src, amp_ref, strength=1.0, out=None, dtype=torch.uint8):
+    """``img`` (uint8 HWC [H, W, 3], device) with the amplitudes of its band ``spec_src``
+    (band_spectrum of the image) blended by ``strength`` in [0, 1] towards ``amp_ref`` (the
+    normalised amplitudes of a target image of any size), the phase kept (rtsds_fda_apply).  HWC
+    out, clamped to [0, 255]: uint8 (rounded half to even; ``out`` may be ``img``) or fp32."""
+    _check_rgb_u8(img, "fourier_adapt")
+    if dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError("rtsds_amd.transforms: fourier_adapt writes uint8 or fp32")
+    if not isinstance(spec_src, torch.Tensor) or spec_src.dim() != 4:
+        raise RuntimeError("rtsds_amd.transforms: fourier_adapt: spec_src must be the [3, 2b+1, b+1, 2] band of the image")
+    b = int(spec_src.shape[2]) - 1
+    h, w, c = img.shape
+    _check_band(h, w, b)
+    _check_band_tensor(spec_src, b, (2,), img.device, "fourier_adapt: spec_src")
+    _check_band_tensor(amp_ref, b, (), img.device, "fourier_adapt: amp_ref")
+    strength = float(strength)
+    if not 0.0 <= strength <= 1.0:
+        raise RuntimeError(f"rtsds_amd.transforms: a blend strength in [0, 1] expected, got {strength}")
+    if out is None:
+        out = torch.empty((h, w, c), dtype=dtype, device=img.device)
+    elif out is not img:
+        if not isinstance(out, torch.Tensor) or out.dtype != dtype or out.shape != img.shape or not out.is_contiguous() or \
+                out.device != img.device:
+            raise RuntimeError("rtsds_amd.transforms: fourier_adapt writes a contiguous image of the source's shape and "
+                               "device in the dtype asked for")
+    elif dtype != torch.uint8:
+        raise RuntimeError("rtsds_amd.transforms: fourier_adapt works in place in uint8 only")
+    _check(lib.rtsds_fda_apply(img.data_ptr(), out.data_ptr(), int(dtype == torch.uint8), c, h, w, b, spec_src.data_ptr(),
+                               amp_ref.data_ptr(), strength, stream()), "fourier adapt")
+    return out
+
+
+class SpectrumBank:
+    """The normalised band amplitudes |F| / (h w) of up to ``capacity`` target images on the device
+    (fp32 [capacity, 3, 2b+1, b+1]): a ring, the oldest entry is overwritten when full.  The
+    images may have any size the band fits in: an entry is in cycles per image."""
+
+    def __init__(self, capacity, b, device="cuda"):
+        if int(capacity) < 1:
+            raise ValueError("capacity should be positive.")
+        if not 1 <= int(b) <= FDA_MAX_BAND:
+            raise ValueError(f"b should be in [1, {FDA_MAX_BAND}].")
+        self.b = int(b)
+        self.data = torch.zeros((int(capacity), 3, 2 * self.b + 1, self.b + 1), dtype=torch.float32, device=device)
+        self._next = 0
+        self._filled = 0
+
+    def add(self, images):
+        """One entry per uint8 HWC device image, each written straight into its slot."""
+        for img in images:
+            _check_rgb_u8(img, "SpectrumBank.add")
+            _check_band(img.shape[0], img.shape[1], self.b)
+            _fda_spectrum(img, self.b, None, self.data[self._next])
+            self._next = (self._next + 1) % self.data.shape[0]
+            self._filled = min(self._filled + 1, self.data.shape[0])
+
+    def __len__(self):
+        return self._filled
+
+    def amp(self, k):
+        if not 0 <= k < self._filled:
+            raise IndexError(f"spectrum {k} of a bank of {self._filled}")
+        return self.data[k]
+
+
 def bank_indices(n, k):
     """The min(n, k) dataset indices floor(i * n / min(n, k)): an even spread over n samples."""
     m = min(int(n), int(k))
@@ -419,6 +601,7 @@ class ImagePipeline:
         self.augment = augment
         self.last_geometry = None  # per sample of the last batch: None or a Geometry
         self.last_style = None  # per sample of the last batch: None or HistogramMatching's (k, A)
+        self.last_spectral = None  # per sample of the last batch: None or FourierAdaptation's (k, strength)
         self._ms = {}
 
     def _mean_std(self, device):
@@ -437,14 +620,20 @@ class ImagePipeline:
         kind = 1 if dtype == torch.bfloat16 else 0
         self.last_geometry = geometry = []
         self.last_style = styles = []
+        self.last_spectral = spectrals = []
         for n, img in enumerate(images):
             img = _as_hwc_u8(img)
             h, w, c = img.shape
-            ops, flip, window, flip_label, style = _sample_draws_styled(self.augment, h, w)
+            ops, flip, window, flip_label, style, spectral = _sample_draws_all(self.augment, h, w)
             styles.append(style and style[1:])
+            spectrals.append(spectral and spectral[1:])
             if style is not None:  # matched into a fresh image: the caller's stays as it is
                 bank, k, a = style
                 img = _hist_match_q8(img, image_histogram(img), bank.hist(k), a)
+            if spectral is not None:  # after the matching; in place only in the pipeline's own copy
+                fda, k, s = spectral
+                spec, _ = band_spectrum(img, fda.band(h, w))
+                img = fourier_adapt(img, spec, fda.bank.amp(k), s, out=img if style is not None else None)
             src, src_u8 = img, 1
             if window == (0, 0, h, w):  # the whole image is no window: the plain resize, for the label too
                 window = None
@@ -584,6 +773,6 @@ def parse_size(s):
 
 
 __all__ = ["ImagePipeline", "LabelPipeline", "DeviceLoader", "GaussianBlur", "RandomHorizontalFlip", "ColorJitter",
-           "RandomResizedCrop", "HistogramMatching", "HistogramBank", "RandomApply", "Geometry", "augmentation_loader",
-           "color_jitter", "image_histogram", "histogram_match", "bank_indices", "decode_gta5_labels", "collate_raw",
-           "parse_size"]
+           "RandomResizedCrop", "HistogramMatching", "HistogramBank", "FourierAdaptation", "SpectrumBank", "RandomApply",
+           "Geometry", "augmentation_loader", "color_jitter", "image_histogram", "histogram_match", "band_spectrum",
+           "fourier_adapt", "bank_indices", "decode_gta5_labels", "collate_raw", "parse_size"]
