@@ -503,6 +503,25 @@ int rtsds_upsample_pseudo(const void* x, uint8_t* pred, uint16_t* cbin, const in
                           int n, int hi, int wi, int c, int ho, int wo, float scale_h, float scale_w,
                           int bins, int ignore_index, int dtype, void* stream);
 
+/* ---------------------------------------------------------------- prediction (painted frames)
+ * No counterpart in the reference (it never writes a prediction out).
+ * rtsds_upsample_paint: the low-resolution head x (NHWC [n][hi][wi][c], fp32 or bf16, geometry as
+ *   rtsds_upsoftmax_acc) -> a class map and a coloured frame at the output size in one pass.  Per
+ *   output pixel p the resized logits are formed as rtsds_bilinear_fwd stores them (the blend of
+ *   the four taps rounded to the storage type) and k = their argmax over classes, first maximum
+ *   wins, NaN handled as rtsds_argmax does; no softmax (it does not move the argmax).  k equals
+ *   the chain rtsds_bilinear_fwd -> rtsds_argmax bit for bit; the resized logits are never written.
+ *   ids[p] (uint8 [n][ho][wo], may be NULL) = lut ? lut[k] : k, lut = c device bytes (train id ->
+ *   label id).  rgb[p][j] (uint8 HWC [n][ho][wo][3], may be NULL, not both) = palette[k][j] when
+ *   alpha_q8 == 256, else (alpha_q8 * palette[k][j] + (256 - alpha_q8) * frame[p][j] + 128) >> 8 in
+ *   integers (reproducible on the host bit for bit; alpha_q8 = 0 returns the frame); palette =
+ *   device uint8 [c][3], frame = uint8 HWC [n][ho][wo][3] (may be NULL when alpha_q8 == 256 or
+ *   rgb is NULL).  No alignment is asked of any byte buffer.  2 <= c <= 32, 0 <= alpha_q8 <= 256.
+ *   No synchronisation, allocation or host access (graph-capture safe).                       */
+int rtsds_upsample_paint(const void* x, const uint8_t* frame, const uint8_t* palette, const uint8_t* lut,
+                         uint8_t* ids, uint8_t* rgb, int n, int hi, int wi, int c, int ho, int wo,
+                         float scale_h, float scale_w, int alpha_q8, int dtype, void* stream);
+
 /* ---------------------------------------------------------------- ClassMix (self-training)
  * No counterpart in the reference.  ClassMix (DACS, DAFormer) pastes the pixels of half of the
  * classes of a labelled source image, image and label, onto a target image; here the rest of
@@ -691,7 +710,7 @@ int rtsds_pooled_mlp_fwd(const void* p, const void* w1, const float* b1, const v
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 19
+#define RTSDS_ABI_VERSION 20
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

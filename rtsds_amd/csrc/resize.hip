@@ -1,6 +1,6 @@
 // Bilinear resize (align_corners=False), forward and backward, and the kernels fused onto it
 // (gfx950): resize + softmax for the discriminator input, multi-scale / flip evaluation, the
-// online teacher's pseudo-labels.
+// online teacher's pseudo-labels, the painted frames of prediction.
 // Every output bit of the unit is pinned (tests/test_resize_bits_gpu.py), and each piece that
 // carries a bit-exactness promise exists once:
 //   bil_src / bil_mix / bil_first_ge (common.h)   taps, weights, the blend's association
@@ -10,6 +10,7 @@
 //   bil_table_build, bil_table_span, BilTables    backward: the weight tables in LDS
 //   bil_bwd_h_launch                              the vertical pass (bilinear and resize + softmax backward)
 //   upsm_tile, upsm_probs                         resize + softmax: one tile's staging, one pixel's probabilities
+//   upsm_logit                                    one class of one pixel's resized logits, for on-the-fly reductions
 #include "ew_common.h"
 
 // ------------------------------------------------------------------ bilinear (align_corners=False)
@@ -623,6 +624,29 @@ RT_DEV UpsmTile<T> upsm_tile(const T* __restrict__ x, float* src, int hi, int wi
   }
   return t;
 }
+// class k of one output pixel's resized logits, upsm_probs' z[k] ahead of its exp: bil_mix of the
+// four taps (column taps w0 / w1 of the staged rows, or of r0 / r1), rounded to T as
+// rtsds_bilinear_fwd stores it and widened again.  For kernels that reduce the classes on the fly
+// (upsample_paint_kernel).  upsm_probs keeps its own copy of the eight tap reads: calling this
+// from it left every staged kernel's code as it was but gave the unstaged ones 64-bit address
+// arithmetic per tap (v_lshl_add_u64 11 -> 135 in upsoftmax_acc_kernel<float, false, 0>).
+template <typename T, bool STAGED>
+RT_DEV float upsm_logit(const T* __restrict__ r0, const T* __restrict__ r1, const float* src, int wlo, int n1, int c, int k, int w0,
+                        int w1, float lh0, float lh1, float lw0, float lw1) {
+  float p00, p01, p10, p11;
+  if (STAGED) {
+    p00 = src[(w0 - wlo) * c + k];
+    p01 = src[(w1 - wlo) * c + k];
+    p10 = src[n1 + (w0 - wlo) * c + k];
+    p11 = src[n1 + (w1 - wlo) * c + k];
+  } else {
+    p00 = to_f(r0[(long)w0 * c + k]);
+    p01 = to_f(r0[(long)w1 * c + k]);
+    p10 = to_f(r1[(long)w0 * c + k]);
+    p11 = to_f(r1[(long)w1 * c + k]);
+  }
+  return to_f(from_f<T>(bil_mix(p00, p01, p10, p11, lh0, lh1, lw0, lw1)));
+}
 // one output pixel's blend + softmax, shared by upsoftmax_fwd_kernel and upsoftmax_acc_kernel:
 // on return the probability of class k is the fp32 product z[k] * iz
 template <typename T, bool STAGED, int CC>
@@ -828,6 +852,68 @@ __global__ void __launch_bounds__(256) upsample_pseudo_kernel(const T* __restric
   if (cbin) cbin[p] = (uint16_t)b;
   if (labels) labels[p] = b >= tbin[bi] ? bi : ignore;
 }
+// ------------------------------------------------------------------ low-resolution head -> painted frame
+// The output side of inference (predict.Predictor): the same tile, but no softmax -- k = arg-max
+// of the resized logits (upsm_logit: what rtsds_bilinear_fwd would store) by argmax_kernel's rule
+// (first maximum wins, a NaN beats every number and the first NaN wins), a running maximum, so
+// ids equal the chain rtsds_bilinear_fwd -> rtsds_argmax bit for bit and the full-resolution
+// logits never exist.  ids[p] = lut[k] (k without a lut); rgb[p] = palette[k], blended over the
+// frame in integers: (alpha * palette + (256 - alpha) * frame + 128) >> 8, alpha in [0, 256].
+// Palette and lut (<= 96 + 32 B) sit in LDS behind the staged rows.  The 3-byte pixels of a tile
+// are contiguous (768 B) at any byte phase: every lane reads its pixel's 3 frame bytes and writes
+// its 3 output bytes itself, a wave covering 192 contiguous bytes per access.  (Routing both
+// tiles through LDS as 16-B chunks with single head / tail bytes, upsm_tile_copy's way, measured
+// 1.0 - 4.6 us slower per call at every shape, profiles/paint: a second barrier, 48 active lanes
+// per copy, and the kernel is bound by the class loop, not by its stores.)
+static const int kPaintTab = 4 * kUpsmMaxC;  // bytes: palette [c][3], then lut [c]
+template <typename T, bool STAGED, int CC>  // CC > 0: compile-time class count (19), 0: runtime c
+__global__ void __launch_bounds__(256) upsample_paint_kernel(const T* __restrict__ x, const uint8_t* __restrict__ frame,
+                                                             const uint8_t* __restrict__ palette, const uint8_t* __restrict__ lut,
+                                                             uint8_t* __restrict__ ids, uint8_t* __restrict__ rgb, int hi, int wi,
+                                                             int c_, int ho, int wo, float sh, float sw, int alpha, int tiles) {
+  const int c = CC > 0 ? CC : c_;
+  extern __shared__ __attribute__((aligned(16))) float src[];  // STAGED: [2][ncols][c]
+  const int tid = threadIdx.x;
+  const UpsmTile<T> tl = upsm_tile<T, STAGED>(x, src, hi, wi, c, ho, wo, sh, sw, tiles);
+  uint8_t* pal = (uint8_t*)(src + ((2 * tl.n1 + 3) & ~3));  // 16-B aligned
+  uint8_t* idt = pal + 3 * kUpsmMaxC;
+  if (rgb != nullptr && tid < 3 * c) pal[tid] = palette[tid];
+  if (tid >= 128 && tid - 128 < c) idt[tid - 128] = lut != nullptr ? lut[tid - 128] : (uint8_t)(tid - 128);
+  const bool blend = rgb != nullptr && alpha < 256;
+  const long p = tl.row * wo + tl.ow0 + tid;  // this lane's pixel (tid < np)
+  int f0 = 0, f1 = 0, f2 = 0;
+  if (blend && tid < tl.np) {  // issued ahead of the barrier and the class loop
+    const uint8_t* f = frame + 3 * p;
+    f0 = f[0], f1 = f[1], f2 = f[2];
+  }
+  __syncthreads();
+  if (tid >= tl.np) return;  // no barrier below
+  int w0, w1;
+  float lw0, lw1;
+  bil_src(tl.ow0 + tid, sw, wi, w0, w1, lw0, lw1);
+  float best = 0.f;
+  int bi = 0;
+#pragma unroll
+  for (int k = 0; k < kUpsmMaxC; ++k)
+    if (k < c) {
+      const float v = upsm_logit<T, STAGED>(tl.r0, tl.r1, src, tl.wlo, tl.n1, c, k, w0, w1, tl.lh0, tl.lh1, lw0, lw1);
+      if (k == 0 || v > best || (v != v && best == best)) {
+        best = v;
+        bi = k;
+      }
+    }
+  if (ids != nullptr) ids[p] = idt[bi];
+  if (rgb != nullptr) {
+    int q0 = pal[3 * bi], q1 = pal[3 * bi + 1], q2 = pal[3 * bi + 2];
+    if (blend) {
+      q0 = (alpha * q0 + (256 - alpha) * f0 + 128) >> 8;
+      q1 = (alpha * q1 + (256 - alpha) * f1 + 128) >> 8;
+      q2 = (alpha * q2 + (256 - alpha) * f2 + 128) >> 8;
+    }
+    uint8_t* o = rgb + 3 * p;
+    o[0] = (uint8_t)q0, o[1] = (uint8_t)q1, o[2] = (uint8_t)q2;
+  }
+}
 template <typename T, int CC>  // CC > 0: compile-time class count (19), 0: runtime c
 __global__ void __launch_bounds__(256) upsoftmax_bwd_w_kernel(const T* __restrict__ dy, int dyld, const T* __restrict__ y,
                                                               int yld, float* __restrict__ tmp, int wi, int c_, int wo, float sw,
@@ -984,6 +1070,27 @@ extern "C" int rtsds_upsample_pseudo(const void* x, uint8_t* pred, uint16_t* cbi
   DISPATCH_T(dtype, upsm_dispatch(staged, c, [&](auto s, auto cc) {
     hipLaunchKernelGGL((upsample_pseudo_kernel<T, decltype(s)::value, decltype(cc)::value>), dim3(p.blocks), dim3(256), lds, st,
                        (const T*)x, pred, cbin, tbin, labels, hi, wi, c, ho, wo, scale_h, scale_w, bins, ignore_index, p.tiles);
+  }));
+  RET_LAUNCH();
+}
+extern "C" int rtsds_upsample_paint(const void* x, const uint8_t* frame, const uint8_t* palette, const uint8_t* lut, uint8_t* ids,
+                                    uint8_t* rgb, int n, int hi, int wi, int c, int ho, int wo, float scale_h, float scale_w,
+                                    int alpha_q8, int dtype, void* stream) {
+  if (c < 2) return RTSDS_ERR_SHAPE;  // (c > 32: upsm_plan)
+  if (alpha_q8 < 0 || alpha_q8 > 256) return RTSDS_ERR_SHAPE;
+  UpsmPlan p;
+  if (const int rc = upsm_plan(n, hi, wi, c, ho, wo, scale_w, p)) return rc;
+  if (x == nullptr || (ids == nullptr && rgb == nullptr) || (rgb != nullptr && palette == nullptr) ||
+      (rgb != nullptr && alpha_q8 < 256 && frame == nullptr))
+    return RTSDS_ERR_UNSUPPORTED;
+  // LDS: the staged source rows (whenever they fit the 64 KiB a workgroup gets without opting in to
+  // more), then the palette / lut table
+  const bool staged = p.taps + 16 + kPaintTab <= (size_t)64 * 1024;
+  const size_t lds = (staged ? p.taps + 16 : 0) + kPaintTab;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_T(dtype, upsm_dispatch(staged, c, [&](auto s, auto cc) {
+    hipLaunchKernelGGL((upsample_paint_kernel<T, decltype(s)::value, decltype(cc)::value>), dim3(p.blocks), dim3(256), lds, st,
+                       (const T*)x, frame, palette, lut, ids, rgb, hi, wi, c, ho, wo, scale_h, scale_w, alpha_q8, p.tiles);
   }));
   RET_LAUNCH();
 }

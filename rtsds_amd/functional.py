@@ -1740,6 +1740,54 @@ def upsample_pseudo(x, geo, bins=1024, tbin=None, ignore_index=None, pred=None, 
     return pred, cbin, labels
 
 
+def upsample_paint(x, geo, palette=None, alpha=1.0, frame=None, lut=None, ids=None, rgb=None, want_ids=True):
+    """A class map and a painted frame straight from a low-resolution head (rtsds_upsample_paint):
+    k = argmax_channels(interpolate_geometry(x, geo)) bit for bit, in one pass, without the
+    full-resolution logits.  ``x``: the head [n, c, hi, wi] (2..32 classes), ``geo`` from
+    upsample_geometry().  ``ids`` (uint8 [n, H, W]; allocated when ``want_ids`` and not given)
+    receives lut[k], or k without ``lut`` (uint8 [c] on the device).  With ``palette`` (uint8
+    [c, 3] on the device) ``rgb`` (uint8 [n, H, W, 3]; allocated unless given) receives
+    palette[k], blended over ``frame`` (uint8 [n, H, W, 3]) when ``alpha`` < 1:
+    (A * palette[k] + (256 - A) * frame + 128) >> 8 with A = floor(alpha * 256 + 0.5), in integers.
+    Inference only, no host sync.  Returns (ids, rgb), None for an output not produced."""
+    fn = "upsample_paint"
+    given = [t for t in (palette, frame, lut, ids, rgb) if t is not None]
+    if not x.is_cuda or not all(t.is_cuda for t in given):
+        raise RuntimeError(f"rtsds_amd: {fn}: x and every buffer must be HIP tensors; there is no CPU fallback")
+    if x.dim() != 4 or x.numel() == 0 or not 2 <= x.shape[1] <= 32:
+        raise RuntimeError(f"rtsds_amd: {fn}: x must be [n, c, hi, wi] with 2..32 classes, got {tuple(x.shape)}")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"rtsds_amd: {fn}: x must be fp32 or bf16, got {x.dtype}")
+    from .transforms import _strength_q8  # (transforms imports this module)
+    try:
+        a = _strength_q8(float(alpha))
+    except RuntimeError:
+        raise RuntimeError(f"rtsds_amd: {fn}: alpha must lie in [0, 1], got {alpha}") from None
+    x = nhwc(x.detach())
+    n, c, hi, wi = x.shape
+    ho, wo, sh, sw = geo
+    dev = x.device
+    if palette is None and rgb is not None:
+        raise RuntimeError(f"rtsds_amd: {fn}: rgb needs a palette")
+    if palette is None and not (want_ids or ids is not None):
+        raise RuntimeError(f"rtsds_amd: {fn}: nothing to produce (no palette and no ids)")
+    if palette is not None:
+        _pseudo_arg(fn, "palette", palette, torch.uint8, (c, 3), dev)
+        if a < 256 and frame is None:
+            raise RuntimeError(f"rtsds_amd: {fn}: alpha < 1 needs the frame to blend over")
+        if rgb is None:
+            rgb = torch.empty((n, ho, wo, 3), dtype=torch.uint8, device=dev)
+    if ids is None and want_ids:
+        ids = torch.empty((n, ho, wo), dtype=torch.uint8, device=dev)
+    for name, t, shape in (("frame", frame, (n, ho, wo, 3)), ("lut", lut, (c,)), ("ids", ids, (n, ho, wo)),
+                           ("rgb", rgb, (n, ho, wo, 3))):
+        if t is not None:
+            _pseudo_arg(fn, name, t, torch.uint8, shape, dev)
+    lib.rtsds_upsample_paint(_P(x), _P(frame), _P(palette), _P(lut), _P(ids), _P(rgb), n, hi, wi, c, ho, wo, sh, sw, a,
+                             dcode(x), stream())
+    return ids, rgb
+
+
 def ema_step(teacher, student, w, shadow=None):
     """Mean-teacher update of one flat fp32 buffer (rtsds_ema_step): teacher += w * (student -
     teacher) as three separately rounded fp32 operations, ``w`` rounded to fp32 here; ``shadow``
