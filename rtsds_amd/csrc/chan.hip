@@ -2,6 +2,7 @@
 // (chan_* reductions, ffm_head_eval), then the per-pixel class-vector ops -- channel softmax,
 // cross-entropy with ignore_index, BCE-with-logits, argmax / pixel accuracy, confusion.
 #include "ew_common.h"
+#include "class_row.h"
 
 // ------------------------------------------------------------------ global average pool
 // y[img][c] = mean_hw x[img][hw][c]   (AdaptiveAvgPool2d(1) / torch.mean over H,W:
@@ -79,14 +80,11 @@ __global__ void __launch_bounds__(256) chan_part_kernel(const T* __restrict__ a,
       if (ch0 + j < c) part[((long)img * S + s) * c + ch0 + j] = acc[j];
   }
 }
-template <typename T>
-__global__ void __launch_bounds__(256) chan_final_kernel(const float* __restrict__ part, T* __restrict__ out, int S, int c, float scale) {
-  const int img = blockIdx.y, ch = blockIdx.x * 256 + threadIdx.x;
-  if (ch >= c) return;
-  const float* p = part + (long)img * S * c + ch;
+// p[0], p[c], .. p[(S - 1) c] summed in slice order, 8 loads in flight
+RT_DEV float slice_sum(const float* __restrict__ p, int S, int c) {
   float s = 0.f;
   int q = 0;
-  for (; q + 8 <= S; q += 8) {  // 8 slices in flight, summed in order
+  for (; q + 8 <= S; q += 8) {
     float t[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) t[u] = p[(long)(q + u) * c];
@@ -94,7 +92,13 @@ __global__ void __launch_bounds__(256) chan_final_kernel(const float* __restrict
     for (int u = 0; u < 8; ++u) s += t[u];
   }
   for (; q < S; ++q) s += p[(long)q * c];
-  out[(long)img * c + ch] = from_f<T>(s * scale);
+  return s;
+}
+template <typename T>
+__global__ void __launch_bounds__(256) chan_final_kernel(const float* __restrict__ part, T* __restrict__ out, int S, int c, float scale) {
+  const int img = blockIdx.y, ch = blockIdx.x * 256 + threadIdx.x;
+  if (ch >= c) return;
+  out[(long)img * c + ch] = from_f<T>(slice_sum(part + (long)img * S * c + ch, S, c) * scale);
 }
 extern "C" size_t rtsds_gap_workspace(int n, long hw, int c) {
   if (n <= 0 || hw <= 0 || c <= 0) return 256;
@@ -225,19 +229,8 @@ __global__ void __launch_bounds__(256) ffm_head_apply_kernel(const float* __rest
   const int nvec = np * C / V;
   const V16* src = (const V16*)(fi + (long)p0 * C);
   for (int e = tid; e < nvec; e += 256) ((V16*)stage)[e] = src[e];
-  if (tid < C) {  // GAP: the slices' partials summed in order (chan_final_kernel's order)
-    const float* pp = part + (long)img * S * C + tid;
-    float t = 0.f;
-    int q = 0;
-    for (; q + 8 <= S; q += 8) {
-      float u[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) u[k] = pp[(long)(q + k) * C];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) t += u[k];
-    }
-    for (; q < S; ++q) t += pp[(long)q * C];
-    gap[tid] = to_f(from_f<T>(t * (1.f / (float)hw)));
+  if (tid < C) {  // GAP: chan_final_kernel's sum
+    gap[tid] = to_f(from_f<T>(slice_sum(part + (long)img * S * C + tid, S, C) * (1.f / (float)hw)));
     bias3[tid] = b3 ? b3[tid] : 0.f;
   }
   __syncthreads();
@@ -309,91 +302,73 @@ extern "C" int rtsds_chscale_bwd(const void* dy, const void* x, const void* a, v
   RET_LAUNCH();
 }
 
-// Staged variants need NHWC-contiguous logits with c <= kStageMaxC.
+// ------------------------------------------------------------------ per-pixel class-vector ops
+// Each op is one per-pixel body over row views (class_row.h) and runs in two shells.  Logits are
+// addressed by (sn, sc, shw) strides, so NHWC and NCHW tensors both work: a grid-stride loop, one
+// thread per pixel straight from global memory at pixel_offset().  NHWC-contiguous logits with
+// c <= kStageMaxC take the staged tile loop (STAGE_TILES / tile_in / tile_out, ew_common.h) and the
+// body runs on dense LDS rows.
 static const int kStageMaxC = 64;
 static inline bool stage_ok(long sn, long sc, long shw, long hw, int c) {
   return sc == 1 && shw == c && sn == hw * c && c <= kStageMaxC;
 }
+// element offset of pixel p's logits
+RT_DEV long pixel_offset(long p, long hw, long sn, long shw) {
+  const long img = p / hw, s = p - img * hw;
+  return img * sn + s * shw;
+}
 
+// ------------------------------------------------------------------ channel softmax (dim=1)
+// train.py:225,245,256.  Output NHWC contiguous with row pitch yld (zero-padded channels
+// c..yld-1 so a padded discriminator input can be produced directly).
+template <typename RI, typename RO>
+RT_DEV void px_softmax(RI x, RO y, int c) {
+  const float m = row_max(x, c);
+  const float iz = 1.f / row_sum_exp(x, c, m);
+  for (int k = 0; k < c; ++k) y[k] = from_f<typename RO::elem>(expf(x(k) - m) * iz);
+}
+// dx = y * (dy - sum_k dy_k y_k); dy/y have row pitch ld (>= c), dx strided like the logits.
+template <typename RG, typename RY, typename RO>
+RT_DEV void px_softmax_bwd(RG g, RY y, RO dx, int c) {
+  float dot = 0.f;
+  for (int k = 0; k < c; ++k) dot = fmaf(g(k), y(k), dot);
+  for (int k = 0; k < c; ++k) dx[k] = from_f<typename RO::elem>(y(k) * (g(k) - dot));
+}
 template <typename T>
 __global__ void __launch_bounds__(256) softmax_fwd_staged(const T* __restrict__ x, T* __restrict__ y, long total, int c) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* buf = (T*)smem_raw;
-  for (long p0 = (long)blockIdx.x * kStagePix; p0 < total; p0 += (long)gridDim.x * kStagePix) {
-    const int np = (int)min<long>(kStagePix, total - p0);
-    __syncthreads();
-    stage_in(x + p0 * c, buf, np * c);
-    __syncthreads();
-    if ((int)threadIdx.x < np) {
-      T* r = buf + threadIdx.x * c;
-      float m = -INFINITY;
-      for (int k = 0; k < c; ++k) m = fmaxf(m, to_f(r[k]));
-      float z = 0.f;
-      for (int k = 0; k < c; ++k) z += expf(to_f(r[k]) - m);
-      const float iz = 1.f / z;
-      for (int k = 0; k < c; ++k) r[k] = from_f<T>(expf(to_f(r[k]) - m) * iz);
-    }
-    __syncthreads();
-    stage_out(y + p0 * c, buf, np * c);
+  T* buf = stage_buf<T>();
+  STAGE_TILES(p0, total) {
+    const int np = tile_in(buf, p0, total, c, x);
+    T* r = buf + threadIdx.x * c;
+    if ((int)threadIdx.x < np) px_softmax(dense_row(r), dense_row(r), c);
+    tile_out(y, buf, p0, np, c);
+  }
+}
+template <typename T>
+__global__ void softmax_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int n, long hw, int c, long sn, long sc, long shw, int yld) {
+  const long total = (long)n * hw;
+  GRID_STRIDE(p, total) {
+    T* o = y + p * yld;
+    px_softmax(strided_row(x + pixel_offset(p, hw, sn, shw), sc), dense_row(o), c);
+    for (int k = c; k < yld; ++k) o[k] = from_f<T>(0.f);
   }
 }
 template <typename T>
 __global__ void __launch_bounds__(256) softmax_bwd_staged(const T* __restrict__ dy, const T* __restrict__ y, T* __restrict__ dx, long total, int c) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* bg = (T*)smem_raw;
-  T* by = bg + kStagePix * c;
-  for (long p0 = (long)blockIdx.x * kStagePix; p0 < total; p0 += (long)gridDim.x * kStagePix) {
-    const int np = (int)min<long>(kStagePix, total - p0);
-    __syncthreads();
-    stage_in(dy + p0 * c, bg, np * c);
-    stage_in(y + p0 * c, by, np * c);
-    __syncthreads();
-    if ((int)threadIdx.x < np) {
-      T* g = bg + threadIdx.x * c;
-      const T* yy = by + threadIdx.x * c;
-      float dot = 0.f;
-      for (int k = 0; k < c; ++k) dot = fmaf(to_f(g[k]), to_f(yy[k]), dot);
-      for (int k = 0; k < c; ++k) g[k] = from_f<T>(to_f(yy[k]) * (to_f(g[k]) - dot));
-    }
-    __syncthreads();
-    stage_out(dx + p0 * c, bg, np * c);
+  T* buf = stage_buf<T>();  // [2][kStagePix][c]: dy (dx in place), y
+  STAGE_TILES(p0, total) {
+    const int np = tile_in(buf, p0, total, c, dy, y);
+    T* g = buf + threadIdx.x * c;
+    if ((int)threadIdx.x < np) px_softmax_bwd(dense_row(g), dense_row((const T*)g + kStagePix * c), dense_row(g), c);
+    tile_out(dx, buf, p0, np, c);
   }
 }
-
-// ------------------------------------------------------------------ channel softmax (dim=1)
-// train.py:225,245,256.  One thread per pixel; logits addressed by (sn, sc, shw) strides so
-// NHWC and NCHW tensors both work.  Output NHWC contiguous with row pitch yld (zero-padded
-// channels c..yld-1 so a padded discriminator input can be produced directly).
-template <typename T, typename O>
-__global__ void softmax_fwd_kernel(const T* __restrict__ x, O* __restrict__ y, int n, long hw, int c, long sn, long sc, long shw, int yld) {
-  const long total = (long)n * hw;
-  GRID_STRIDE(p, total) {
-    const long img = p / hw, s = p - img * hw;
-    const T* b = x + img * sn + s * shw;
-    float m = -INFINITY;
-    for (int k = 0; k < c; ++k) m = fmaxf(m, to_f(b[k * sc]));
-    float z = 0.f;
-    for (int k = 0; k < c; ++k) z += expf(to_f(b[k * sc]) - m);
-    const float iz = 1.f / z;
-    O* o = y + p * yld;
-    for (int k = 0; k < c; ++k) o[k] = from_f<O>(expf(to_f(b[k * sc]) - m) * iz);
-    for (int k = c; k < yld; ++k) o[k] = from_f<O>(0.f);
-  }
-}
-// dx = y * (dy - sum_k dy_k y_k); dy/y have row pitch ld (>= c), dx strided like the logits.
-template <typename T, typename O>
-__global__ void softmax_bwd_kernel(const O* __restrict__ dy, const O* __restrict__ y, T* __restrict__ dx, int n, long hw, int c, int ld,
+template <typename T>
+__global__ void softmax_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y, T* __restrict__ dx, int n, long hw, int c, int ld,
                                    long sn, long sc, long shw) {
   const long total = (long)n * hw;
-  GRID_STRIDE(p, total) {
-    const long img = p / hw, s = p - img * hw;
-    const O* g = dy + p * ld;
-    const O* yy = y + p * ld;
-    float dot = 0.f;
-    for (int k = 0; k < c; ++k) dot = fmaf(to_f(g[k]), to_f(yy[k]), dot);
-    T* o = dx + img * sn + s * shw;
-    for (int k = 0; k < c; ++k) o[k * sc] = from_f<T>(to_f(yy[k]) * (to_f(g[k]) - dot));
-  }
+  GRID_STRIDE(p, total)
+    px_softmax_bwd(dense_row(dy + p * ld), dense_row(y + p * ld), strided_row(dx + pixel_offset(p, hw, sn, shw), sc), c);
 }
 extern "C" int rtsds_softmax_fwd(const void* x, long sn, long sc, long shw, void* y, int y_ld, int n, long hw, int c, int dtype,
                                  void* stream) {
@@ -403,7 +378,7 @@ extern "C" int rtsds_softmax_fwd(const void* x, long sn, long sc, long shw, void
       hipLaunchKernelGGL(softmax_fwd_staged<T>, dim3(ew_blocks((long)n * hw, kStagePix, 4096)), dim3(256), kStagePix * c * sizeof(T),
                          (hipStream_t)stream, (const T*)x, (T*)y, (long)n * hw, c);
     else
-      hipLaunchKernelGGL((softmax_fwd_kernel<T, T>), dim3(ew_blocks((long)n * hw)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, hw, c, sn, sc, shw, y_ld);
+      hipLaunchKernelGGL(softmax_fwd_kernel<T>, dim3(ew_blocks((long)n * hw)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, n, hw, c, sn, sc, shw, y_ld);
   });
   RET_LAUNCH();
 }
@@ -415,7 +390,7 @@ extern "C" int rtsds_softmax_bwd(const void* dy, const void* y, int ld, void* dx
       hipLaunchKernelGGL(softmax_bwd_staged<T>, dim3(ew_blocks((long)n * hw, kStagePix, 4096)), dim3(256), 2 * kStagePix * c * sizeof(T),
                          (hipStream_t)stream, (const T*)dy, (const T*)y, (T*)dx, (long)n * hw, c);
     else
-      hipLaunchKernelGGL((softmax_bwd_kernel<T, T>), dim3(ew_blocks((long)n * hw)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)y, (T*)dx, n, hw, c, ld, sn, sc, shw);
+      hipLaunchKernelGGL(softmax_bwd_kernel<T>, dim3(ew_blocks((long)n * hw)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (const T*)y, (T*)dx, n, hw, c, ld, sn, sc, shw);
   });
   RET_LAUNCH();
 }
@@ -424,46 +399,87 @@ extern "C" int rtsds_softmax_bwd(const void* dy, const void* y, int ld, void* dx
 // nn.CrossEntropyLoss(ignore_index=19) (main.py:124-130, train.py:86-92,202-204): mean over
 // non-ignored pixels of logsumexp(x) - x[t].  Two passes for the forward (per-block partial
 // (sum, count) -> final), one fused pass for the backward.
-// ws layout: [0, RB) partial sums, [RB, 2RB) partial counts, [2RB] total count.
+// ws layout: [0, RB) partial sums, [RB, 2RB) partial counts, [2RB] total count, [2RB + 1] total sum.
 static const int kCeRB = 1024;
+// One non-ignored pixel's loss; a target outside [0, c) gives NaN.
+template <typename R>
+RT_DEV float px_ce_loss(R x, long t, int c) {
+  const float m = row_max(x, c), z = row_sum_exp(x, c, m);
+  const float xt = (t >= 0 && t < c) ? x(t) : NAN;
+  return logf(z) + m - xt;
+}
+// dx = g * (softmax - onehot), zeros for an ignored pixel.  The two routes round differently and
+// both are pinned: the strided one scales the probability (GZ = false), the staged one folds g
+// into 1 / z first (GZ = true).
+template <bool GZ, typename RI, typename RO>
+RT_DEV void px_ce_grad(RI x, RO dx, long t, int c, int ignore, float g) {
+  typedef typename RO::elem T;
+  if (t == ignore) {
+    for (int k = 0; k < c; ++k) dx[k] = from_f<T>(0.f);
+    return;
+  }
+  const float m = row_max(x, c), z = row_sum_exp(x, c, m);
+  if (GZ) {
+    const float gz = g / z;
+    for (int k = 0; k < c; ++k) dx[k] = from_f<T>(gz * expf(x(k) - m) - (k == t ? g : 0.f));
+  } else {
+    const float iz = 1.f / z;
+    for (int k = 0; k < c; ++k) {
+      const float pr = expf(x(k) - m) * iz;
+      dx[k] = from_f<T>(g * (pr - (k == t ? 1.f : 0.f)));
+    }
+  }
+}
+// the block's (sum, count), both wave sums ahead of the exchanges
+RT_DEV void ce_block_sums(float& s, float& cnt) {
+  __shared__ float red[4];
+  s = wave_sum(s);
+  cnt = wave_sum(cnt);
+  s = waves_sum4(s, red);
+  cnt = waves_sum4(cnt, red);
+}
+RT_DEV void ce_part_store(float s, float cnt, float* __restrict__ part) {
+  ce_block_sums(s, cnt);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = s;
+    part[kCeRB + blockIdx.x] = cnt;
+  }
+}
 template <typename T>
 __global__ void ce_fwd_part_kernel(const T* __restrict__ x, const int64_t* __restrict__ tgt, float* __restrict__ part, int n, long hw, int c,
                                    long sn, long sc, long shw, int ignore) {
-  __shared__ float rs[4], rc[4];
   const long total = (long)n * hw;
   float ls = 0.f, lc = 0.f;
   GRID_STRIDE(p, total) {
     const long t = tgt[p];
     if (t == ignore) continue;
-    const long img = p / hw, s = p - img * hw;
-    const T* b = x + img * sn + s * shw;
-    float m = -INFINITY;
-    for (int k = 0; k < c; ++k) m = fmaxf(m, to_f(b[k * sc]));
-    float z = 0.f;
-    for (int k = 0; k < c; ++k) z += expf(to_f(b[k * sc]) - m);
-    const float xt = (t >= 0 && t < c) ? to_f(b[t * sc]) : NAN;
-    ls += logf(z) + m - xt;
+    ls += px_ce_loss(strided_row(x + pixel_offset(p, hw, sn, shw), sc), t, c);
     lc += 1.f;
   }
-  ls = wave_sum(ls);
-  lc = wave_sum(lc);
-  if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = ls; rc[threadIdx.x >> 6] = lc; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[blockIdx.x] = rs[0] + rs[1] + rs[2] + rs[3];
-    part[kCeRB + blockIdx.x] = rc[0] + rc[1] + rc[2] + rc[3];
+  ce_part_store(ls, lc, part);
+}
+template <typename T>
+__global__ void __launch_bounds__(256) ce_fwd_part_staged(const T* __restrict__ x, const int64_t* __restrict__ tgt, float* __restrict__ part,
+                                                          long total, int c, int ignore) {
+  T* buf = stage_buf<T>();
+  float ls = 0.f, lc = 0.f;
+  STAGE_TILES(p0, total) {
+    const int np = tile_in(buf, p0, total, c, x);
+    if ((int)threadIdx.x < np) {
+      const long t = tgt[p0 + threadIdx.x];
+      if (t != ignore) {
+        ls += px_ce_loss(dense_row((const T*)buf + threadIdx.x * c), t, c);
+        lc += 1.f;
+      }
+    }
   }
+  ce_part_store(ls, lc, part);
 }
 __global__ void ce_fwd_final_kernel(float* __restrict__ part, int nb, float* __restrict__ loss) {
-  __shared__ float rs[4], rc[4];
-  float s = 0.f, cn = 0.f;
-  for (int i = threadIdx.x; i < nb; i += blockDim.x) { s += part[i]; cn += part[kCeRB + i]; }
-  s = wave_sum(s);
-  cn = wave_sum(cn);
-  if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = s; rc[threadIdx.x >> 6] = cn; }
-  __syncthreads();
+  float S = 0.f, C = 0.f;
+  for (int i = threadIdx.x; i < nb; i += blockDim.x) { S += part[i]; C += part[kCeRB + i]; }
+  ce_block_sums(S, C);
   if (threadIdx.x == 0) {
-    const float S = rs[0] + rs[1] + rs[2] + rs[3], C = rc[0] + rc[1] + rc[2] + rc[3];
     part[2 * kCeRB] = C;
     part[2 * kCeRB + 1] = S;
     loss[0] = S / C;
@@ -476,91 +492,23 @@ template <typename T>
 __global__ void ce_bwd_kernel(const T* __restrict__ x, const int64_t* __restrict__ tgt, const float* __restrict__ gout,
                               const float* __restrict__ count, T* __restrict__ dx, int n, long hw, int c, long sn, long sc, long shw,
                               int ignore) {
-  const long total = (long)n * hw;
   const float g = gout[0] / count[0];
+  const long total = (long)n * hw;
   GRID_STRIDE(p, total) {
-    const long t = tgt[p];
-    const long img = p / hw, s = p - img * hw;
-    const T* b = x + img * sn + s * shw;
-    T* o = dx + img * sn + s * shw;
-    if (t == ignore) {
-      for (int k = 0; k < c; ++k) o[k * sc] = from_f<T>(0.f);
-      continue;
-    }
-    float m = -INFINITY;
-    for (int k = 0; k < c; ++k) m = fmaxf(m, to_f(b[k * sc]));
-    float z = 0.f;
-    for (int k = 0; k < c; ++k) z += expf(to_f(b[k * sc]) - m);
-    const float iz = 1.f / z;
-    for (int k = 0; k < c; ++k) {
-      const float pr = expf(to_f(b[k * sc]) - m) * iz;
-      o[k * sc] = from_f<T>(g * (pr - (k == t ? 1.f : 0.f)));
-    }
-  }
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256) ce_fwd_part_staged(const T* __restrict__ x, const int64_t* __restrict__ tgt, float* __restrict__ part,
-                                                          long total, int c, int ignore) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* buf = (T*)smem_raw;
-  __shared__ float rs[4], rc[4];
-  float ls = 0.f, lc = 0.f;
-  for (long p0 = (long)blockIdx.x * kStagePix; p0 < total; p0 += (long)gridDim.x * kStagePix) {
-    const int np = (int)min<long>(kStagePix, total - p0);
-    __syncthreads();
-    stage_in(x + p0 * c, buf, np * c);
-    __syncthreads();
-    if ((int)threadIdx.x < np) {
-      const long t = tgt[p0 + threadIdx.x];
-      if (t != ignore) {
-        const T* r = buf + threadIdx.x * c;
-        float m = -INFINITY;
-        for (int k = 0; k < c; ++k) m = fmaxf(m, to_f(r[k]));
-        float z = 0.f;
-        for (int k = 0; k < c; ++k) z += expf(to_f(r[k]) - m);
-        const float xt = (t >= 0 && t < c) ? to_f(r[t]) : NAN;
-        ls += logf(z) + m - xt;
-        lc += 1.f;
-      }
-    }
-  }
-  ls = wave_sum(ls);
-  lc = wave_sum(lc);
-  if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = ls; rc[threadIdx.x >> 6] = lc; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[blockIdx.x] = rs[0] + rs[1] + rs[2] + rs[3];
-    part[kCeRB + blockIdx.x] = rc[0] + rc[1] + rc[2] + rc[3];
+    const long off = pixel_offset(p, hw, sn, shw);
+    px_ce_grad<false>(strided_row(x + off, sc), strided_row(dx + off, sc), tgt[p], c, ignore, g);
   }
 }
 template <typename T>
 __global__ void __launch_bounds__(256) ce_bwd_staged(const T* __restrict__ x, const int64_t* __restrict__ tgt, const float* __restrict__ gout,
                                                      const float* __restrict__ count, T* __restrict__ dx, long total, int c, int ignore) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* buf = (T*)smem_raw;
+  T* buf = stage_buf<T>();
   const float g = gout[0] / count[0];
-  for (long p0 = (long)blockIdx.x * kStagePix; p0 < total; p0 += (long)gridDim.x * kStagePix) {
-    const int np = (int)min<long>(kStagePix, total - p0);
-    __syncthreads();
-    stage_in(x + p0 * c, buf, np * c);
-    __syncthreads();
-    if ((int)threadIdx.x < np) {
-      const long t = tgt[p0 + threadIdx.x];
-      T* r = buf + threadIdx.x * c;
-      if (t == ignore) {
-        for (int k = 0; k < c; ++k) r[k] = from_f<T>(0.f);
-      } else {
-        float m = -INFINITY;
-        for (int k = 0; k < c; ++k) m = fmaxf(m, to_f(r[k]));
-        float z = 0.f;
-        for (int k = 0; k < c; ++k) z += expf(to_f(r[k]) - m);
-        const float gz = g / z;
-        for (int k = 0; k < c; ++k) r[k] = from_f<T>(gz * expf(to_f(r[k]) - m) - (k == t ? g : 0.f));
-      }
-    }
-    __syncthreads();
-    stage_out(dx + p0 * c, buf, np * c);
+  STAGE_TILES(p0, total) {
+    const int np = tile_in(buf, p0, total, c, x);
+    T* r = buf + threadIdx.x * c;
+    if ((int)threadIdx.x < np) px_ce_grad<true>(dense_row(r), dense_row(r), tgt[p0 + threadIdx.x], c, ignore, g);
+    tile_out(dx, buf, p0, np, c);
   }
 }
 
@@ -610,10 +558,8 @@ __global__ void bce_fwd_kernel(const float* __restrict__ x, const float* __restr
     const float v = x[i];
     s += fmaxf(v, 0.f) - v * t[i] + log1pf(expf(-fabsf(v)));
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) r[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) loss[0] = (r[0] + r[1] + r[2] + r[3]) / (float)n;
+  s = block_sum4(s, r);
+  if (threadIdx.x == 0) loss[0] = s / (float)n;
 }
 __global__ void bce_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ gout, float* __restrict__ dx, int n) {
   const float g = gout[0] / (float)n;
@@ -637,57 +583,37 @@ extern "C" int rtsds_bce_bwd(const float* x, const float* target, const float* g
 // argmax over channels, first maximum wins (torch.argmax / max(1), train.py:102-106,272-275,
 // validation.py:51).  out_idx may be NULL; correct += #(argmax == target) (ignored pixels
 // count as wrong, exactly like the reference).
-template <typename T>
-__global__ void argmax_kernel(const T* __restrict__ x, int64_t* __restrict__ out, const int64_t* __restrict__ tgt,
-                              unsigned long long* __restrict__ correct, int n, long hw, int c, long sn, long sc, long shw) {
-  const long total = (long)n * hw;
-  unsigned long long cnt = 0;
-  GRID_STRIDE(p, total) {
-    const long img = p / hw, s = p - img * hw;
-    const T* b = x + img * sn + s * shw;
-    float best = to_f(b[0]);
-    int bi = 0;
-    for (int k = 1; k < c; ++k) {
-      const float v = to_f(b[k * sc]);
-      if (v > best || (v != v && best == best)) { best = v; bi = k; }
-    }
-    if (out) out[p] = bi;
-    if (tgt && tgt[p] == bi) ++cnt;
-  }
+template <typename R>
+RT_DEV void px_argmax(R x, long p, int c, int64_t* __restrict__ out, const int64_t* __restrict__ tgt, unsigned long long& cnt) {
+  float best;
+  const int bi = first_max(x, c, best);
+  if (out) out[p] = bi;
+  if (tgt && tgt[p] == bi) ++cnt;
+}
+RT_DEV void argmax_count(unsigned long long* correct, unsigned long long cnt) {
   if (correct) {
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(correct, cnt);
   }
 }
-
+template <typename T>
+__global__ void argmax_kernel(const T* __restrict__ x, int64_t* __restrict__ out, const int64_t* __restrict__ tgt,
+                              unsigned long long* __restrict__ correct, int n, long hw, int c, long sn, long sc, long shw) {
+  const long total = (long)n * hw;
+  unsigned long long cnt = 0;
+  GRID_STRIDE(p, total) px_argmax(strided_row(x + pixel_offset(p, hw, sn, shw), sc), p, c, out, tgt, cnt);
+  argmax_count(correct, cnt);
+}
 template <typename T>
 __global__ void __launch_bounds__(256) argmax_staged(const T* __restrict__ x, int64_t* __restrict__ out, const int64_t* __restrict__ tgt,
                                                      unsigned long long* __restrict__ correct, long total, int c) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T* buf = (T*)smem_raw;
+  T* buf = stage_buf<T>();
   unsigned long long cnt = 0;
-  for (long p0 = (long)blockIdx.x * kStagePix; p0 < total; p0 += (long)gridDim.x * kStagePix) {
-    const int np = (int)min<long>(kStagePix, total - p0);
-    __syncthreads();
-    stage_in(x + p0 * c, buf, np * c);
-    __syncthreads();
-    if ((int)threadIdx.x < np) {
-      const T* r = buf + threadIdx.x * c;
-      float best = to_f(r[0]);
-      int bi = 0;
-      for (int k = 1; k < c; ++k) {
-        const float v = to_f(r[k]);
-        if (v > best || (v != v && best == best)) { best = v; bi = k; }
-      }
-      const long p = p0 + threadIdx.x;
-      if (out) out[p] = bi;
-      if (tgt && tgt[p] == bi) ++cnt;
-    }
+  STAGE_TILES(p0, total) {
+    const int np = tile_in(buf, p0, total, c, x);
+    if ((int)threadIdx.x < np) px_argmax(dense_row((const T*)buf + threadIdx.x * c), p0 + threadIdx.x, c, out, tgt, cnt);
   }
-  if (correct) {
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(correct, cnt);
-  }
+  argmax_count(correct, cnt);
 }
 
 extern "C" int rtsds_argmax(const void* x, long sn, long sc, long shw, int64_t* out, const int64_t* target, unsigned long long* correct,

@@ -6,6 +6,7 @@
 // Kept in a unit of its own (not in pseudo.hip), so the generated code of the pseudo-label
 // kernels does not depend on this file.
 #include "ew_common.h"
+#include "class_row.h"
 
 static const int kCmMinC = 2, kCmMaxC = 32;  // one bit per class in a 32-bit mask
 // One wave owns one item: kCmChunk consecutive pixels of one window row (64 lanes x 8 pixels).
@@ -158,7 +159,7 @@ RT_DEV void cm_pixel(const CmArgs& a, const int* tb, unsigned int chosen, long e
   long long lab = s;
   if (!m) {
     const int k = a.pred[t], b = a.cbin[t];
-    lab = (k < a.c && b >= tb[k]) ? k : a.ignore;
+    lab = pseudo_label(k, b, tb, a.c, a.ignore);
   }
   cm_copy_pixel<PIX>(a.out_img + t * PIX, m ? a.src + e * PIX : a.tgt + t * PIX);
   a.out_lab[t] = lab;
@@ -205,7 +206,7 @@ RT_DEV void cm_group(const CmArgs& a, const int* tb, unsigned int chosen, long e
     m[p] = hi == 0 && lo < (unsigned int)a.c && ((chosen >> (lo & 31)) & 1u);
     const int k = (int)((pw[p >> 2] >> (8 * (p & 3))) & 0xffu);
     const int b = (int)((cw[p >> 1] >> (16 * (p & 1))) & 0xffffu);
-    const long long pl = (k < a.c && b >= tb[k]) ? k : a.ignore;
+    const long long pl = pseudo_label(k, b, tb, a.c, a.ignore);
     o[p] = m[p] ? (long long)lo : pl;
   }
   longlong2* ol = (longlong2*)(a.out_lab + t);

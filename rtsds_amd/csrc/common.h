@@ -53,6 +53,16 @@ RT_DEV float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// Sum over a 256-thread block (four waves, added in wave order); red: 4 floats of LDS, free for
+// reuse after the leading barrier.  waves_sum4 takes each wave's sum: a kernel with several values
+// forms all their wave sums first, so that the shuffles overlap instead of queueing behind barriers.
+RT_DEV float waves_sum4(float w, float* red) {
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+RT_DEV float block_sum4(float v, float* red) { return waves_sum4(wave_sum(v), red); }
 RT_DEV float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

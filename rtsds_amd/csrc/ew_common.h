@@ -52,3 +52,26 @@ RT_DEV void stage_out(T* __restrict__ g, const T* s, int nel) {
     for (int i = threadIdx.x; i < nel; i += blockDim.x) g[i] = s[i];
   }
 }
+// The tile loop of a staged kernel: STAGE_TILES(p0, total) { np = tile_in(..); per-pixel work under
+// threadIdx.x < np; tile_out(..) where the tile is an output }.  tile_in stages the tile's rows of
+// every input (the i-th into the i-th [kStagePix][c] buffer) between two barriers, tile_out stores
+// the first buffer behind one: every thread of the block must reach each call.
+template <typename T>
+RT_DEV T* stage_buf() {  // the kernel's dynamic LDS
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  return (T*)smem_raw;
+}
+#define STAGE_TILES(p0, total) for (long p0 = (long)blockIdx.x * kStagePix; p0 < (total); p0 += (long)gridDim.x * kStagePix)
+template <typename T, typename... X>
+RT_DEV int tile_in(T* buf, long p0, long total, int c, const X*... x) {
+  const int np = (int)min<long>(kStagePix, total - p0);
+  __syncthreads();
+  ((stage_in(x + p0 * c, buf, np * c), buf += kStagePix * c), ...);  // one buffer per input, in order
+  __syncthreads();
+  return np;
+}
+template <typename T>
+RT_DEV void tile_out(T* __restrict__ y, const T* buf, long p0, int np, int c) {
+  __syncthreads();
+  stage_out(y + p0 * c, buf, np * c);
+}

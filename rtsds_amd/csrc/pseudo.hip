@@ -1,9 +1,10 @@
 // Class-balanced pseudo-labels for target self-training (gfx950): the per-class confidence
 // histogram of a summed-probability map (rtsds_conf_hist) and the thresholded label map
 // (rtsds_pseudo_select).  No reference counterpart (its train.py never trains on target pixels).
-// Kept in a unit of its own: no device helper here is shared with the kernels of chan.hip /
-// resize.hip, so their generated code does not depend on this file.
+// The per-pixel rules (first maximum, confidence bin, thresholded label) are class_row.h's, shared
+// with chan.hip, resize.hip and classmix.hip.
 #include "ew_common.h"
+#include "class_row.h"
 
 static const int kPlMinC = 2, kPlMaxC = 32;         // uint8 pred, one LDS row of thresholds
 static const int kPlMinBins = 16, kPlMaxBins = 1024;  // uint16 cbin; a power of two
@@ -18,11 +19,10 @@ static inline bool pl_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline size_t pl_lds_bytes(int tile, int c, int bins) { return ((size_t)tile * c + (size_t)c * bins) * 4; }
 
 // ------------------------------------------------------------------ confidence histogram
-// acc: total pixels x c fp32 (the sum upsoftmax_acc_kernel leaves).  Per pixel k = first-max class
-// (argmax_kernel's rule: a NaN beats every number, the first NaN wins), conf = acc[k] * inv,
-// b = floor(conf * bins) clamped to [0, bins - 1] (conf not > 0, NaN included: bin 0);
-// hist[k * bins + b] += 1, pred[p] = k, cbin[p] = b.  bins is a power of two, so conf * bins is
-// exact and the bin is the one the host computes from the same two fp32 multiplies.
+// acc: total pixels x c fp32 (the sum upsoftmax_acc_kernel leaves).  Per pixel k = first_max()
+// class, conf = acc[k] * inv, b = conf_bin(conf, bins); hist[k * bins + b] += 1, pred[p] = k,
+// cbin[p] = b.  bins is a power of two, so conf * bins is exact and the bin is the one the host
+// computes from the same two fp32 multiplies.
 //
 // One workgroup = TILE threads: a tile of TILE pixel rows (TILE * c contiguous floats, not 16-B
 // aligned per pixel) is staged through LDS with 16-B loads, one thread then owns one pixel.  The
@@ -43,23 +43,12 @@ template <int TILE>
 RT_DEV void conf_hist_tile(const float* buf, unsigned int* lh, uint8_t* __restrict__ pred, uint16_t* __restrict__ cbin, long p0, int np,
                            int c, int bins, float inv) {
   const int tid = threadIdx.x, lane = tid & 63;
-  const float fb = (float)bins;
   const bool valid = tid < np;
   int key = 0;
   if (valid) {
-    const float* r = buf + tid * c;
-    float best = r[0];
-    int bi = 0;
-    for (int k = 1; k < c; ++k) {
-      const float v = r[k];
-      if (v > best || (v != v && best == best)) { best = v; bi = k; }
-    }
-    const float conf = best * inv;
-    int b = 0;
-    if (conf > 0.f) {
-      const float t = floorf(conf * fb);
-      b = t >= fb ? bins - 1 : (int)t;
-    }
+    float best;
+    const int bi = first_max(dense_row(buf + tid * c), c, best);
+    const int b = conf_bin(best * inv, bins);
     key = bi * bins + b;
     const long p = p0 + tid;
     if (pred) pred[p] = (uint8_t)bi;
@@ -185,9 +174,9 @@ extern "C" int rtsds_conf_hist(const float* acc, unsigned long long* hist, uint8
 }
 
 // ------------------------------------------------------------------ thresholded labels
-// out[p] = pred[p] if cbin[p] >= tbin[pred[p]] else ignore_index (a class outside [0, c) is
-// ignored too).  3 B in, 8 B out per pixel; groups of 8 pixels move as one 8-B + one 16-B load and
-// four 16-B stores when the three pointers allow it.
+// out[p] = pseudo_label(pred[p], cbin[p], tbin, c, ignore_index).  3 B in, 8 B out per pixel;
+// groups of 8 pixels move as one 8-B + one 16-B load and four 16-B stores when the three pointers
+// allow it.
 __global__ void __launch_bounds__(256) pseudo_select_kernel(const uint8_t* __restrict__ pred, const uint16_t* __restrict__ cbin,
                                                             const int* __restrict__ tbin, int64_t* __restrict__ out, long total, int c,
                                                             int ignore, int vec) {
@@ -204,7 +193,7 @@ __global__ void __launch_bounds__(256) pseudo_select_kernel(const uint8_t* __res
     for (int j = 0; j < 8; ++j) {
       const int k = (int)((pw[j >> 2] >> (8 * (j & 3))) & 0xffu);
       const int b = (int)((cw[j >> 1] >> (16 * (j & 1))) & 0xffffu);
-      o[j] = (k < c && b >= tb[k]) ? k : ignore;
+      o[j] = pseudo_label(k, b, tb, c, ignore);
     }
     longlong2* dst = (longlong2*)(out + (g << 3));
 #pragma unroll
@@ -214,7 +203,7 @@ __global__ void __launch_bounds__(256) pseudo_select_kernel(const uint8_t* __res
   GRID_STRIDE(i, total - done) {
     const long p = done + i;
     const int k = pred[p], b = cbin[p];
-    out[p] = (k < c && b >= tb[k]) ? k : ignore;
+    out[p] = pseudo_label(k, b, tb, c, ignore);
   }
 }
 extern "C" int rtsds_pseudo_select(const uint8_t* pred, const uint16_t* cbin, const int* tbin, int64_t* out, long total, int c,

@@ -12,6 +12,7 @@
 //   upsm_tile, upsm_probs                         resize + softmax: one tile's staging, one pixel's probabilities
 //   upsm_logit                                    one class of one pixel's resized logits, for on-the-fly reductions
 #include "ew_common.h"
+#include "class_row.h"
 
 // ------------------------------------------------------------------ bilinear (align_corners=False)
 // bil_src (ATen source index, align_corners=False): common.h
@@ -795,7 +796,7 @@ __global__ void __launch_bounds__(256) upsoftmax_acc_kernel(const T* __restrict_
         float v = __fmul_rn(z[k], iz);
         if (accumulate) v = __fadd_rn(o[k], v);
         o[k] = v;
-        if (k == 0 || v > best) {
+        if (k == 0 || v > best) {  // not first_max(): no NaN clause (class-vector unit)
           best = v;
           bi = k;
         }
@@ -808,9 +809,8 @@ __global__ void __launch_bounds__(256) upsoftmax_acc_kernel(const T* __restrict_
 // ------------------------------------------------------------------ low-resolution head -> pseudo-labels
 // The online teacher's labels (selftrain.TeacherLoader): upsoftmax_acc_kernel's tile and
 // probabilities (accumulate = 0, flip = 0: v[k] = __fmul_rn(z[k], iz)), reduced in registers by
-// conf_hist_tile's rule (pseudo.hip: first maximum wins, a NaN beats every number and the first
-// NaN wins, conf = best * 1.0f, bin = floor(conf * bins) clamped to [0, bins - 1], a conf that is
-// not > 0 in bin 0) and thresholded by pseudo_select_kernel's: pred / cbin / labels equal the
+// conf_hist_tile's calls (class_row.h: first_max(), conf_bin() of conf = best * 1.0f) and
+// thresholded by pseudo_select_kernel's pseudo_label(): pred / cbin / labels equal the
 // chain rtsds_upsoftmax_acc -> rtsds_conf_hist (inv = 1) -> rtsds_pseudo_select bit for bit, and
 // the fp32 probability tensor (c x 4 B written and read again per pixel) never exists.  LDS holds
 // the staged source rows only; a tile's pixels are lane-consecutive, so each output leaves as
@@ -829,33 +829,18 @@ __global__ void __launch_bounds__(256) upsample_pseudo_kernel(const T* __restric
   float z[kUpsmMaxC];
   float iz;
   upsm_probs<T, STAGED, CC>(tl.r0, tl.r1, src, tl.wlo, tl.n1, c, tl.ow0 + tid, sw, wi, tl.lh0, tl.lh1, z, iz);
-  float best = 0.f;
-  int bi = 0;
-#pragma unroll
-  for (int k = 0; k < kUpsmMaxC; ++k)
-    if (k < c) {
-      const float v = __fmul_rn(z[k], iz);
-      if (k == 0 || v > best || (v != v && best == best)) {
-        best = v;
-        bi = k;
-      }
-    }
-  const float fb = (float)bins;
-  const float conf = best * 1.0f;
-  int b = 0;
-  if (conf > 0.f) {
-    const float t = floorf(conf * fb);
-    b = t >= fb ? bins - 1 : (int)t;
-  }
+  float best;
+  const int bi = first_max<kUpsmMaxC>([&](int k) { return __fmul_rn(z[k], iz); }, c, best);
+  const int b = conf_bin(best * 1.0f, bins);
   const long p = tl.row * wo + tl.ow0 + tid;
   if (pred) pred[p] = (uint8_t)bi;
   if (cbin) cbin[p] = (uint16_t)b;
-  if (labels) labels[p] = b >= tbin[bi] ? bi : ignore;
+  if (labels) labels[p] = pseudo_label<false>(bi, b, tbin, c, ignore);  // bi < c by construction
 }
 // ------------------------------------------------------------------ low-resolution head -> painted frame
 // The output side of inference (predict.Predictor): the same tile, but no softmax -- k = arg-max
-// of the resized logits (upsm_logit: what rtsds_bilinear_fwd would store) by argmax_kernel's rule
-// (first maximum wins, a NaN beats every number and the first NaN wins), a running maximum, so
+// of the resized logits (upsm_logit: what rtsds_bilinear_fwd would store) by first_max()
+// (class_row.h, rtsds_argmax's scan) over a callable, a running maximum, so
 // ids equal the chain rtsds_bilinear_fwd -> rtsds_argmax bit for bit and the full-resolution
 // logits never exist.  ids[p] = lut[k] (k without a lut); rgb[p] = palette[k], blended over the
 // frame in integers: (alpha * palette + (256 - alpha) * frame + 128) >> 8, alpha in [0, 256].
@@ -891,17 +876,9 @@ __global__ void __launch_bounds__(256) upsample_paint_kernel(const T* __restrict
   int w0, w1;
   float lw0, lw1;
   bil_src(tl.ow0 + tid, sw, wi, w0, w1, lw0, lw1);
-  float best = 0.f;
-  int bi = 0;
-#pragma unroll
-  for (int k = 0; k < kUpsmMaxC; ++k)
-    if (k < c) {
-      const float v = upsm_logit<T, STAGED>(tl.r0, tl.r1, src, tl.wlo, tl.n1, c, k, w0, w1, tl.lh0, tl.lh1, lw0, lw1);
-      if (k == 0 || v > best || (v != v && best == best)) {
-        best = v;
-        bi = k;
-      }
-    }
+  float best;
+  const int bi = first_max<kUpsmMaxC>(
+      [&](int k) { return upsm_logit<T, STAGED>(tl.r0, tl.r1, src, tl.wlo, tl.n1, c, k, w0, w1, tl.lh0, tl.lh1, lw0, lw1); }, c, best);
   if (ids != nullptr) ids[p] = idt[bi];
   if (rgb != nullptr) {
     int q0 = pal[3 * bi], q1 = pal[3 * bi + 1], q2 = pal[3 * bi + 2];

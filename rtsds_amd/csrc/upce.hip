@@ -53,14 +53,6 @@ struct UpceArgs {
   int nheads, ignore, want_grad;
 };
 
-RT_DEV float upce_block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
 // CP: channel count padded to a multiple of 4 (compile time, so every per-class loop is
 // fully unrolled without guards); padding classes hold -1e30 logits (softmax weight 0).
 //
@@ -485,12 +477,12 @@ __global__ void __launch_bounds__(256) upce_final_kernel(const float* __restrict
         for (int a = 0; a <= kUpceMaxHeads; ++a) acc[a] += v[a][u];
       }
   }
-  const float c = upce_block_sum(acc[0], red);
+  const float c = block_sum4(acc[0], red);
   if (threadIdx.x == 0) stat[0] = c;
 #pragma unroll
   for (int h = 0; h < kUpceMaxHeads; ++h) {
     if (h >= nheads) break;
-    const float s = upce_block_sum(acc[1 + h], red);
+    const float s = block_sum4(acc[1 + h], red);
     if (threadIdx.x == 0) stat[1 + h] = s;
   }
   if (threadIdx.x == 0) upce_losses(stat, nheads, loss, loss_sum);

@@ -1,9 +1,10 @@
-"""Records tests/pinned/UNIT_bits.json (UNIT = bn, resize): one SHA-256 per output tensor per
+"""Records tests/pinned/UNIT_bits.json (UNIT = bn, resize, chan): one SHA-256 per output tensor per
 case of tests/UNIT_bits_cases.py, from the library this checkout built (or RTSDS_LIB).
 
     python tools/record_bits.py UNIT [--check] [--out FILE]
     python tools/record_bn_bits.py [--check] [--out FILE]        (UNIT = bn)
     python tools/record_resize_bits.py [--check] [--out FILE]    (UNIT = resize)
+    python tools/record_chan_bits.py [--check] [--out FILE]      (UNIT = chan)
 
 The file is recorded on the parent of a commit that means to change the unit's arithmetic --
 first with --check (compares, writes nothing) to show that the committed file was still green
@@ -22,7 +23,7 @@ sys.path.insert(0, ROOT)
 def main(unit=None):
     ap = argparse.ArgumentParser()
     if unit is None:
-        ap.add_argument("unit", choices=("bn", "resize"))
+        ap.add_argument("unit", choices=("bn", "resize", "chan"))
     ap.add_argument("--check", action="store_true", help="compare with the recorded file instead of writing it")
     ap.add_argument("--out")
     args = ap.parse_args()
