@@ -522,6 +522,39 @@ int rtsds_upsample_paint(const void* x, const uint8_t* frame, const uint8_t* pal
                          uint8_t* ids, uint8_t* rgb, int n, int hi, int wi, int c, int ho, int wo,
                          float scale_h, float scale_w, int alpha_q8, int dtype, void* stream);
 
+/* rtsds_slide_paint: sliding-window ("tiled") inference at native resolution.  The model ran on
+ *   nwin overlapping hw x ww crops of an H x W canvas, for nf frames; x holds their NHWC heads
+ *   [nwin * nf][hi][wi][c] (fp32 or bf16), window-major: the head of window k of frame f at index
+ *   k * nf + f, so a chunk of windows is a contiguous slice.  Geometry (hi, wi) -> (hw, ww) with
+ *   scale_h / scale_w as rtsds_upsoftmax_acc takes them (any geometry that entry accepts).
+ *   win = HOST array of nwin triples {y0, x0, flip}, 1 <= nwin <= 64, copied into the kernel's
+ *   arguments by the launcher (no device table, nothing to clamp, graph-capture safe); every
+ *   window must lie inside the canvas, 0 <= y0 <= H - hw and 0 <= x0 <= W - ww.
+ *   Window k's probabilities at its own pixel (oy, ow): p = z[k] * iz exactly as
+ *   rtsds_upsoftmax_acc forms them (bf16 mode: the value before any bf16 rounding); with
+ *   flip != 0 the pixel computed at window column ow belongs to window column ww - 1 - ow.
+ *   Sum at canvas pixel (f, Y, X): the windows covering it in ascending k; s starts as
+ *   acc[f][Y][X][:] when accumulate != 0, else as the first covering window's p; every further
+ *   window is one fp32 add of the rounded product, never an FMA.  A pixel no window covers has
+ *   s = acc (accumulate) or all zeros.  Equal, bit for bit, to rtsds_upsoftmax_acc per window
+ *   followed by an fp32 add of each window's tensor onto its slice of the canvas.
+ *   acc (fp32 [nf][H][W][c], dense pitch c; may be NULL when accumulate == 0) receives s.
+ *   k* = argmax s by rtsds_upsoftmax_acc's pred rule (strictly greater wins, first maximum kept,
+ *   no NaN clause).  ids[p] (uint8 [nf][H][W]) = lut ? lut[k*] : k*, rgb[p] (uint8 [nf][H][W][3])
+ *   the palette blend over frame -- rtsds_upsample_paint's outputs bit for bit (integer blend,
+ *   0 <= alpha_q8 <= 256, frame needed only when blending, no alignment asked of byte buffers).
+ *   acc, ids and rgb may each be NULL, not all three; with acc NULL no fp32 canvas is touched.
+ *   RTSDS_ERR_SHAPE: nf, a size or nwin < 1, hw > H, ww > W, a window outside the canvas, c
+ *   outside [2, 32], alpha_q8 outside [0, 256].  RTSDS_ERR_UNSUPPORTED: nwin > 64 (the caller
+ *   chunks: accumulate), a bad dtype, a missing pointer the asked outputs need.  Every check is
+ *   made on the host before any HIP call.  One owner per canvas pixel: no atomics; never
+ *   synchronises, allocates or touches host memory other than win.                            */
+int rtsds_slide_paint(const void* x, const int* win, int nwin, const uint8_t* frame,
+                      const uint8_t* palette, const uint8_t* lut, float* acc, uint8_t* ids,
+                      uint8_t* rgb, int nf, int hi, int wi, int c, int hw, int ww, int H, int W,
+                      float scale_h, float scale_w, int accumulate, int alpha_q8, int dtype,
+                      void* stream);
+
 /* ---------------------------------------------------------------- ClassMix (self-training)
  * No counterpart in the reference.  ClassMix (DACS, DAFormer) pastes the pixels of half of the
  * classes of a labelled source image, image and label, onto a target image; here the rest of
@@ -710,7 +743,7 @@ int rtsds_pooled_mlp_fwd(const void* p, const void* w1, const float* b1, const v
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 20
+#define RTSDS_ABI_VERSION 21
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSDS_LIB: alternative in-tree build of the same ABI (kernel-variant A/B measurements)
 DEFAULT_LIB_PATH = os.path.join(_HERE, "librtsds_hip.so")
-ABI_VERSION = 20  # include/rtsds_hip.h RTSDS_ABI_VERSION
+ABI_VERSION = 21  # include/rtsds_hip.h RTSDS_ABI_VERSION
 LIB_PATH = os.environ.get("RTSDS_LIB") or DEFAULT_LIB_PATH
 
 F32, BF16 = 0, 1
@@ -132,6 +132,8 @@ SIGNATURES = {
     "rtsds_pseudo_select": (c_int, [P, P, P, P, c_long, c_int, c_int, P]),
     "rtsds_upsample_pseudo": (c_int, [P, P, P, P, P] + [c_int] * 6 + [c_float, c_float, c_int, c_int, c_int, P]),
     "rtsds_upsample_paint": (c_int, [P, P, P, P, P, P] + [c_int] * 6 + [c_float, c_float, c_int, c_int, P]),
+    "rtsds_slide_paint": (c_int, [P, ctypes.POINTER(c_int), c_int, P, P, P, P, P, P] + [c_int] * 8 +
+                          [c_float, c_float, c_int, c_int, c_int, P]),
     "rtsds_ema_step": (c_int, [P, P, P, c_long, c_float, P]),
     "rtsds_ema_many": (c_int, [c_int, P, P, P, c_float, P]),
     "rtsds_class_presence": (c_int, [P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),

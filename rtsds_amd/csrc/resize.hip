@@ -891,6 +891,145 @@ __global__ void __launch_bounds__(256) upsample_paint_kernel(const T* __restrict
     o[0] = (uint8_t)q0, o[1] = (uint8_t)q1, o[2] = (uint8_t)q2;
   }
 }
+// ------------------------------------------------------------------ sliding windows -> painted frame
+// Tiled inference at native resolution (validation.predict_sliding, predict.Predictor(stride=)):
+// the model ran on nwin overlapping hw x ww crops of an H x W canvas; each crop's head gives
+// upsoftmax_acc_kernel's probabilities (upsm_probs, then __fmul_rn) at the crop's own pixels, and a
+// canvas pixel's result is their sum over the windows covering it, in ascending window index, one
+// __fadd_rn each -- the chain rtsds_upsoftmax_acc per window -> slice add onto a zero canvas, bit
+// for bit.  One owner per canvas pixel, so no atomics: a block takes 256 consecutive columns of
+// one canvas row (slide tile set-up below: upsm_tile's, in canvas coordinates), filters the window
+// table by its row and column range -- a test on blockIdx alone, so block-uniform, as is the
+// barrier count -- and per kept window stages the two source rows of the window columns it covers
+// (a mirrored window maps the tile's range to a contiguous, reversed range of window columns:
+// the staging is the same) and lets the lanes inside the window add their probabilities onto
+// their register row.  The sum is reduced in registers to the class (upsoftmax_acc_kernel's
+// pred rule) and leaves as upsample_paint_kernel's bytes; the fp32 canvas acc is optional (in:
+// accumulate, for window chunks; out: when given) and moves as upsm_tile_copy's 16-B chunks
+// through an LDS tile.  Without it the kernel touches no fp32 canvas at all: 1 - 7 B per pixel.
+// The window table travels by value in the kernel's arguments (<= 64 windows, 520 B): no device
+// table to keep alive or to clamp.
+static const int kSlideMaxWin = 64;
+struct SlideWins {
+  int y0[kSlideMaxWin], x0[kSlideMaxWin];
+  unsigned long long flip;  // bit k: window k is mirrored
+};
+// one class of one window's probabilities, p = __fmul_rn(z, iz), added onto the running sum by one
+// __fadd_rn (first: the sum starts as p).  The header intrinsics are plain operators the compiler
+// may still contract into an FMA (optim.hip, ema_update), and here it did: the two operations
+// are written out with contraction switched off for this function.
+RT_DEV float slide_sum(float s, float z, float iz, bool any) {
+#pragma clang fp contract(off)
+  const float p = z * iz;
+  return any ? s + p : p;
+}
+template <typename T, bool STAGED, int CC>  // CC > 0: compile-time class count (19), 0: runtime c
+__global__ void __launch_bounds__(256) slide_paint_kernel(const T* __restrict__ x, const SlideWins wt, int nwin,
+                                                          const uint8_t* __restrict__ frame, const uint8_t* __restrict__ palette,
+                                                          const uint8_t* __restrict__ lut, float* __restrict__ acc,
+                                                          uint8_t* __restrict__ ids, uint8_t* __restrict__ rgb, int nf, int hi, int wi,
+                                                          int c_, int hw, int ww, int H, int W, float sh, float sw, int accumulate,
+                                                          int alpha, int tiles, int srcf) {
+  const int c = CC > 0 ? CC : c_;
+  // STAGED: [2][ncols][c] of the current window (srcf floats hold any window's), then the
+  // palette / lut table, then (acc) the fp32 tile [np][c] at its destination's 16-B phase
+  extern __shared__ __attribute__((aligned(16))) float src[];
+  const int tid = threadIdx.x;
+  const int tile = blockIdx.x % tiles;
+  const long row = blockIdx.x / tiles;  // f * H + Y
+  const int Y = (int)(row % H), f = (int)(row / H);
+  const int X0 = tile * kUpsmPix, np = min(kUpsmPix, W - X0), X = X0 + tid;
+  uint8_t* pal = (uint8_t*)(src + srcf);  // 16-B aligned
+  uint8_t* idt = pal + 3 * kUpsmMaxC;
+  if (rgb != nullptr && tid < 3 * c) pal[tid] = palette[tid];
+  if (tid >= 128 && tid - 128 < c) idt[tid - 128] = lut != nullptr ? lut[tid - 128] : (uint8_t)(tid - 128);
+  const bool blend = rgb != nullptr && alpha < 256;
+  const long p = row * W + X;  // this lane's pixel (tid < np)
+  int f0 = 0, f1 = 0, f2 = 0;
+  if (blend && tid < np) {  // issued ahead of the barriers and the window loop
+    const uint8_t* fp = frame + 3 * p;
+    f0 = fp[0], f1 = fp[1], f2 = fp[2];
+  }
+  const int nel = np * c;
+  float* dst = nullptr;
+  float* tbuf = src + srcf + kPaintTab / 4;
+  int head = 0;
+  if (acc != nullptr) {
+    dst = acc + (row * W + X0) * c;
+    const int mis = (int)(((uintptr_t)dst >> 2) & 3);
+    head = min(nel, (4 - mis) & 3);
+    tbuf += mis;
+  }
+  if (accumulate) upsm_tile_copy<true>(dst, tbuf, nel, head);  // host: acc != nullptr
+  __syncthreads();
+  float s[kUpsmMaxC];
+  bool any = accumulate != 0;  // s holds a sum already
+#pragma unroll
+  for (int k = 0; k < kUpsmMaxC; ++k) s[k] = (accumulate && tid < np && k < c) ? tbuf[tid * c + k] : 0.f;
+  for (int k = 0; k < nwin; ++k) {
+    const int y0 = wt.y0[k], x0 = wt.x0[k];
+    if (Y < y0 || Y >= y0 + hw || x0 >= X0 + np || x0 + ww <= X0) continue;  // block-uniform
+    const bool flip = (wt.flip >> k) & 1;
+    int h0, h1;
+    float lh0, lh1;
+    bil_src(Y - y0, sh, hi, h0, h1, lh0, lh1);
+    const T* hb = x + (long)(k * nf + f) * hi * wi * c;  // window-major heads
+    const T* r0 = hb + (long)h0 * wi * c;
+    const T* r1 = hb + (long)h1 * wi * c;
+    int wlo = 0, n1 = 0;
+    if (STAGED) {  // the window columns of the tile's part of this window; taps are monotone in ow
+      const int da = max(X0, x0) - x0, db = min(X0 + np, x0 + ww) - 1 - x0;
+      const int oa = flip ? ww - 1 - db : da, ob = flip ? ww - 1 - da : db;
+      int a0, a1, b0, b1;
+      float t0, t1;
+      bil_src(oa, sw, wi, a0, a1, t0, t1);
+      bil_src(ob, sw, wi, b0, b1, t0, t1);
+      wlo = a0;
+      n1 = (b1 - a0 + 1) * c;  // 2 * n1 <= srcf (host: slide_cols)
+      __syncthreads();  // the previous window's taps have been read
+      bil_stage_rows(r0 + (long)wlo * c, r1 + (long)wlo * c, src, n1);
+      __syncthreads();
+    }
+    const int d = X - x0;  // this lane's column of the window
+    if (tid < np && d >= 0 && d < ww) {
+      float z[kUpsmMaxC];
+      float iz;
+      upsm_probs<T, STAGED, CC>(r0, r1, src, wlo, n1, c, flip ? ww - 1 - d : d, sw, wi, lh0, lh1, z, iz);
+#pragma unroll
+      for (int j = 0; j < kUpsmMaxC; ++j)
+        if (j < c) s[j] = slide_sum(s[j], z[j], iz, any);
+      any = true;
+    }
+  }
+  if (tid < np) {
+    float best = 0.f;
+    int bi = 0;
+#pragma unroll
+    for (int j = 0; j < kUpsmMaxC; ++j)
+      if (j < c) {
+        if (acc != nullptr) tbuf[tid * c + j] = s[j];
+        if (j == 0 || s[j] > best) {  // upsoftmax_acc_kernel's pred: no NaN clause
+          best = s[j];
+          bi = j;
+        }
+      }
+    if (ids != nullptr) ids[p] = idt[bi];
+    if (rgb != nullptr) {
+      int q0 = pal[3 * bi], q1 = pal[3 * bi + 1], q2 = pal[3 * bi + 2];
+      if (blend) {
+        q0 = (alpha * q0 + (256 - alpha) * f0 + 128) >> 8;
+        q1 = (alpha * q1 + (256 - alpha) * f1 + 128) >> 8;
+        q2 = (alpha * q2 + (256 - alpha) * f2 + 128) >> 8;
+      }
+      uint8_t* o = rgb + 3 * p;
+      o[0] = (uint8_t)q0, o[1] = (uint8_t)q1, o[2] = (uint8_t)q2;
+    }
+  }
+  if (acc != nullptr) {  // block-uniform; every lane reaches the barrier (no early exit above)
+    __syncthreads();
+    upsm_tile_copy<false>(dst, tbuf, nel, head);
+  }
+}
 template <typename T, int CC>  // CC > 0: compile-time class count (19), 0: runtime c
 __global__ void __launch_bounds__(256) upsoftmax_bwd_w_kernel(const T* __restrict__ dy, int dyld, const T* __restrict__ y,
                                                               int yld, float* __restrict__ tmp, int wi, int c_, int wo, float sw,
@@ -1068,6 +1207,51 @@ extern "C" int rtsds_upsample_paint(const void* x, const uint8_t* frame, const u
   DISPATCH_T(dtype, upsm_dispatch(staged, c, [&](auto s, auto cc) {
     hipLaunchKernelGGL((upsample_paint_kernel<T, decltype(s)::value, decltype(cc)::value>), dim3(p.blocks), dim3(256), lds, st,
                        (const T*)x, frame, palette, lut, ids, rgb, hi, wi, c, ho, wo, scale_h, scale_w, alpha_q8, p.tiles);
+  }));
+  RET_LAUNCH();
+}
+// columns of a head's rows that any run of <= 256 consecutive window columns [a, b] taps: at most
+// floor(src(b)) + 1 - floor(src(a)) + 1 <= sw * (b - a) + 3, one more for the device's own float
+// rounding; never more than the head has
+static int slide_cols(int wi, int ww, float sw) {
+  const int run = std::min(ww, kUpsmPix) - 1;
+  return (int)std::min((double)wi, std::ceil((double)sw * run) + 4.0);
+}
+extern "C" int rtsds_slide_paint(const void* x, const int* win, int nwin, const uint8_t* frame, const uint8_t* palette,
+                                 const uint8_t* lut, float* acc, uint8_t* ids, uint8_t* rgb, int nf, int hi, int wi, int c, int hw,
+                                 int ww, int H, int W, float scale_h, float scale_w, int accumulate, int alpha_q8, int dtype,
+                                 void* stream) {
+  if (nf < 1 || hi < 1 || wi < 1 || hw < 1 || ww < 1 || H < 1 || W < 1 || nwin < 1 || hw > H || ww > W) return RTSDS_ERR_SHAPE;
+  if (c < 2 || c > kUpsmMaxC || alpha_q8 < 0 || alpha_q8 > 256) return RTSDS_ERR_SHAPE;
+  if (nwin > kSlideMaxWin || win == nullptr) return RTSDS_ERR_UNSUPPORTED;
+  SlideWins wt = {};
+  for (int k = 0; k < nwin; ++k) {
+    const int y0 = win[3 * k], x0 = win[3 * k + 1];
+    if (y0 < 0 || y0 > H - hw || x0 < 0 || x0 > W - ww) return RTSDS_ERR_SHAPE;
+    wt.y0[k] = y0;
+    wt.x0[k] = x0;
+    if (win[3 * k + 2] != 0) wt.flip |= 1ull << k;
+  }
+  if (dtype != RTSDS_F32 && dtype != RTSDS_BF16) return RTSDS_ERR_UNSUPPORTED;
+  if (x == nullptr || (acc == nullptr && ids == nullptr && rgb == nullptr) || (accumulate && acc == nullptr) ||
+      (rgb != nullptr && palette == nullptr) || (rgb != nullptr && alpha_q8 < 256 && frame == nullptr) || ((uintptr_t)acc & 3))
+    return RTSDS_ERR_UNSUPPORTED;
+  const int tiles = rt_cdiv(W, kUpsmPix);
+  const long blocks = (long)nf * H * tiles;
+  if (blocks > INT_MAX) return RTSDS_ERR_UNSUPPORTED;
+  // LDS: the staged rows of one window (while they stay within kUpsmLds and the whole within the
+  // 64 KiB a workgroup gets without opting in to more), the palette / lut table, and with acc the
+  // fp32 tile + up to 3 floats of phase
+  const size_t taps = (size_t)2 * slide_cols(wi, ww, scale_w) * c * sizeof(float);
+  const size_t tileb = acc != nullptr ? 16 + (size_t)kUpsmPix * c * sizeof(float) : 0;
+  const bool staged = taps <= (size_t)kUpsmLds && taps + 16 + kPaintTab + tileb <= (size_t)64 * 1024;
+  const int srcf = staged ? (int)((taps / 4 + 3) & ~(size_t)3) : 0;
+  const size_t lds = (size_t)srcf * 4 + kPaintTab + tileb;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_T(dtype, upsm_dispatch(staged, c, [&](auto s, auto cc) {
+    hipLaunchKernelGGL((slide_paint_kernel<T, decltype(s)::value, decltype(cc)::value>), dim3((unsigned)blocks), dim3(256), lds, st,
+                       (const T*)x, wt, nwin, frame, palette, lut, acc, ids, rgb, nf, hi, wi, c, hw, ww, H, W, scale_h, scale_w,
+                       accumulate, alpha_q8, tiles, srcf);
   }));
   RET_LAUNCH();
 }

@@ -1788,6 +1788,77 @@ def upsample_paint(x, geo, palette=None, alpha=1.0, frame=None, lut=None, ids=No
     return ids, rgb
 
 
+MAX_SLIDE_WINDOWS = 64  # rtsds_slide_paint: the window table travels in the kernel's arguments
+
+
+def slide_paint(x, geo, windows, canvas, nf, palette=None, alpha=1.0, frame=None, lut=None, acc=None, accumulate=False,
+                ids=None, rgb=None, want_ids=True):
+    """Sliding-window prediction (rtsds_slide_paint): the heads of overlapping crops -> the class
+    map and painted frame of the whole canvas in one pass.  ``x``: the heads [nwin * nf, c, hi, wi]
+    (2..32 classes), window-major (window k of frame f at index k * nf + f); ``geo`` from
+    upsample_geometry(): one head -> one window (hw, ww).  ``windows``: 1..64 entries (y0, x0) or
+    (y0, x0, flip), each window inside ``canvas`` = (H, W); ``flip`` marks the head of a mirrored
+    crop.  Per canvas pixel the probabilities upsample_softmax_accumulate forms for each covering
+    window are summed in fp32 in window order (onto ``acc`` when ``accumulate``), and the first-max
+    class of the sum gives ``ids`` (uint8 [nf, H, W]; lut[k] with ``lut``; allocated when
+    ``want_ids`` and not given) and ``rgb`` (uint8 [nf, H, W, 3], with ``palette``; blended over
+    ``frame`` when ``alpha`` < 1) exactly as upsample_paint writes them.  ``acc`` (fp32
+    [nf, H, W, c], optional) receives the sum; without it no fp32 canvas exists.  Bit-identical to
+    upsample_softmax_accumulate per window + a slice add per window.  Inference only, no host
+    sync.  Returns (ids, rgb), None for an output not produced."""
+    fn = "slide_paint"
+    given = [t for t in (palette, frame, lut, acc, ids, rgb) if t is not None]
+    if not x.is_cuda or not all(t.is_cuda for t in given):
+        raise RuntimeError(f"rtsds_amd: {fn}: x and every buffer must be HIP tensors; there is no CPU fallback")
+    if x.dim() != 4 or x.numel() == 0 or not 2 <= x.shape[1] <= 32:
+        raise RuntimeError(f"rtsds_amd: {fn}: x must be [nwin * nf, c, hi, wi] with 2..32 classes, got {tuple(x.shape)}")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"rtsds_amd: {fn}: x must be fp32 or bf16, got {x.dtype}")
+    from .transforms import _strength_q8  # (transforms imports this module)
+    try:
+        a = _strength_q8(float(alpha))
+    except RuntimeError:
+        raise RuntimeError(f"rtsds_amd: {fn}: alpha must lie in [0, 1], got {alpha}") from None
+    hw, ww, sh, sw = geo
+    H, W = int(canvas[0]), int(canvas[1])
+    nf = int(nf)
+    table = [(int(w[0]), int(w[1]), int(bool(w[2])) if len(w) > 2 else 0) for w in windows]
+    nwin = len(table)
+    if not 1 <= nwin <= MAX_SLIDE_WINDOWS:
+        raise RuntimeError(f"rtsds_amd: {fn}: 1..{MAX_SLIDE_WINDOWS} windows per call, got {nwin} (chunk them: accumulate)")
+    if nf < 1 or x.shape[0] != nwin * nf:
+        raise RuntimeError(f"rtsds_amd: {fn}: x must hold nwin * nf = {nwin} * {nf} heads, got {x.shape[0]}")
+    if hw > H or ww > W or any(not (0 <= y0 <= H - hw and 0 <= x0 <= W - ww) for y0, x0, _ in table):
+        raise RuntimeError(f"rtsds_amd: {fn}: every {hw} x {ww} window must lie inside the {H} x {W} canvas")
+    x = nhwc(x.detach())
+    _, c, hi, wi = x.shape
+    dev = x.device
+    if palette is None and rgb is not None:
+        raise RuntimeError(f"rtsds_amd: {fn}: rgb needs a palette")
+    if accumulate and acc is None:
+        raise RuntimeError(f"rtsds_amd: {fn}: accumulate needs acc")
+    if palette is None and acc is None and not (want_ids or ids is not None):
+        raise RuntimeError(f"rtsds_amd: {fn}: nothing to produce (no palette, no ids and no acc)")
+    if palette is not None:
+        _pseudo_arg(fn, "palette", palette, torch.uint8, (c, 3), dev)
+        if a < 256 and frame is None:
+            raise RuntimeError(f"rtsds_amd: {fn}: alpha < 1 needs the frame to blend over")
+        if rgb is None:
+            rgb = torch.empty((nf, H, W, 3), dtype=torch.uint8, device=dev)
+    if ids is None and want_ids:
+        ids = torch.empty((nf, H, W), dtype=torch.uint8, device=dev)
+    for name, t, shape in (("frame", frame, (nf, H, W, 3)), ("lut", lut, (c,)), ("ids", ids, (nf, H, W)),
+                           ("rgb", rgb, (nf, H, W, 3))):
+        if t is not None:
+            _pseudo_arg(fn, name, t, torch.uint8, shape, dev)
+    if acc is not None:
+        _pseudo_arg(fn, "acc", acc, torch.float32, (nf, H, W, c), dev)
+    win = (ctypes.c_int * (3 * nwin))(*[v for w in table for v in w])
+    lib.rtsds_slide_paint(_P(x), win, nwin, _P(frame), _P(palette), _P(lut), _P(acc), _P(ids), _P(rgb), nf, hi, wi, c,
+                          int(hw), int(ww), H, W, sh, sw, int(bool(accumulate)), a, dcode(x), stream())
+    return ids, rgb
+
+
 def ema_step(teacher, student, w, shadow=None):
     """Mean-teacher update of one flat fp32 buffer (rtsds_ema_step): teacher += w * (student -
     teacher) as three separately rounded fp32 operations, ``w`` rounded to fp32 here; ``shadow``

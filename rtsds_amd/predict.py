@@ -3,6 +3,7 @@
     python -m rtsds_amd.predict --weights CKPT.pth --input FRAME_OR_DIR --output DIR
                                 [--config rtsds_amd/config.yaml] [--model bisenet|deeplab]
                                 [--overlay A] [--label_ids] [--batch_size N]
+                                [--stride SY,SX] [--flip] [--max_batch N]
 
 No counterpart in the reference (its only consumers of a prediction are the validation histogram
 and the losses).  Protocol, per call of a ``Predictor``: the uint8 frames, of any sizes, are
@@ -13,8 +14,16 @@ validation.predict_multiscale -- and reduced to the arg-max class, which is what
 functional.upsample_paint does resize, arg-max, id lookup, palette lookup and the blend over the
 frame in one launch (rtsds_upsample_paint), one launch for all frames when they share a size.
 
-Out of scope here: a hipGraph-replayed frame loop (the op is capture-safe, so it can be added),
-video decode, and multi-scale prediction from the command line.
+Sliding windows (``Predictor(stride=...)``, ``--stride``): a frame at least as large as the network
+size is not shrunk but cut into overlapping crops of the network size at its native resolution
+(validation.sliding_windows; ``flip`` adds each crop's mirrored twin); the crops go through the
+same pipeline (at equal size its resize is the identity) and model, and functional.slide_paint
+(rtsds_slide_paint) sums the class probabilities of the crops covering each pixel -- the protocol
+of validation.predict_sliding -- and paints the arg-max of the sum, one launch per chunk of
+windows and no fp32 canvas when one chunk holds them all.  Smaller frames take the resize path.
+
+Out of scope here: a hipGraph-replayed frame loop (the ops are capture-safe, so it can be added),
+video decode, and multi-scale prediction (sliding windows at several scales included).
 """
 import argparse
 import os
@@ -44,9 +53,12 @@ class Predictor:
     (default TRAIN_ID_COLORS); ``label_ids``: optional [c] ids written instead of the train ids
     (CITYSCAPES_LABEL_IDS); ``alpha`` in [0, 1]: weight of the colour over the frame (1.0: the
     mask alone); ``dtype``: compute dtype of the forward (default: the runtime's).  Palette and
-    id table are moved to the device once."""
+    id table are moved to the device once.  ``stride`` = (sy, sx): sliding windows of ``size`` for
+    every frame at least that large (None: every frame is resized, as before); ``flip`` adds the
+    mirrored twin of each window; ``max_batch``: crops per forward."""
 
-    def __init__(self, model, size, palette=None, label_ids=None, alpha=1.0, dtype=None):
+    def __init__(self, model, size, palette=None, label_ids=None, alpha=1.0, dtype=None, stride=None, flip=False,
+                 max_batch=16):
         from . import transforms as T
         if not hasattr(model, "forward_lowres"):
             raise RuntimeError("rtsds_amd: Predictor needs a model with forward_lowres() (BiSeNet, DeepLabV2); "
@@ -75,6 +87,13 @@ class Predictor:
                 raise RuntimeError(f"rtsds_amd: Predictor: label_ids must be {pal.shape[0]} ids in 0..255")
             self.lut = lut.to(torch.uint8).contiguous().to(self.device)
         self.pipe = T.ImagePipeline(size)
+        self.size = self.pipe.size
+        self.stride = None if stride is None else (int(stride[0]), int(stride[1]))
+        if self.stride is not None and min(self.stride) < 1:
+            raise RuntimeError(f"rtsds_amd: Predictor: the stride must be positive, got {stride}")
+        self.flip, self.max_batch = bool(flip), int(max_batch)
+        if self.max_batch < 1:
+            raise RuntimeError(f"rtsds_amd: Predictor: max_batch must be positive, got {max_batch}")
 
     def lowres(self, frames):
         """The main head [n, c, h/8, w/8] of the frames (uint8 HWC device tensors), resized and
@@ -94,6 +113,27 @@ class Predictor:
                                f"{self.palette.shape[0]}")
         return low
 
+    def slide(self, frames, ids=True, rgb=True):
+        """Sliding-window prediction of frames that share one size >= the network size: (ids, rgb)
+        as uint8 [n, H, W] / [n, H, W, 3] tensors, None for one not asked for."""
+        from .validation import slide_chunks, slide_table
+        n, (H, W), (h, w) = len(frames), frames[0].shape[:2], self.size
+        chunks = slide_chunks(slide_table((H, W), (h, w), self.stride, self.flip), n, self.max_batch)
+        blend = rgb and self.alpha < 1.0
+        acc = out_i = out_c = None
+        for i, chunk in enumerate(chunks):
+            crops = [f[y0:y0 + h, x0:x0 + w] for y0, x0, _ in chunk for f in frames]  # window-major
+            crops = [(torch.flip(cr, dims=[1]) if chunk[j // n][2] else cr).contiguous() for j, cr in enumerate(crops)]
+            low = self.lowres(crops)
+            if acc is None and len(chunks) > 1:
+                acc = torch.empty((n, H, W, low.shape[1]), dtype=torch.float32, device=self.device)
+            last = i == len(chunks) - 1
+            out_i, out_c = F.slide_paint(low, F.upsample_geometry(low, size=(h, w)), chunk, (H, W), n,
+                                         palette=self.palette if rgb and last else None, alpha=self.alpha,
+                                         frame=torch.stack(frames) if blend and last else None, lut=self.lut, acc=acc,
+                                         accumulate=i > 0, want_ids=bool(ids) and last)
+        return out_i, out_c
+
     def __call__(self, frames, ids=True, rgb=True):
         """``frames``: a list of uint8 HWC [H_i, W_i, 3] tensors (CPU ones are moved to the model's
         device).  Returns ``(ids, rgb)``: per frame a uint8 [H_i, W_i] id map and a uint8
@@ -105,6 +145,23 @@ class Predictor:
             if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
                 raise RuntimeError(f"rtsds_amd: Predictor takes uint8 HWC [H, W, 3] frames, got {f.dtype} {tuple(f.shape)}")
         frames = [f.contiguous() for f in frames]
+        if self.stride is None:
+            return self._resized(frames, ids, rgb)
+        # frames of one size are batched: those at least as large as the network size slide, the rest are resized
+        large = lambda f: f.shape[0] >= self.size[0] and f.shape[1] >= self.size[1]  # noqa: E731
+        groups = {}
+        for j, f in enumerate(frames):
+            groups.setdefault((large(f),) + tuple(f.shape[:2]), []).append(j)
+        out_i, out_c = [None] * len(frames), [None] * len(frames)
+        for (slides, _, _), idx in groups.items():
+            gi, gc = (self.slide if slides else self._resized)([frames[j] for j in idx], ids, rgb)
+            for m, j in enumerate(idx):
+                out_i[j] = gi[m] if ids else None
+                out_c[j] = gc[m] if rgb else None
+        return (out_i if ids else None), (out_c if rgb else None)
+
+    def _resized(self, frames, ids, rgb):
+        """The frames shrunk (or stretched) to the network size, the head painted at each frame's own size."""
         low = self.lowres(frames)
         blend = rgb and self.alpha < 1.0
         kw = dict(palette=self.palette if rgb else None, alpha=self.alpha, lut=self.lut, want_ids=bool(ids))
@@ -132,6 +189,10 @@ def argument_parser(argv=None):
     p.add_argument("--overlay", type=float, default=1.0, help="weight of the colour over the frame (1.0: the mask alone)")
     p.add_argument("--label_ids", action="store_true", help="write Cityscapes label ids instead of train ids")
     p.add_argument("--batch_size", type=int, default=1)
+    p.add_argument("--stride", type=str, default=None, help="SY,SX: sliding windows of the network size at the frame's own "
+                                                            "resolution, this far apart (default: every frame is resized)")
+    p.add_argument("--flip", action="store_true", help="with --stride: add the mirrored twin of every window")
+    p.add_argument("--max_batch", type=int, default=16, help="with --stride: crops per forward")
     return p.parse_args(argv)
 
 
@@ -169,12 +230,18 @@ def main(argv=None):
     args = argument_parser(argv)
     if args.batch_size < 1:
         raise RuntimeError("rtsds_amd.predict: --batch_size must be positive")
+    if args.max_batch < 1:
+        raise RuntimeError("rtsds_amd.predict: --max_batch must be positive")
+    if args.flip and args.stride is None:
+        raise RuntimeError("rtsds_amd.predict: --flip needs --stride")
     config = load_config(args.config)
     set_compute_dtype(torch.bfloat16 if getattr(config, "precision", "fp32") == "bf16" else torch.float32)
     paths = input_paths(args.input)
     model = build_model(config, args.model, args.weights)
     predictor = Predictor(model, T.parse_size(config.data["cityscapes"]["image_size"]), alpha=args.overlay,
-                          label_ids=CITYSCAPES_LABEL_IDS if args.label_ids else None)
+                          label_ids=CITYSCAPES_LABEL_IDS if args.label_ids else None,
+                          stride=None if args.stride is None else T.parse_size(args.stride), flip=args.flip,
+                          max_batch=args.max_batch)
     os.makedirs(args.output, exist_ok=True)
     t0 = time.perf_counter()
     for b in range(0, len(paths), args.batch_size):
