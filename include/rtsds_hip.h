@@ -740,10 +740,40 @@ int rtsds_pooled_mlp_bwd(const void* da, const void* a, const void* h, const voi
 int rtsds_pooled_mlp_fwd(const void* p, const void* w1, const float* b1, const void* w2, const float* b2, void* h,
                          void* a, int n, int c0, int c1, int c2, int dtype, void* stream);
 
+/* Training-mode tail of the FeatureFusionModule (build_bisenet.py:75-80) on a narrow class map
+ * [n][hw][c] (c = 19, n <= 8, hw a multiple of the 16-B vector), in fewer launches than the
+ * op-by-op chain and equal to it bit for bit (functional.FfmTailFn).
+ *
+ * rtsds_bn_fwd_gap: training BatchNorm + act of x (statistics / finalize as rtsds_bn_fwd, conv
+ *   epilogue partials in stats_part / stats_nrb or NULL / 0), whose apply pass also leaves
+ *   rtsds_gap_fwd's stage-1 partials of y in gap_part (rtsds_gap_workspace(n, hw, c) bytes).
+ * rtsds_ffm_att_scale: from those partials pooled = GAP(f), hid = relu(conv1(pooled) + b1),
+ *   att = sigmoid(conv2(hid) + b2) (each [n][c]) and r = f * att + f, one launch.  r has pixel
+ *   pitch ldr: c, or a vector multiple up to 64 with zeros beyond c (RTSDS_INPUT_PADDED's form).
+ * rtsds_ffm_att_bwd: from dr = dL/dr the attention's whole backward (rtsds_chscale_bwd's da, then
+ *   rtsds_pooled_mlp_bwd) in two launches; ws: rtsds_gap_workspace(n, hw, c) bytes.
+ * rtsds_bn_bwd_ffm: rtsds_bn_bwd of that BatchNorm with its incoming gradient
+ *   round(round(dr * (att + 1)) + round(dpooled / hw)) formed per element instead of stored
+ *   (rtsds_chscale_bwd's dx followed by rtsds_gap_bwd's accumulate).                            */
+int rtsds_bn_fwd_gap(const void* x, void* y, float* gap_part, int n, long hw, int c, const float* gamma, const float* beta,
+                     float* running_mean, float* running_var, long long* num_batches_tracked, float* save_mean,
+                     float* save_invstd, float momentum, float eps, int act, const float* stats_part, int stats_nrb,
+                     int dtype, void* ws, size_t ws_bytes, void* stream);
+int rtsds_ffm_att_scale(const float* part, const void* f, const void* w1, const float* b1, const void* w2, const float* b2,
+                        void* pooled, void* hid, void* att, void* r, int ldr, int n, long hw, int c, int dtype,
+                        void* stream);
+int rtsds_ffm_att_bwd(const void* dr, const void* f, const void* a, const void* h, const void* p, const void* w1,
+                      const void* w2, float* dw1, float* db1, float* dw2, float* db2, void* dp, int n, long hw, int c,
+                      int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream);
+int rtsds_bn_bwd_ffm(const void* dr, const void* att, const void* dpooled, int n, long hw, const void* x, void* dx,
+                     float* dgamma, float* dbeta, int c, const float* gamma, const float* beta, const float* save_mean,
+                     const float* save_invstd, int training, int act, int accumulate_params, int dtype, void* ws,
+                     size_t ws_bytes, void* stream);
+
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 21
+#define RTSDS_ABI_VERSION 22
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

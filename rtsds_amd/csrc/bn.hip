@@ -7,6 +7,7 @@
 // main.py:69-72) do not cancel catastrophically.  Three launches per direction:
 // partial statistics (grid over row chunks) -> per-channel finalize -> vectorised apply.
 #include "bn_dev.h"
+#include "chan_dev.h"
 #include <type_traits>
 #include <algorithm>
 
@@ -297,6 +298,31 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const T* __restrict__ x, 
   }
 }
 
+// Pass 3 (forward) for a feature that is pooled next (the FeatureFusionModule's ConvBlock, whose
+// output feeds a global average pool): y = act(x * scale + shift), bn_apply_kernel's expression,
+// in chan_part_kernel<T, 1, false>'s partition, thread layout and order, which also leaves that
+// kernel's per-slice sums of the rounded values -- bit for bit the two launches' results.
+template <typename T>
+struct BnApplyLoad {
+  const T* x;
+  T* y;
+  float sc, sh;
+  int act;
+  RT_DEV float at(long o) const {
+    const T v = from_f<T>(act_f(fmaf(to_f(x[o]), sc, sh), act));
+    y[o] = v;
+    return to_f(v);
+  }
+};
+template <typename T>
+__global__ void __launch_bounds__(256) bn_apply_gap_kernel(const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, float* __restrict__ part, long hw, int c,
+                                                            int act) {
+  __shared__ float red[256];
+  const int ch = threadIdx.x % c;  // (c <= 256: the thread's channel in chan_part_body)
+  chan_part_body<T, 1, false>(BnApplyLoad<T>{x, y, scale[ch], shift[ch], act}, (const T*)nullptr, part, hw, c, red);
+}
+
 // Where the backward passes read g (before the activation mask): the stored dY, or -- for a
 // BatchNorm + ReLU feeding a 3x3 stride-2 max pool (the ResNet stem, fused forward in
 // bn_relu_pool_fwd_kernel) -- a gather of the pooled gradient: input pixel r of channel vector
@@ -343,6 +369,27 @@ struct GradPool {
       for (int j = 0; j < VEC; ++j)
         if (((ib[t] >> (8 * j)) & 0xff) == want) g[j] += to_f(gv[t][j]);
     }
+  }
+};
+
+// The FeatureFusionModule's feature gradient, never stored (rtsds_bn_bwd_ffm): the feature has two
+// readers, the channel scale r = f * a + f and the global average pool, so its gradient is
+// round(round(dr * (a + 1)) + round(dpooled / hw)) -- chscale_bwd_dx_kernel (mode 1) followed by
+// gap_bwd_kernel's accumulate, the expressions and roundings of functional.GradJoin's order.
+template <typename T>
+struct GradScalePool {
+  static constexpr bool kDirect = false;
+  const T *dr, *att, *dp;  // [rows][c], [n][c], [n][c]
+  int c;
+  long hw;
+  float inv;  // 1 / hw
+  template <int VEC> RT_DEV void load(long r, int ch0, float* g, int cvalid) const {
+    static_assert(VEC == 1, "scale + pool gradient source: narrow class maps, one channel per thread");
+    if (cvalid <= 0) { g[0] = 0.f; return; }
+    const long v = (r / hw) * c + ch0;
+    const T s = from_f<T>(to_f(dr[r * c + ch0]) * (to_f(att[v]) + 1.f));
+    const T p = from_f<T>(to_f(dp[v]) * inv);
+    g[0] = to_f(from_f<T>(to_f(s) + to_f(p)));
   }
 };
 
@@ -1017,6 +1064,51 @@ extern "C" int rtsds_bn_bwd(const void* dy, const void* x, const void* y, void* 
                             size_t ws_bytes, void* stream) {
   return rtsds_bn_bwd_ld(dy, c, x, y, dx, dres, dgamma, dbeta, rows, c, gamma, beta, save_mean, save_invstd, training, act,
                          accumulate_params, dtype, ws, ws_bytes, stream);
+}
+
+// Training-mode BatchNorm + activation of an [n][hw][c] feature whose global average pool is wanted
+// too: statistics / finalize as rtsds_bn_fwd, then one pass that applies and leaves the pool's
+// stage-1 partials (gap_part: rtsds_gap_workspace(n, hw, c) bytes, [n][chan_slices][c]).
+extern "C" int rtsds_bn_fwd_gap(const void* x, void* y, float* gap_part, int n, long hw, int c, const float* gamma, const float* beta,
+                                float* running_mean, float* running_var, long long* num_batches_tracked, float* save_mean,
+                                float* save_invstd, float momentum, float eps, int act, const float* stats_part, int stats_nrb,
+                                int dtype, void* ws, size_t ws_bytes, void* stream) {
+  if (n <= 0 || n > 65535 || hw <= 0 || c <= 0 || !x || !y || !gap_part) return RTSDS_ERR_SHAPE;
+  const long rows = (long)n * hw;
+  // the pool's scalar route only (c off the vector multiples), one channel chunk
+  if (c > 256 || c % (dtype == RTSDS_BF16 ? 8 : 4) == 0) return RTSDS_ERR_UNSUPPORTED;
+  if (ws_bytes < rtsds_bn_workspace(rows, c)) return RTSDS_ERR_WORKSPACE;
+  BnArgs a(rows, c, ws, stream);
+  if (int rc = bn_fwd_args(a, gamma, beta, running_mean, running_var, num_batches_tracked, save_mean, save_invstd, momentum, eps,
+                           1, stats_part, stats_nrb))
+    return rc;
+  a.x = x, a.y = y, a.ldy = c, a.act = act;
+  DISPATCH_T(dtype, {
+    bn_fwd_coefs<T, 1>(a);
+    hipLaunchKernelGGL(bn_apply_gap_kernel<T>, dim3(chan_slices(n, hw), n, 1), dim3(256), 0, a.st, (const T*)x, (T*)y, a.w.coef,
+                       a.w.coef + c, gap_part, hw, c, act);
+  });
+  RET_LAUNCH();
+}
+// rtsds_bn_bwd for the FeatureFusionModule's ConvBlock with the incoming gradient formed per element
+// from its two readers' (GradScalePool): dr [n][hw][c] the channel scale's output gradient,
+// att / dpooled [n][c].  No activation output kept (the mask is recomputed from x).
+extern "C" int rtsds_bn_bwd_ffm(const void* dr, const void* att, const void* dpooled, int n, long hw, const void* x, void* dx,
+                                float* dgamma, float* dbeta, int c, const float* gamma, const float* beta, const float* save_mean,
+                                const float* save_invstd, int training, int act, int accumulate_params, int dtype, void* ws,
+                                size_t ws_bytes, void* stream) {
+  if (n <= 0 || hw <= 0 || c <= 0 || !dr || !att || !dpooled || !x) return RTSDS_ERR_SHAPE;
+  const long rows = (long)n * hw;
+  if (c % (dtype == RTSDS_BF16 ? 8 : 4) == 0) return RTSDS_ERR_UNSUPPORTED;  // one channel per thread
+  if (!(act == RTSDS_ACT_NONE || act == RTSDS_ACT_RELU || act == RTSDS_ACT_LEAKY)) return RTSDS_ERR_UNSUPPORTED;
+  if (ws_bytes < rtsds_bn_workspace(rows, c)) return RTSDS_ERR_WORKSPACE;
+  BnArgs a(rows, c, ws, stream);
+  bn_bwd_args(a, x, dx, dgamma, dbeta, gamma, beta, save_mean, save_invstd, training, act, accumulate_params);
+  DISPATCH_T(dtype, {
+    const GradScalePool<T> gs{(const T*)dr, (const T*)att, (const T*)dpooled, c, hw, 1.f / (float)hw};
+    bn_bwd_launch<T, 1, GradScalePool<T>>(gs, a);
+  });
+  RET_LAUNCH();
 }
 
 // ---- BatchNorm + ReLU + MaxPool2d(3, 2, p) (the ResNet stem: bn1 -> relu -> maxpool,

@@ -3,6 +3,7 @@
 // cross-entropy with ignore_index, BCE-with-logits, argmax / pixel accuracy, confusion.
 #include "ew_common.h"
 #include "class_row.h"
+#include "chan_dev.h"
 
 // ------------------------------------------------------------------ global average pool
 // y[img][c] = mean_hw x[img][hw][c]   (AdaptiveAvgPool2d(1) / torch.mean over H,W:
@@ -13,87 +14,7 @@
 // laid out [row group][16-B channel vector] (VEC = 8 bf16 / 4 f32 when c allows, else 1) ->
 // part[img][s][c] fp32.  Stage 2 sums the S slices in order.  (One block per image would
 // leave all but n CUs idle: the ARM / FFM / tail pools have n = 8 images.)
-static int chan_slices(int n, long hw) {
-  return (int)std::max<long>(1, std::min<long>(hw / 32, std::max(1, 1024 / std::max(1, n))));
-}
-template <typename T, int VEC, bool DOT>
-__global__ void __launch_bounds__(256) chan_part_kernel(const T* __restrict__ a, const T* __restrict__ b, float* __restrict__ part,
-                                                        long hw, int c) {
-  __shared__ float red[256 * VEC];
-  const int s = blockIdx.x, S = gridDim.x, img = blockIdx.y;
-  const int cbase = blockIdx.z * 256 * VEC;
-  const int cl = min(c - cbase, 256 * VEC);
-  const int tpr = (cl + VEC - 1) / VEC, rpi = 256 / tpr;
-  const int tid = threadIdx.x, cv = tid % tpr, rg = tid / tpr;
-  const int ch0 = cbase + cv * VEC;
-  const long per = (hw + S - 1) / S, r0 = s * per, r1 = min(hw, r0 + per);
-  float acc[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
-  if (rg < rpi) {
-    const long base = (long)img * hw * c + ch0;
-    long r = r0 + rg;
-    for (; r + rpi < r1; r += 2 * rpi) {  // two rows in flight
-      const long o0 = base + r * c, o1 = o0 + (long)rpi * c;
-      if (VEC > 1) {
-        typedef typename VecT<T>::v16 V16;
-        const V16 a0 = *(const V16*)(a + o0), a1 = *(const V16*)(a + o1);
-        if (DOT) {
-          const V16 b0 = *(const V16*)(b + o0), b1 = *(const V16*)(b + o1);
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) acc[j] = fmaf(to_f(a1[j]), to_f(b1[j]), fmaf(to_f(a0[j]), to_f(b0[j]), acc[j]));
-        } else {
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) acc[j] += to_f(a0[j]) + to_f(a1[j]);
-        }
-      } else {
-        acc[0] = DOT ? fmaf(to_f(a[o1]), to_f(b[o1]), fmaf(to_f(a[o0]), to_f(b[o0]), acc[0])) : acc[0] + (to_f(a[o0]) + to_f(a[o1]));
-      }
-    }
-    for (; r < r1; r += rpi) {
-      const long o = base + r * c;
-      if (VEC > 1) {
-        typedef typename VecT<T>::v16 V16;
-        const V16 va = *(const V16*)(a + o);
-        if (DOT) {
-          const V16 vb = *(const V16*)(b + o);
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) acc[j] = fmaf(to_f(va[j]), to_f(vb[j]), acc[j]);
-        } else {
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) acc[j] += to_f(va[j]);
-        }
-      } else {
-        acc[0] = DOT ? fmaf(to_f(a[o]), to_f(b[o]), acc[0]) : acc[0] + to_f(a[o]);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) red[tid * VEC + j] = acc[j];
-  __syncthreads();
-  if (rg == 0 && cv * VEC < cl) {
-    for (int g = 1; g < rpi; ++g)
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) acc[j] += red[(g * tpr + cv) * VEC + j];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j)
-      if (ch0 + j < c) part[((long)img * S + s) * c + ch0 + j] = acc[j];
-  }
-}
-// p[0], p[c], .. p[(S - 1) c] summed in slice order, 8 loads in flight
-RT_DEV float slice_sum(const float* __restrict__ p, int S, int c) {
-  float s = 0.f;
-  int q = 0;
-  for (; q + 8 <= S; q += 8) {
-    float t[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t[u] = p[(long)(q + u) * c];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += t[u];
-  }
-  for (; q < S; ++q) s += p[(long)q * c];
-  return s;
-}
+// (the partition, the stage-1 loop and the slice sum: chan_dev.h)
 template <typename T>
 __global__ void __launch_bounds__(256) chan_final_kernel(const float* __restrict__ part, T* __restrict__ out, int S, int c, float scale) {
   const int img = blockIdx.y, ch = blockIdx.x * 256 + threadIdx.x;
@@ -287,6 +208,143 @@ extern "C" int rtsds_ffm_head_eval(const void* f, const void* w1, const float* b
     hipLaunchKernelGGL((ffm_head_apply_kernel<T, 19>), dim3(S, n), dim3(256), 0, st, (const float*)part, (const T*)f, (const T*)w1,
                        b1, (const T*)w2, b2, (const T*)w3, b3, (T*)out, (int)hw);
   });
+  RET_LAUNCH();
+}
+// Training form of the FeatureFusionModule's attention tail (build_bisenet.py:75-80) after the
+// BatchNorm apply that also left the GAP partials (rtsds_bn_fwd_gap): unfused these are
+// chan_final_kernel, pooled_mlp_fwd_kernel and chscale_fwd_kernel (mode 1).  Grid (pixel chunks,
+// N): every workgroup sums its image's partials in slice order (slice_sum's order; staged in LDS
+// when they fit, so the memory round trips do not queue), evaluates the two pooled convs for its
+// image with pooled_mlp_fwd_kernel's arithmetic (a wave per output channel, lanes over the input
+// channels, the wave's shuffle sum, then bias and activation) and maps its pixels
+// r = round(fma(f, a, f)).  The first workgroup of an image stores pooled / hid / att for the
+// backward.  Each intermediate is rounded to T where the unfused chain stores it.  r has pixel
+// pitch ldr: C (dense), or the zero-padded pitch a reading conv gathers (RTSDS_INPUT_PADDED),
+// written from an LDS copy of the chunk -- that conv's channel-pad launch is then not needed.
+static constexpr int kFfmPartMax = 256;  // slices per image whose partials are staged in LDS
+template <typename T, int C>
+__global__ void __launch_bounds__(256) ffm_att_scale_kernel(const float* __restrict__ part, int S, const T* __restrict__ f,
+                                                            const T* __restrict__ w1, const float* __restrict__ b1,
+                                                            const T* __restrict__ w2, const float* __restrict__ b2,
+                                                            T* __restrict__ pooled, T* __restrict__ hid_o, T* __restrict__ att_o,
+                                                            T* __restrict__ r, int hw, float inv, int ldr) {
+  typedef typename VecT<T>::v16 V16;
+  constexpr int V = VecT<T>::N;
+  constexpr int KI = (C + 3) / 4;                          // output channels per wave
+  constexpr int NV = (kFfmChunk * C / V + 255) / 256;      // pixel vectors per thread
+  static_assert(C <= 64, "one input channel per lane");
+  __shared__ float sp[kFfmPartMax * C];
+  __shared__ float gap[C], hid[C], att[C];
+  __shared__ __attribute__((aligned(16))) T stage[kFfmChunk * C];  // (ldr > C: the chunk's r before the padded stores)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, img = blockIdx.y;
+  const bool first = blockIdx.x == 0;
+  // weights, biases and this chunk's pixels in flight while the attention vector is formed
+  float w1v[KI], w2v[KI], b1v[KI], b2v[KI];
+#pragma unroll
+  for (int u = 0; u < KI; ++u) {
+    const int k = wave + 4 * u;
+    const bool ok = k < C && lane < C;
+    const int e = ok ? k * C + lane : 0;
+    w1v[u] = ok ? to_f(w1[e]) : 0.f;
+    w2v[u] = ok ? to_f(w2[e]) : 0.f;
+    b1v[u] = b1 && k < C ? b1[k] : 0.f;
+    b2v[u] = b2 && k < C ? b2[k] : 0.f;
+  }
+  const int p0 = blockIdx.x * kFfmChunk, np = min(kFfmChunk, hw - p0);  // np % V == 0 (host: hw % V == 0)
+  const int nvec = np * C / V;
+  const long off = ((long)img * hw + p0) * C;
+  const V16* src = (const V16*)(f + off);
+  V16 xv[NV];
+#pragma unroll
+  for (int u = 0; u < NV; ++u) xv[u] = src[min(tid + 256 * u, nvec - 1)];
+  // GAP: chan_final_kernel's sum
+  const float* pp = part + (long)img * S * C;
+  const bool staged = S <= kFfmPartMax;
+  if (staged)
+    for (int e = tid; e < S * C; e += 256) sp[e] = pp[e];
+  __syncthreads();
+  if (tid < C) {
+    float s = 0.f;
+    if (staged)
+      for (int q = 0; q < S; ++q) s += sp[q * C + tid];
+    else
+      s = slice_sum(pp + tid, S, C);
+    const T o = from_f<T>(s * inv);
+    gap[tid] = to_f(o);
+    if (first) pooled[(long)img * C + tid] = o;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < KI; ++u) {
+    const int k = wave + 4 * u;
+    if (k >= C) break;
+    float acc = 0.f;
+    if (lane < C) acc = fmaf(gap[lane], w1v[u], acc);
+    acc = wave_sum(acc);
+    if (lane == 0) {
+      const T o = from_f<T>(fmaxf(fmaf(acc, 1.f, b1v[u]), 0.f));
+      hid[k] = to_f(o);
+      if (first) hid_o[(long)img * C + k] = o;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < KI; ++u) {
+    const int k = wave + 4 * u;
+    if (k >= C) break;
+    float acc = 0.f;
+    if (lane < C) acc = fmaf(hid[lane], w2v[u], acc);
+    acc = wave_sum(acc);
+    if (lane == 0) {
+      const float v = fmaf(acc, 1.f, b2v[u]);
+      const T o = from_f<T>(1.f / (1.f + expf(-v)));
+      att[k] = to_f(o);
+      if (first) att_o[(long)img * C + k] = o;
+    }
+  }
+  __syncthreads();
+  const bool dense = ldr == C;
+  V16* dst = dense ? (V16*)(r + off) : (V16*)stage;
+#pragma unroll
+  for (int u = 0; u < NV; ++u) {
+    const int e = tid + 256 * u;
+    if (e >= nvec) break;
+    int ch = (e * V) % C;
+    V16 o;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const float x = to_f(xv[u][j]);
+      o[j] = from_f<T>(fmaf(x, att[ch], x));
+      ch = ch + 1 == C ? 0 : ch + 1;
+    }
+    dst[e] = o;
+  }
+  if (dense) return;
+  // pixel pitch ldr (a multiple of V), zero beyond C: the padded form the final conv gathers
+  __syncthreads();
+  const int vpp = ldr / V;
+  V16* out = (V16*)(r + ((long)img * hw + p0) * ldr);
+  for (int e = tid; e < np * vpp; e += 256) {
+    const int p = e / vpp, j0 = (e - p * vpp) * V;
+    V16 o;
+#pragma unroll
+    for (int j = 0; j < V; ++j) o[j] = j0 + j < C ? stage[p * C + j0 + j] : from_f<T>(0.f);
+    out[e] = o;
+  }
+}
+extern "C" int rtsds_ffm_att_scale(const float* part, const void* f, const void* w1, const float* b1, const void* w2,
+                                   const float* b2, void* pooled, void* hid, void* att, void* r, int ldr, int n, long hw, int c,
+                                   int dtype, void* stream) {
+  if (n <= 0 || n > 65535 || hw <= 0 || hw >= (1L << 31) / 64) return RTSDS_ERR_SHAPE;
+  if (c != 19) return RTSDS_ERR_UNSUPPORTED;  // instantiated for the 19-class maps
+  const int V = dtype == RTSDS_BF16 ? 8 : 4;
+  if (hw % V) return RTSDS_ERR_UNSUPPORTED;
+  if (ldr != c && (ldr < c || ldr % V || ldr > 64 || ((size_t)r & 15))) return RTSDS_ERR_UNSUPPORTED;
+  if (!part || !f || !w1 || !w2 || !pooled || !hid || !att || !r) return RTSDS_ERR_SHAPE;
+  const int S = chan_slices(n, hw);
+  DISPATCH_T(dtype, hipLaunchKernelGGL((ffm_att_scale_kernel<T, 19>), dim3((int)((hw + kFfmChunk - 1) / kFfmChunk), n), dim3(256),
+                                       0, (hipStream_t)stream, part, S, (const T*)f, (const T*)w1, b1, (const T*)w2, b2,
+                                       (T*)pooled, (T*)hid, (T*)att, (T*)r, (int)hw, 1.f / (float)hw, ldr));
   RET_LAUNCH();
 }
 extern "C" int rtsds_chscale_bwd(const void* dy, const void* x, const void* a, void* dx, void* da, int n, long hw, int c, int mode,

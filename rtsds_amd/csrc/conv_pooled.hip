@@ -2,6 +2,7 @@
 // attention convs), one launch per pass, and the FFM attention MLP's forward / backward in one
 // launch each (rtsds_pooled_mlp_fwd / _bwd).
 #include "conv_host.h"
+#include "chan_dev.h"
 
 template <typename T> RT_DEV typename VecT<T>::v16 vzero() {
   typename VecT<T>::v16 z;
@@ -276,8 +277,12 @@ int pooled_wgrad(const rtsds_conv_desc* d, const void* x, const void* dy, float*
 // wave's shuffle sum), the weight gradients as pooled_wgrad_kernel (sums over rows in order) --
 // so every result is bit-identical to the chain.
 static constexpr int kMlpMaxC = 64, kMlpMaxN = 8, kMlpThreads = 1024;  // 16 waves: a wave per input channel or two
-template <typename T>
-__global__ void __launch_bounds__(kMlpThreads) pooled_mlp_bwd_kernel(const T* __restrict__ da, const T* __restrict__ a, const T* __restrict__ h,
+// PART: da is not stored -- it is the channel scale's attention gradient sum_hw dr * f, summed here
+// from chan_part_kernel<T, 1, true>'s slice partials (part [n][S][c2]) as chan_final_kernel sums
+// and rounds them (rtsds_ffm_att_bwd).
+template <typename T, bool PART>
+__global__ void __launch_bounds__(kMlpThreads) pooled_mlp_bwd_kernel(const T* __restrict__ da, const float* __restrict__ part, int S,
+                                                             const T* __restrict__ a, const T* __restrict__ h,
                                                              const T* __restrict__ p, const T* __restrict__ w1, const T* __restrict__ w2,
                                                              float* __restrict__ dw1, float* __restrict__ db1, float* __restrict__ dw2,
                                                              float* __restrict__ db2, T* __restrict__ dp, int n, int c0, int c1, int c2,
@@ -301,7 +306,8 @@ __global__ void __launch_bounds__(kMlpThreads) pooled_mlp_bwd_kernel(const T* __
 #pragma unroll
     for (int u = 0; u < NV; ++u) {
       const int e = tid + kMlpThreads * u, m = min(e >> 6, n - 1), ch = e & 63;
-      vd[u] = to_f(da[m * c2 + min(ch, c2 - 1)]);
+      if constexpr (PART) vd[u] = to_f(from_f<T>(slice_sum<32>(part + (long)m * S * c2 + min(ch, c2 - 1), S, c2) * 1.f));
+      else vd[u] = to_f(da[m * c2 + min(ch, c2 - 1)]);
       va[u] = to_f(a[m * c2 + min(ch, c2 - 1)]);
       vh[u] = to_f(h[m * c1 + min(ch, c1 - 1)]);
       vp[u] = to_f(p[m * c0 + min(ch, c0 - 1)]);
@@ -452,8 +458,31 @@ extern "C" int rtsds_pooled_mlp_bwd(const void* da, const void* a, const void* h
                                     int accumulate, int dtype, void* stream) {
   if (int e = mlp_check(n, c0, c1, c2)) return e;
   if (!da || !a || !h || !p || !w1 || !w2 || !dw1 || !dw2 || !dp) return RTSDS_ERR_SHAPE;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(pooled_mlp_bwd_kernel<T>, dim3(1), dim3(kMlpThreads), 0, (hipStream_t)stream, (const T*)da,
-                                       (const T*)a, (const T*)h, (const T*)p, (const T*)w1, (const T*)w2, dw1, db1, dw2, db2,
-                                       (T*)dp, n, c0, c1, c2, accumulate ? 1 : 0));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((pooled_mlp_bwd_kernel<T, false>), dim3(1), dim3(kMlpThreads), 0, (hipStream_t)stream,
+                                       (const T*)da, (const float*)nullptr, 0, (const T*)a, (const T*)h, (const T*)p, (const T*)w1,
+                                       (const T*)w2, dw1, db1, dw2, db2, (T*)dp, n, c0, c1, c2, accumulate ? 1 : 0));
+  RET_LAUNCH();
+}
+// The FeatureFusionModule attention's whole backward from the channel scale's output gradient dr
+// and the feature f ([n][hw][c], r = f * a + f): the attention gradient's slice partials
+// (chan_part_kernel<T, 1, true>, as rtsds_chscale_bwd's da), then one launch that sums them and
+// runs rtsds_pooled_mlp_bwd's body.  Two launches for the chain's three; same bits.
+// ws: rtsds_gap_workspace(n, hw, c) bytes.
+extern "C" int rtsds_ffm_att_bwd(const void* dr, const void* f, const void* a, const void* h, const void* p, const void* w1,
+                                 const void* w2, float* dw1, float* db1, float* dw2, float* db2, void* dp, int n, long hw, int c,
+                                 int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  if (int e = mlp_check(n, c, c, c)) return e;
+  if (hw <= 0 || !dr || !f || !a || !h || !p || !w1 || !w2 || !dw1 || !dw2 || !dp) return RTSDS_ERR_SHAPE;
+  if (c % (dtype == RTSDS_BF16 ? 8 : 4) == 0) return RTSDS_ERR_UNSUPPORTED;  // the reductions' scalar route
+  const int S = chan_slices(n, hw);
+  if (ws_bytes < (size_t)n * S * c * 4) return RTSDS_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  float* part = (float*)ws;
+  DISPATCH_T(dtype, {
+    hipLaunchKernelGGL((chan_part_kernel<T, 1, true>), dim3(S, n, 1), dim3(256), 0, st, (const T*)dr, (const T*)f, part, hw, c);
+    hipLaunchKernelGGL((pooled_mlp_bwd_kernel<T, true>), dim3(1), dim3(kMlpThreads), 0, st, (const T*)nullptr, (const float*)part, S,
+                       (const T*)a, (const T*)h, (const T*)p, (const T*)w1, (const T*)w2, dw1, db1, dw2, db2, (T*)dp, n, c, c, c,
+                       accumulate ? 1 : 0);
+  });
   RET_LAUNCH();
 }

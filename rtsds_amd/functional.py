@@ -1242,6 +1242,115 @@ def pooled_mlp(p, w1, b1, wq1, w2, b2, wq2):
     return PooledMlpFn.apply(p, w1, b1, wq1, w2, b2, wq2)
 
 
+class FfmTailFn(torch.autograd.Function):
+    """Training-mode tail of the FeatureFusionModule after its 3x3 conv (build_bisenet.py:75-80):
+    feature = relu(bn(x)), att = sigmoid(conv2(relu(conv1(GAP(feature))))), r = feature * att +
+    feature -- BatchNormFn, GapFn, PooledMlpFn and ChScaleFn (mode 1) as one Function.
+
+    Forward: the BatchNorm apply also leaves the pool's slice partials (rtsds_bn_fwd_gap), then one
+    launch sums them, runs the two pooled convs and scales (rtsds_ffm_att_scale): 2 launches after
+    the finalize for the chain's 5.  Backward: the attention gradient's slice partials and one
+    launch for their sum + the pooled convs' backward (rtsds_ffm_att_bwd), then the BatchNorm
+    backward reading round(round(dr * (att + 1)) + round(dpooled / hw)) per element
+    (rtsds_bn_bwd_ffm) instead of the joined feature gradient the channel scale and the pool
+    would have written: 5 launches for the chain's 8.  Every result equals the chain's bit for
+    bit (each reduction keeps its partition and order)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, stats, stats_nrb, nbt,
+                w1, b1, wq1, w2, b2, wq2, pitch=0):
+        require_hip(x)
+        x = nhwc(x)
+        n, c, h, w = x.shape
+        hw = h * w
+        feature = torch.empty_like(x, memory_format=CL)
+        if pitch > c:  # r in the zero-padded pixel pitch its reader gathers (is_padded_input)
+            r = torch.empty((n, h, w, pitch), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2)[:, :c]
+        else:
+            pitch = c
+            r = torch.empty_like(x, memory_format=CL)
+        sm = torch.empty(c, dtype=torch.float32, device=x.device)
+        si = torch.empty(c, dtype=torch.float32, device=x.device)
+        pooled, hid, att = (empty_nhwc(n, c, 1, 1, x.dtype, x.device) for _ in range(3))
+        ws = workspace(lib.rtsds_bn_workspace(n * hw, c), x.device)
+        part = workspace(lib.rtsds_gap_workspace(n, hw, c), x.device)
+        lib.rtsds_bn_fwd_gap(_P(x), _P(feature), _P(part), n, hw, c, _P(gamma), _P(beta), _P(running_mean),
+                             _P(running_var), _P(nbt), _P(sm), _P(si), float(momentum), float(eps), ACT_RELU,
+                             _P(stats), int(stats_nrb or 0), dcode(x), _P(ws), ws.numel(), stream())
+        lib.rtsds_ffm_att_scale(_P(part), _P(feature), _P(wq1), _P(b1), _P(wq2), _P(b2), _P(pooled), _P(hid), _P(att),
+                                _P(r), pitch, n, hw, c, dcode(x), stream())
+        ctx.gamma, ctx.beta = gamma, beta
+        ctx.params = (w1, b1, w2, b2)
+        ctx.save_for_backward(x, feature, pooled, hid, att, wq1, wq2, gamma, beta, sm, si)
+        return r
+
+    @staticmethod
+    def backward(ctx, dr):
+        x, feature, pooled, hid, att, wq1, wq2, gamma, beta, sm, si = ctx.saved_tensors
+        w1, b1, w2, b2 = ctx.params
+        n, c, h, w = x.shape
+        hw = h * w
+        dr = nhwc(dr)
+        if dr.dtype != x.dtype:
+            dr = cast(dr, x.dtype)
+        sinks = _sinks(w1, b1, w2, b2)
+        if sinks is not None:
+            dw1, db1, dw2, db2 = sinks
+            acc = 1
+        else:
+            dw1 = torch.empty(c, c, 1, 1, dtype=torch.float32, device=x.device)
+            dw2 = torch.empty(c, c, 1, 1, dtype=torch.float32, device=x.device)
+            db1 = torch.empty(c, dtype=torch.float32, device=x.device) if b1 is not None else None
+            db2 = torch.empty(c, dtype=torch.float32, device=x.device) if b2 is not None else None
+            acc = 0
+        dp = empty_nhwc(n, c, 1, 1, x.dtype, x.device)
+        part = workspace(lib.rtsds_gap_workspace(n, hw, c), x.device)
+        lib.rtsds_ffm_att_bwd(_P(dr), _P(feature), _P(att), _P(hid), _P(pooled), _P(wq1), _P(wq2), _P(dw1), _P(db1),
+                              _P(dw2), _P(db2), _P(dp), n, hw, c, acc, dcode(x), _P(part), part.numel(), stream())
+        if acc:
+            dw1 = db1 = dw2 = db2 = None
+        dx = torch.empty_like(x, memory_format=CL) if ctx.needs_input_grad[0] else None
+        dg, db, bacc = _bn_param_grads(ctx, c, x.device)
+        ws = workspace(lib.rtsds_bn_workspace(n * hw, c), x.device)
+        lib.rtsds_bn_bwd_ffm(_P(dr), _P(att), _P(dp), n, hw, _P(x), _P(dx), _P(dg), _P(db), c, _P(gamma), _P(beta),
+                             _P(sm), _P(si), 1, ACT_RELU, bacc, dcode(x), _P(ws), ws.numel(), stream())
+        if bacc:
+            dg = db = None
+        return dx, dg, db, None, None, None, None, None, None, None, dw1, db1, None, dw2, db2, None, None
+
+
+def ffm_tail_ok(x, convs):
+    """Whether FfmTailFn takes ``x`` (the fusion module's conv output) with the 1x1 ``convs``: the
+    shapes its kernels are instantiated for and reproduce bit for bit -- 19-channel maps, N <= 8
+    (pooled_mlp_ok), hw a multiple of the 16-byte vector, square 1x1 convs of that width."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.bfloat16, torch.float32):
+        return False
+    n, c, h, w = x.shape
+    v = 8 if x.dtype == torch.bfloat16 else 4
+    return c == 19 and n <= 8 and (h * w) % v == 0 and \
+        all(m.kernel_size == (1, 1) and m.in_channels == m.out_channels == c and m.stride == (1, 1)
+            and m.padding == (0, 0) and m.groups == 1 for m in convs)
+
+
+def ffm_tail(x, gamma, beta, running_mean, running_var, momentum, eps, nbt, w1, b1, wq1, w2, b2, wq2, reader=None):
+    """``x``: the conv output, carrying its epilogue's BatchNorm statistics when it has them.
+    ``reader``: the conv module that alone reads the result (BiSeNet's final 1x1 conv): the result
+    is then written in the zero-padded pixel pitch that conv gathers (is_padded_input), which
+    saves its channel-pad launch; any other reader sees an ordinary [N, C, H, W] view."""
+    stats, nrb = _bn_epilogue_stats(x, True, running_mean)
+    pitch = 0
+    if reader is not None:
+        k, _, kh, kw = reader.weight.shape
+        d = _conv_desc(x, k, kh, kw, reader.stride, reader.padding, reader.dilation)
+        pitch = lib.rtsds_conv2d_input_pitch(ctypes.byref(d))
+        pitch = pitch if x.shape[1] < pitch <= 64 else 0
+    r = FfmTailFn.apply(x, gamma, beta, running_mean, running_var, momentum, eps, stats, nrb, nbt,
+                        w1, b1, wq1, w2, b2, wq2, pitch)
+    if pitch:
+        r._rt_cpad = pitch
+    return r
+
+
 class GapFn(torch.autograd.Function):
     """Mean over H, W keeping dims -> [N, C, 1, 1].  ``join``: GradJoin shared with the other
     reader of x (the attention modules' channel scale): the backward adds its broadcast into

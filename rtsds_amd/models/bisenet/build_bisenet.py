@@ -87,6 +87,11 @@ class FeatureFusionModule(torch.nn.Module):
     # with autograd: the attention (two pooled 1x1 convs) as functional.PooledMlpFn, whose
     # backward is one launch instead of six (False: the per-conv chain, for A/B tests)
     fused_attention = True
+    # training with autograd on a 19-class map: everything after the 3x3 conv -- BatchNorm apply,
+    # pool, attention, scale and their backward -- as functional.FfmTailFn, 7 launches for the
+    # chain's 13, and the result in the padded pitch BiSeNet's final conv gathers, one more
+    # (needs fused_attention; False or any other shape: the chain, for A/B tests)
+    fused_head = True
 
     def __init__(self, num_classes, in_channels):
         super().__init__()
@@ -98,9 +103,10 @@ class FeatureFusionModule(torch.nn.Module):
         self.sigmoid = Sigmoid()
         self.avgpool = AdaptiveAvgPool2d(output_size=(1, 1))
 
-    def forward(self, input_1, input_2=None, joins=None):
+    def forward(self, input_1, input_2=None, joins=None, reader=None):
         # input_2 may be the (cx1, cx2) pair itself: one concat pass instead of the
         # reference's nested cat (build_bisenet.py:153 then :72), same channel order.
+        # reader: the conv module that alone reads the result (functional.ffm_tail).
         # joins: GradJoin per concatenated input (functional.cat).  input_2 None: input_1 is
         # the concatenation already (BiSeNet's inference path writes it in place).
         if input_2 is None:
@@ -110,7 +116,22 @@ class FeatureFusionModule(torch.nn.Module):
             x = F.cat(parts, joins)
         assert self.in_channels == x.size(1), \
             "in_channels of ConvBlock should be {}".format(x.size(1))
-        feature = self.convblock(x)
+        cb = self.convblock
+        if self.fused_head and self.fused_attention and torch.is_grad_enabled() and x.is_cuda and \
+                (cb.bn.training or not cb.bn.track_running_stats) and cb.bn.momentum is not None and \
+                cb.conv1.in_channels != 3:  # (a 3-channel image conv pairs with its BatchNorm: nn.conv_bn)
+            y = cb.conv1(x, bn_stats=True)
+            if F.ffm_tail_ok(y, (self.conv1, self.conv2)):
+                bn = cb.bn
+                track = bn.track_running_stats
+                return F.ffm_tail(y, bn.weight, bn.bias, bn.running_mean if track else None,
+                                  bn.running_var if track else None, bn.momentum, bn.eps,
+                                  bn.num_batches_tracked if bn.training and track else None,
+                                  self.conv1.weight, self.conv1.bias, _shadow(self.conv1.weight, y.dtype),
+                                  self.conv2.weight, self.conv2.bias, _shadow(self.conv2.weight, y.dtype), reader)
+            feature = cb.bn(y, act="relu")  # the chain, from the conv output already made
+        else:
+            feature = cb(x)
         join = F.GradJoin(2) if torch.is_grad_enabled() and feature.requires_grad else None  # see ARM.forward
         pooled = F.global_avg_pool(feature, join)
         if self.fused_attention and torch.is_grad_enabled() and pooled.is_cuda and \
@@ -295,7 +316,8 @@ class BiSeNet(torch.nn.Module):
         # the two resizes write straight into the fusion module's concatenated input and read
         # their gradients straight from its gradient (functional.CatResizeFn; the reference:
         # interpolate, interpolate, cat)
-        result = self.feature_fusion_module(F.concat_resized(sx, (cx1, cx2), hw, joins=(j1, j2), into=into))
+        result = self.feature_fusion_module(F.concat_resized(sx, (cx1, cx2), hw, joins=(j1, j2), into=into),
+                                            reader=self.conv if self.with_interpolation else None)
         if self.with_interpolation:
             # reference: conv(up8(result)) (build_bisenet.py:165-167).  A 1x1 conv mixes channels
             # per pixel and bilinear resize mixes pixels per channel with weights summing to 1,
