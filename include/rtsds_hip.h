@@ -307,6 +307,17 @@ int rtsds_chscale_fwd(const void* x, const void* a, void* y, int n, long hw, int
                       int dtype, void* stream);
 int rtsds_chscale_bwd(const void* dy, const void* x, const void* a, void* dx, void* da, int n,
                       long hw, int c, int mode, int dtype, void* ws, size_t ws_bytes, void* stream);
+/* Two mode-0 scales in a row, y = round(round(x * a) * b) with a, b [n][c] (BiSeNet's
+ * cx2 = (f4 * att2) * tail, build_bisenet.py:52,149), without the intermediate tensor: the forward
+ * is one launch, the backward one pixel pass (dx, both gradients' slice partials) and one final
+ * launch for da / db.  Every result equals two rtsds_chscale_fwd / rtsds_chscale_bwd calls' bit
+ * for bit.  c a multiple of the 16-B vector length and 16-B aligned tensors only
+ * (RTSDS_ERR_UNSUPPORTED otherwise: the caller runs the two calls); dx must not alias dy or x;
+ * ws: 2 * rtsds_gap_workspace(n, hw, c) bytes.                                               */
+int rtsds_chscale2_fwd(const void* x, const void* a, const void* b, void* y, int n, long hw, int c,
+                       int dtype, void* stream);
+int rtsds_chscale2_bwd(const void* dy, const void* x, const void* a, const void* b, void* dx, void* da,
+                       void* db, int n, long hw, int c, int dtype, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- bilinear resize
  * F.interpolate(mode='bilinear', align_corners=False) (build_bisenet.py:151-152,158-159,166;
@@ -773,7 +784,7 @@ int rtsds_bn_bwd_ffm(const void* dr, const void* att, const void* dpooled, int n
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 22
+#define RTSDS_ABI_VERSION 23
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

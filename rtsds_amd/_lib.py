@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSDS_LIB: alternative in-tree build of the same ABI (kernel-variant A/B measurements)
 DEFAULT_LIB_PATH = os.path.join(_HERE, "librtsds_hip.so")
-ABI_VERSION = 22  # include/rtsds_hip.h RTSDS_ABI_VERSION
+ABI_VERSION = 23  # include/rtsds_hip.h RTSDS_ABI_VERSION
 LIB_PATH = os.environ.get("RTSDS_LIB") or DEFAULT_LIB_PATH
 
 F32, BF16 = 0, 1
@@ -113,6 +113,8 @@ SIGNATURES = {
     "rtsds_gap_bwd": (c_int, [P, P, c_int, c_long, c_int, c_int, c_int, P]),
     "rtsds_chscale_fwd": (c_int, [P, P, P, c_int, c_long, c_int, c_int, c_int, P]),
     "rtsds_chscale_bwd": (c_int, [P, P, P, P, P, c_int, c_long, c_int, c_int, c_int, P, c_size_t, P]),
+    "rtsds_chscale2_fwd": (c_int, [P, P, P, P, c_int, c_long, c_int, c_int, P]),
+    "rtsds_chscale2_bwd": (c_int, [P, P, P, P, P, P, P, c_int, c_long, c_int, c_int, P, c_size_t, P]),
     "rtsds_bilinear_fwd": (c_int, [P, P] + [c_int] * 6 + [c_float, c_float, c_int, c_int, c_int, P]),
     "rtsds_bilinear_fwd_scaled": (c_int, [P, P, P, P] + [c_int] * 6 + [c_float, c_float, c_int, c_int, c_int, P]),
     "rtsds_bilinear_bwd_workspace": (c_size_t, [c_int] * 6),

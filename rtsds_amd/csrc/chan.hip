@@ -108,10 +108,78 @@ __global__ void chscale_bwd_dx_kernel(const T* __restrict__ dy, const T* __restr
     dx[i] = from_f<T>(to_f(dy[i]) * av);
   }
 }
+// 16-B channel vectors (c % V == 0, 16-B aligned tensors): grid (chunks of an image's vectors, img),
+// one 32-bit division per vector instead of two 64-bit ones per element; the per-element
+// expressions are the scalar kernels' (BWD: chscale_bwd_dx_kernel's).  b: a second [n][c] scale
+// (mode 0 only), y = round(round(x * a) * b) -- two chscale_fwd_kernel launches without the
+// intermediate tensor (BiSeNet's cx2 = (f4 * att2) * tail, build_bisenet.py:52,149).
+template <typename T, bool BWD>
+__global__ void __launch_bounds__(256) chscale_vec_kernel(const T* __restrict__ x, const T* __restrict__ a, const T* __restrict__ b,
+                                                          T* __restrict__ y, unsigned per_img, unsigned cv, int mode) {
+  typedef typename VecT<T>::v16 V16;
+  constexpr int V = VecT<T>::N;
+  const long img = blockIdx.y;
+  const V16* xi = (const V16*)x + img * per_img;
+  const V16* ai = (const V16*)a + img * cv;
+  const V16* bi = b ? (const V16*)b + img * cv : nullptr;
+  V16* yi = (V16*)y + img * per_img;
+  for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < per_img; e += gridDim.x * 256u) {
+    const unsigned q = e % cv;
+    const V16 xv = xi[e], av = ai[q];
+    V16 o;
+    if (BWD) {
+      const float one = mode ? 1.f : 0.f;
+#pragma unroll
+      for (int j = 0; j < V; ++j) o[j] = from_f<T>(to_f(xv[j]) * (to_f(av[j]) + one));
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const float xf = to_f(xv[j]), af = to_f(av[j]);
+        o[j] = from_f<T>(mode ? fmaf(xf, af, xf) : xf * af);
+      }
+      if (bi) {
+        const V16 bv = bi[q];
+#pragma unroll
+        for (int j = 0; j < V; ++j) o[j] = from_f<T>(to_f(o[j]) * to_f(bv[j]));
+      }
+    }
+    yi[e] = o;
+  }
+}
+// whether the vector kernels take the tensors: whole 16-B channel vectors, 16-B aligned, 32-bit
+// vector indices within an image
+template <typename T>
+static bool chscale_vec_ok(int n, long hw, int c, std::initializer_list<const void*> ptrs) {
+  constexpr int V = VecT<T>::N;
+  if (c % V || n > 65535 || hw * (c / V) >= (1L << 31)) return false;
+  for (const void* p : ptrs)
+    if ((size_t)p & 15) return false;
+  return true;
+}
+template <typename T, bool BWD>
+static void chscale_vec(const T* x, const T* a, const T* b, T* y, int n, long hw, int c, int mode, hipStream_t st) {
+  const long per_img = hw * (c / VecT<T>::N);
+  hipLaunchKernelGGL((chscale_vec_kernel<T, BWD>), dim3(ew_blocks(per_img, 256, std::max(1, 8192 / n)), n), dim3(256), 0, st, x, a, b, y,
+                     (unsigned)per_img, (unsigned)(c / VecT<T>::N), mode);
+}
 extern "C" int rtsds_chscale_fwd(const void* x, const void* a, void* y, int n, long hw, int c, int mode, int dtype, void* stream) {
   const long total = (long)n * hw * c;
   if (total <= 0) return RTSDS_ERR_SHAPE;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(chscale_fwd_kernel<T>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)a, (T*)y, n, hw, c, mode));
+  DISPATCH_T(dtype, {
+    if (chscale_vec_ok<T>(n, hw, c, {x, a, y}))
+      chscale_vec<T, false>((const T*)x, (const T*)a, (const T*)nullptr, (T*)y, n, hw, c, mode, (hipStream_t)stream);
+    else
+      hipLaunchKernelGGL(chscale_fwd_kernel<T>, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)a, (T*)y, n, hw, c, mode);
+  });
+  RET_LAUNCH();
+}
+extern "C" int rtsds_chscale2_fwd(const void* x, const void* a, const void* b, void* y, int n, long hw, int c, int dtype,
+                                  void* stream) {
+  if (n <= 0 || hw <= 0 || c <= 0 || !x || !a || !b || !y) return RTSDS_ERR_SHAPE;
+  DISPATCH_T(dtype, {
+    if (!chscale_vec_ok<T>(n, hw, c, {x, a, b, y})) return RTSDS_ERR_UNSUPPORTED;
+    chscale_vec<T, false>((const T*)x, (const T*)a, (const T*)b, (T*)y, n, hw, c, 0, (hipStream_t)stream);
+  });
   RET_LAUNCH();
 }
 // Inference tail of the FeatureFusionModule plus BiSeNet's final 1x1 conv (build_bisenet.py:75-80,
@@ -347,6 +415,90 @@ extern "C" int rtsds_ffm_att_scale(const float* part, const void* f, const void*
                                        (T*)pooled, (T*)hid, (T*)att, (T*)r, (int)hw, 1.f / (float)hw, ldr));
   RET_LAUNCH();
 }
+// The channel scale's backward in one pixel pass (c % V == 0): stage 1 of da = sum_hw dy * x reads
+// dy through a functor that also stores dx = round(dy * (a + mode)), chscale_bwd_dx_kernel's
+// expression -- every element is read by exactly one thread of chan_part_body's partition (as
+// bn.hip's BnApplyLoad stores y).  The partials are chan_part_kernel<T, V, true>'s.
+template <typename T, int VEC>
+struct ScaleGradLoad {
+  typedef typename VecT<T>::v16 V16;
+  const T* dy;
+  T* dx;
+  float f[VEC];  // a + mode of the thread's channels
+  RT_DEV float at(long o) const { return to_f(dy[o]); }  // (VEC > 1 only)
+  RT_DEV V16 vec(long o) const {
+    const V16 g = *(const V16*)(dy + o);
+    V16 d;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) d[j] = from_f<T>(to_f(g[j]) * f[j]);
+    *(V16*)(dx + o) = d;
+    return g;
+  }
+};
+template <typename T, int VEC>
+__global__ void __launch_bounds__(256) chscale_bwd_part_kernel(const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ a,
+                                                               T* __restrict__ dx, float* __restrict__ part, long hw, int c, int mode) {
+  typedef typename VecT<T>::v16 V16;
+  __shared__ float red[256 * VEC];
+  const V16 av = *(const V16*)(a + (long)blockIdx.y * c + chan_part_channel<VEC>(c));
+  ScaleGradLoad<T, VEC> ld{dy, dx, {}};
+  const float one = mode ? 1.f : 0.f;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) ld.f[j] = to_f(av[j]) + one;
+  chan_part_body<T, VEC, true>(ld, x, part, hw, c, red);
+}
+// Backward of y = round(round(x * a) * b) (chscale_vec_kernel with b) in one pass over dy and x,
+// for the chain's chscale_bwd_dx + chan_part<DOT> of the outer scale and then of the inner one:
+// y1 = round(x * a) and dy1 = round(dy * b) are formed again per element, dx = round(dy1 * a),
+// set 0 = sum dy1 * x (a's gradient), set 1 = sum dy * y1 (b's gradient).
+template <typename T, int VEC>
+struct Scale2GradRow {
+  typedef typename VecT<T>::v16 V16;
+  const T* dy;
+  const T* x;
+  T* dx;
+  float a[VEC], b[VEC];  // the scales as chscale_bwd_dx_kernel takes them (+ 0.f: mode 0)
+  RT_DEV void row(long o, float* acc_a, float* acc_b) const {
+    const V16 g = *(const V16*)(dy + o), xv = *(const V16*)(x + o);
+    V16 d;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      const float gf = to_f(g[j]), xf = to_f(xv[j]);
+      const float y1 = to_f(from_f<T>(xf * a[j]));
+      const float g1 = to_f(from_f<T>(gf * (b[j] + 0.f)));
+      d[j] = from_f<T>(g1 * (a[j] + 0.f));
+      acc_a[j] = fmaf(g1, xf, acc_a[j]);
+      acc_b[j] = fmaf(gf, y1, acc_b[j]);
+    }
+    *(V16*)(dx + o) = d;
+  }
+};
+template <typename T, int VEC>
+__global__ void __launch_bounds__(256) chscale2_bwd_part_kernel(const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ a,
+                                                                const T* __restrict__ b, T* __restrict__ dx, float* __restrict__ part_a,
+                                                                float* __restrict__ part_b, long hw, int c) {
+  typedef typename VecT<T>::v16 V16;
+  __shared__ float red[2 * 256 * VEC];
+  const long so = (long)blockIdx.y * c + chan_part_channel<VEC>(c);
+  const V16 av = *(const V16*)(a + so), bv = *(const V16*)(b + so);
+  Scale2GradRow<T, VEC> f{dy, x, dx, {}, {}};
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    f.a[j] = to_f(av[j]);
+    f.b[j] = to_f(bv[j]);
+  }
+  chan_part2_body<T, VEC>(f, part_a, part_b, hw, c, red);
+}
+// chan_final_kernel (scale 1) of two partial sets in one launch: blockIdx.z picks the set
+template <typename T>
+__global__ void __launch_bounds__(256) chan_final2_kernel(const float* __restrict__ part0, const float* __restrict__ part1,
+                                                          T* __restrict__ out0, T* __restrict__ out1, int S, int c) {
+  const int img = blockIdx.y, ch = blockIdx.x * 256 + threadIdx.x;
+  if (ch >= c) return;
+  const float* part = blockIdx.z ? part1 : part0;
+  T* out = blockIdx.z ? out1 : out0;
+  out[(long)img * c + ch] = from_f<T>(slice_sum(part + (long)img * S * c + ch, S, c) * 1.f);
+}
 extern "C" int rtsds_chscale_bwd(const void* dy, const void* x, const void* a, void* dx, void* da, int n, long hw, int c, int mode,
                                  int dtype, void* ws, size_t ws_bytes, void* stream) {
   const long total = (long)n * hw * c;
@@ -354,8 +506,40 @@ extern "C" int rtsds_chscale_bwd(const void* dy, const void* x, const void* a, v
   if (da && ws_bytes < rtsds_gap_workspace(n, hw, c)) return RTSDS_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_T(dtype, {
-    if (dx) hipLaunchKernelGGL(chscale_bwd_dx_kernel<T>, dim3(ew_blocks(total)), dim3(256), 0, st, (const T*)dy, (const T*)a, (T*)dx, n, hw, c, mode);
-    if (da) chan_reduce<T, true>((const T*)dy, (const T*)x, (T*)da, n, hw, c, 1.f, (float*)ws, st);
+    constexpr int V = VecT<T>::N;
+    if (dx && da && chscale_vec_ok<T>(n, hw, c, {dy, x, a, dx})) {  // one pixel pass for both
+      const int S = chan_slices(n, hw);
+      hipLaunchKernelGGL((chscale_bwd_part_kernel<T, V>), dim3(S, n, rt_cdiv(c, 256 * V)), dim3(256), 0, st, (const T*)dy,
+                         (const T*)x, (const T*)a, (T*)dx, (float*)ws, hw, c, mode);
+      hipLaunchKernelGGL(chan_final_kernel<T>, dim3(rt_cdiv(c, 256), n), dim3(256), 0, st, (const float*)ws, (T*)da, S, c, 1.f);
+    } else {
+      if (dx && chscale_vec_ok<T>(n, hw, c, {dy, a, dx}))
+        chscale_vec<T, true>((const T*)dy, (const T*)a, (const T*)nullptr, (T*)dx, n, hw, c, mode, st);
+      else if (dx)
+        hipLaunchKernelGGL(chscale_bwd_dx_kernel<T>, dim3(ew_blocks(total)), dim3(256), 0, st, (const T*)dy, (const T*)a, (T*)dx, n, hw, c, mode);
+      if (da) chan_reduce<T, true>((const T*)dy, (const T*)x, (T*)da, n, hw, c, 1.f, (float*)ws, st);
+    }
+  });
+  RET_LAUNCH();
+}
+// Backward of rtsds_chscale2_fwd, y = round(round(x * a) * b): the chain's two rtsds_chscale_bwd
+// (four pixel passes, two finals) as one pixel pass and one final launch.
+extern "C" int rtsds_chscale2_bwd(const void* dy, const void* x, const void* a, const void* b, void* dx, void* da, void* db, int n,
+                                  long hw, int c, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  if (n <= 0 || hw <= 0 || c <= 0 || !dy || !x || !a || !b || !dx || !da || !db) return RTSDS_ERR_SHAPE;
+  const size_t set = (size_t)n * chan_slices(n, hw) * c;  // floats per partial set
+  if (ws_bytes < 2 * set * 4 || ((size_t)ws & 15)) return RTSDS_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_T(dtype, {
+    constexpr int V = VecT<T>::N;
+    if (!chscale_vec_ok<T>(n, hw, c, {dy, x, a, b, dx})) return RTSDS_ERR_UNSUPPORTED;
+    const int S = chan_slices(n, hw);
+    float* pa = (float*)ws;
+    float* pb = pa + set;
+    hipLaunchKernelGGL((chscale2_bwd_part_kernel<T, V>), dim3(S, n, rt_cdiv(c, 256 * V)), dim3(256), 0, st, (const T*)dy, (const T*)x,
+                       (const T*)a, (const T*)b, (T*)dx, pa, pb, hw, c);
+    hipLaunchKernelGGL(chan_final2_kernel<T>, dim3(rt_cdiv(c, 256), n, 2), dim3(256), 0, st, (const float*)pa, (const float*)pb, (T*)da,
+                       (T*)db, S, c);
   });
   RET_LAUNCH();
 }

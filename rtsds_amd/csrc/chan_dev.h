@@ -93,6 +93,58 @@ __global__ void __launch_bounds__(256) chan_part_kernel(const T* __restrict__ a,
   __shared__ float red[256 * VEC];
   chan_part_body<T, VEC, DOT>(ChanLoad<T>{a}, b, part, hw, c, red);
 }
+// First channel of the calling thread's vector in chan_part_body's layout (c % VEC == 0: inside c
+// for every thread), for operand functors that carry per-channel values.
+template <int VEC>
+RT_DEV int chan_part_channel(int c) {
+  const int cbase = blockIdx.z * 256 * VEC;
+  const int tpr = (min(c - cbase, 256 * VEC) + VEC - 1) / VEC;
+  return cbase + (threadIdx.x % tpr) * VEC;
+}
+// Two DOT reductions in one pass over the pixels: part0 / part1 exactly as two
+// chan_part_body<T, VEC, true> passes leave them -- the same partition, and per set the same fma
+// chain (a thread's rows in order; the two-rows-in-flight form above is that chain too) and the
+// same row-group sum.  f.row(o, acc0, acc1) adds the VEC products at element offset o to each
+// set's accumulators with one fmaf per channel.  c % VEC == 0; red: 2 * 256 * VEC floats of LDS.
+template <typename T, int VEC, class F>
+RT_DEV void chan_part2_body(const F& f, float* __restrict__ part0, float* __restrict__ part1, long hw, int c, float* red) {
+  const int s = blockIdx.x, S = gridDim.x, img = blockIdx.y;
+  const int cbase = blockIdx.z * 256 * VEC;
+  const int cl = min(c - cbase, 256 * VEC);
+  const int tpr = (cl + VEC - 1) / VEC, rpi = 256 / tpr;
+  const int tid = threadIdx.x, cv = tid % tpr, rg = tid / tpr;
+  const int ch0 = cbase + cv * VEC;
+  const long per = (hw + S - 1) / S, r0 = s * per, r1 = min(hw, r0 + per);
+  float acc0[VEC], acc1[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) acc0[j] = acc1[j] = 0.f;
+  if (rg < rpi) {
+    const long base = (long)img * hw * c + ch0;
+#pragma unroll 2
+    for (long r = r0 + rg; r < r1; r += rpi) f.row(base + r * c, acc0, acc1);
+  }
+  float* red1 = red + 256 * VEC;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    red[tid * VEC + j] = acc0[j];
+    red1[tid * VEC + j] = acc1[j];
+  }
+  __syncthreads();
+  if (rg == 0 && cv * VEC < cl) {
+    for (int g = 1; g < rpi; ++g)
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        acc0[j] += red[(g * tpr + cv) * VEC + j];
+        acc1[j] += red1[(g * tpr + cv) * VEC + j];
+      }
+    const long o = ((long)img * S + s) * c + ch0;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      part0[o + j] = acc0[j];
+      part1[o + j] = acc1[j];
+    }
+  }
+}
 // p[0], p[c], .. p[(S - 1) c] summed in slice order, U loads in flight (the adds stay one chain
 // in slice order, so U changes no bit)
 template <int U = 8>

@@ -1386,10 +1386,12 @@ def global_avg_pool(x, join=None):
 
 class ChScaleFn(torch.autograd.Function):
     """x * a[N,C,1,1] (mode 0) or x * a + x (mode 1).  ``join``: GradJoin shared with x's
-    other reader (GapFn); ``join_a``: the same for a's other reader."""
+    other reader (GapFn); ``join_a``: the same for a's other reader.  ``fused``: the backward's
+    dx and da from one rtsds_chscale_bwd call (one pixel pass where the library has it); False:
+    one call each, the separate passes (for A/B tests; the same bits)."""
 
     @staticmethod
-    def forward(ctx, x, a, mode, join=None, join_a=None):
+    def forward(ctx, x, a, mode, join=None, join_a=None, fused=True):
         require_hip(x, a)
         x = nhwc(x)
         a = a.contiguous()
@@ -1399,7 +1401,7 @@ class ChScaleFn(torch.autograd.Function):
         y = torch.empty_like(x, memory_format=CL)
         lib.rtsds_chscale_fwd(_P(x), _P(a), _P(y), n, h * w, c, mode, dcode(x), stream())
         ctx.mode = mode
-        ctx.join, ctx.join_a = join, join_a
+        ctx.join, ctx.join_a, ctx.fused = join, join_a, fused
         ctx.save_for_backward(x, a)
         return y
 
@@ -1411,18 +1413,74 @@ class ChScaleFn(torch.autograd.Function):
         dx = torch.empty_like(x, memory_format=CL) if ctx.needs_input_grad[0] else None
         da = torch.empty_like(a) if ctx.needs_input_grad[1] else None
         ws = workspace(lib.rtsds_gap_workspace(n, h * w, c) if da is not None else 0, x.device)
-        lib.rtsds_chscale_bwd(_P(dy), _P(x), _P(a), _P(dx), _P(da), n, h * w, c, ctx.mode,
-                              dcode(x), _P(ws), ws.numel(), stream())
+        for gx, ga in ((dx, da),) if ctx.fused else ((dx, None), (None, da)):
+            if gx is not None or ga is not None:
+                lib.rtsds_chscale_bwd(_P(dy), _P(x), _P(a), _P(gx), _P(ga), n, h * w, c, ctx.mode,
+                                      dcode(x), _P(ws), ws.numel(), stream())
         if dx is not None and ctx.join is not None:
             dx = _join_add(ctx.join, dx)
         if da is not None and ctx.join_a is not None:
             da = _join_add(ctx.join_a, da)
-        return dx, da, None, None, None
+        return dx, da, None, None, None, None
 
 
-def channel_scale(x, a, residual=False, join=None, join_a=None):
+def channel_scale(x, a, residual=False, join=None, join_a=None, fused=True):
     """``join`` / ``join_a``: GradJoin shared with x's / a's other reader (see GapFn)."""
-    return ChScaleFn.apply(x, a, 1 if residual else 0, join, join_a)
+    return ChScaleFn.apply(x, a, 1 if residual else 0, join, join_a, fused)
+
+
+class ChScale2Fn(torch.autograd.Function):
+    """(x * a) * b with a, b [N,C,1,1] -- BiSeNet's cx2 = ARM2(f4) * tail (build_bisenet.py:52,
+    149) -- as one Function: two ChScaleFn (mode 0) without the intermediate tensor written, read
+    back and saved.  Forward one launch (rtsds_chscale2_fwd) for two; backward one pixel pass and
+    one final launch (rtsds_chscale2_bwd) for the chain's four passes and two finals.  Bit-identical
+    to the chain: the intermediate and its gradient are rounded per element as the chain stores
+    them, each reduction keeps its partition and order.  ``join`` / ``join_b``: GradJoin shared
+    with x's / b's other reader, fed in the chain's order."""
+
+    @staticmethod
+    def forward(ctx, x, a, b, join=None, join_b=None):
+        require_hip(x, a, b)
+        x = nhwc(x)
+        n, c, h, w = x.shape
+        a, b = (cast(t.contiguous(), x.dtype) for t in (a, b))
+        y = torch.empty_like(x, memory_format=CL)
+        lib.rtsds_chscale2_fwd(_P(x), _P(a), _P(b), _P(y), n, h * w, c, dcode(x), stream())
+        ctx.join, ctx.join_b = join, join_b
+        ctx.save_for_backward(x, a, b)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, a, b = ctx.saved_tensors
+        n, c, h, w = x.shape
+        dy = nhwc(dy)
+        if dy.dtype != x.dtype:
+            dy = cast(dy, x.dtype)
+        dx = torch.empty_like(x, memory_format=CL)
+        da, db = torch.empty_like(a), torch.empty_like(b)
+        ws = workspace(2 * lib.rtsds_gap_workspace(n, h * w, c), x.device)
+        lib.rtsds_chscale2_bwd(_P(dy), _P(x), _P(a), _P(b), _P(dx), _P(da), _P(db), n, h * w, c, dcode(x),
+                               _P(ws), ws.numel(), stream())
+        # the chain's order: the outer scale's db, then the inner scale's dx
+        db = _join_add(ctx.join_b, db) if ctx.needs_input_grad[2] else None
+        dx = _join_add(ctx.join, dx) if ctx.needs_input_grad[0] else None
+        return dx, (da if ctx.needs_input_grad[1] else None), db, None, None
+
+
+def channel_scale2_ok(x, a, b):
+    """Whether ChScale2Fn takes (x * a) * b: HIP tensors of one bf16 / fp32 dtype, whole 16-byte
+    channel vectors (what rtsds_chscale2_fwd / _bwd are written for)."""
+    if x.dim() != 4 or not x.is_cuda or x.dtype not in (torch.bfloat16, torch.float32):
+        return False
+    n, c = x.shape[0], x.shape[1]
+    return c % (8 if x.dtype == torch.bfloat16 else 4) == 0 and n <= 65535 and \
+        all(t.dtype == x.dtype and tuple(t.shape) == (n, c, 1, 1) for t in (a, b))
+
+
+def channel_scale2(x, a, b, join=None, join_b=None):
+    """``join`` / ``join_b``: GradJoin shared with x's / b's other reader (see GapFn)."""
+    return ChScale2Fn.apply(x, a, b, join, join_b)
 
 
 # ----------------------------------------------------------------------------- bilinear

@@ -50,6 +50,11 @@ class AttentionRefinementModule(torch.nn.Module):
     """GAP -> 1x1 conv(bias) -> BN -> sigmoid -> x*a (build_bisenet.py:35-53).
     BN+sigmoid fused; BN statistics are over the N pooled vectors, as in the reference."""
 
+    # with autograd: the scale's backward as one pixel pass (dx stored by the attention gradient's
+    # stage-1 read) and, for BiSeNet's ARM2, its scale and the tail's as functional.ChScale2Fn
+    # (False: the per-op chain, for A/B tests)
+    fused_train = True
+
     def __init__(self, in_channels, out_channels):
         super().__init__()
         self.conv = Conv2d(in_channels, out_channels, kernel_size=1)
@@ -78,7 +83,18 @@ class AttentionRefinementModule(torch.nn.Module):
         if pooled is None and join is None:
             join = F.GradJoin(2) if torch.is_grad_enabled() and input.requires_grad else None
         att = self.attention(input, pooled, join if pooled is None else None, pooled_join)
-        return F.channel_scale(input, att, join=join)
+        return F.channel_scale(input, att, join=join, fused=self.fused_train)
+
+    def forward_scaled(self, input, scale, pooled, join=None, pooled_join=None, scale_join=None):
+        """forward(input, pooled, ...) * scale[N, C, 1, 1] (BiSeNet's cx2 = ARM2(f4) * tail);
+        ``scale_join``: GradJoin of scale's readers."""
+        if self.fused_train and torch.is_grad_enabled():
+            att = self.attention(input, pooled, None, pooled_join)
+            if F.channel_scale2_ok(input, att, scale):
+                return F.channel_scale2(input, att, scale, join=join, join_b=scale_join)
+            return F.channel_scale(F.channel_scale(input, att, join=join), scale, join_a=scale_join)
+        return F.channel_scale(self(input, pooled=pooled, join=join, pooled_join=pooled_join), scale,
+                               join_a=scale_join, fused=self.fused_train)
 
 
 class FeatureFusionModule(torch.nn.Module):
@@ -274,8 +290,8 @@ class BiSeNet(torch.nn.Module):
         if cat is None:
             cx1 = self.attention_refinement_module1(f3)
             # ARM2's global average pool is the tail itself (same kernel, same f4)
-            cx2 = F.channel_scale(self.attention_refinement_module2(f4, pooled=tail, join=j4, pooled_join=jt), tail,
-                                  join_a=jt)
+            cx2 = self.attention_refinement_module2.forward_scaled(f4, tail, pooled=tail, join=j4, pooled_join=jt,
+                                                                   scale_join=jt)
         if infer:
             if cat is None:  # a geometry outside the fused resize
                 cat = F.concat_resized(sx, (cx1, cx2), hw)
