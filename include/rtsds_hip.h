@@ -231,6 +231,50 @@ int rtsds_bn_bwd_part(const void* dy, const void* x, void* dx, float* dgamma, fl
                       int training, int act, int accumulate_params, const float* part, int nrb, int dtype, void* ws,
                       size_t ws_bytes, void* stream);
 
+/* Training-mode residual BatchNorm + ReLU, y = relu(bn(x) + res), that keeps one mask bit per
+ * element for its backward instead of y (bf16 / fp32, c % 8 == 0).  bits: one byte per 16-byte
+ * channel vector of a row, [rows][c / V] with V = 8 (bf16) or 4 (fp32), rtsds_bn_bits_bytes(rows,
+ * c, dtype) bytes (0: unsupported); bit j of a byte = (y[ch0 + j] > 0) of the value as stored.
+ * rtsds_bn_fwd_bits: rtsds_bn_fwd(training = 1, act = RELU, res != NULL) plus the bits.
+ * rtsds_bn_bwd_bits: rtsds_bn_bwd_ld(training = 1, act = RELU, y) with the mask read from bits;
+ * dx and dres both wanted.  Results are bit for bit those of the calls named.             */
+size_t rtsds_bn_bits_bytes(long rows, int c, int dtype);
+int rtsds_bn_fwd_bits(const void* x, const void* res, void* y, uint8_t* bits, long rows, int c, const float* gamma,
+                      const float* beta, float* running_mean, float* running_var, long long* num_batches_tracked,
+                      float* save_mean, float* save_invstd, float momentum, float eps, const float* stats_part,
+                      int stats_nrb, int dtype, void* ws, size_t ws_bytes, void* stream);
+int rtsds_bn_bwd_bits(const void* dy, long ldy, const void* x, const uint8_t* bits, void* dx, void* dres, float* dgamma,
+                      float* dbeta, long rows, int c, const float* gamma, const float* beta, const float* save_mean,
+                      const float* save_invstd, int accumulate_params, int dtype, void* ws, size_t ws_bytes,
+                      void* stream);
+/* The two BatchNorms at the end of a residual block with a downsample branch, on tensors of one
+ * [rows][c] shape, in three launches per direction: y = relu(bnA(xa) + round(bnB(xb))), where xa is
+ * the raw output of the block's last conv and xb of its downsample conv; the rounded inner value
+ * is the skip tensor the separate calls store, which is never written.  Bit for bit
+ * rtsds_bn_fwd(xb; act NONE) -> rtsds_bn_fwd(xa, res = skip; RELU) and, backward,
+ * rtsds_bn_bwd(A: dx = dxa, dres = g) -> rtsds_bn_bwd(B: dy = g, dx = dxb), both in training mode.
+ * One rtsds_bn_params per BatchNorm: the forward reads gamma .. eps (stats_part as rtsds_bn_fwd),
+ * the backward gamma, beta, save_*, dgamma, dbeta, accumulate.  bits as rtsds_bn_fwd_bits.
+ * Workspace: rtsds_bn_pair_workspace(rows, c).                                             */
+typedef struct rtsds_bn_params {
+  const float *gamma, *beta;
+  float *running_mean, *running_var;
+  long long* num_batches_tracked;
+  float *save_mean, *save_invstd;
+  float momentum, eps;
+  const float* stats_part;
+  int stats_nrb;
+  int accumulate;
+  float *dgamma, *dbeta;
+} rtsds_bn_params;
+size_t rtsds_bn_pair_workspace(long rows, int c);
+int rtsds_bn_pair_fwd(const void* xa, const void* xb, void* y, uint8_t* bits, long rows, int c,
+                      const rtsds_bn_params* pa, const rtsds_bn_params* pb, int dtype, void* ws, size_t ws_bytes,
+                      void* stream);
+int rtsds_bn_pair_bwd(const void* dy, long ldy, const void* xa, const void* xb, const uint8_t* bits, void* dxa,
+                      void* dxb, long rows, int c, const rtsds_bn_params* pa, const rtsds_bn_params* pb, int dtype,
+                      void* ws, size_t ws_bytes, void* stream);
+
 /* BatchNorm2d + ReLU + MaxPool2d(3, 2, p in {0,1}) fused -- the ResNet stem bn1 -> relu ->
  * maxpool (build_contextpath.py:15-18 via torchvision resnet.py; deeplabv2.py:106-110, ceil
  * mode via ho / wo).  bf16, c % 8 == 0.  x: the conv output [n][h][w][c]; y: pooled
@@ -784,7 +828,7 @@ int rtsds_bn_bwd_ffm(const void* dr, const void* att, const void* dpooled, int n
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 23
+#define RTSDS_ABI_VERSION 24
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSDS_LIB: alternative in-tree build of the same ABI (kernel-variant A/B measurements)
 DEFAULT_LIB_PATH = os.path.join(_HERE, "librtsds_hip.so")
-ABI_VERSION = 23  # include/rtsds_hip.h RTSDS_ABI_VERSION
+ABI_VERSION = 24  # include/rtsds_hip.h RTSDS_ABI_VERSION
 LIB_PATH = os.environ.get("RTSDS_LIB") or DEFAULT_LIB_PATH
 
 F32, BF16 = 0, 1
@@ -37,6 +37,14 @@ class SplitReduceDesc(ctypes.Structure):
     """rtsds_split_reduce_desc (include/rtsds_hip.h)."""
     _fields_ = [("slab", c_void_p), ("dw", c_void_p), ("slab_stride", c_long), ("nv", c_int), ("cv", c_int),
                 ("cp", c_int), ("splits", c_int), ("accumulate", c_int)]
+
+
+class BnParams(ctypes.Structure):
+    """rtsds_bn_params (include/rtsds_hip.h): one BatchNorm of rtsds_bn_pair_fwd / rtsds_bn_pair_bwd."""
+    _fields_ = [("gamma", c_void_p), ("beta", c_void_p), ("running_mean", c_void_p), ("running_var", c_void_p),
+                ("num_batches_tracked", c_void_p), ("save_mean", c_void_p), ("save_invstd", c_void_p),
+                ("momentum", c_float), ("eps", c_float), ("stats_part", c_void_p), ("stats_nrb", c_int),
+                ("accumulate", c_int), ("dgamma", c_void_p), ("dbeta", c_void_p)]
 
 
 P = c_void_p
@@ -87,6 +95,15 @@ SIGNATURES = {
                              P, c_size_t, P]),
     "rtsds_bn_bwd_ld": (c_int, [P, c_long, P, P, P, P, P, P, c_long, c_int, P, P, P, P, c_int, c_int, c_int, c_int,
                                 P, c_size_t, P]),
+    "rtsds_bn_bits_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "rtsds_bn_fwd_bits": (c_int, [P, P, P, P, c_long, c_int, P, P, P, P, P, P, P, c_float, c_float, P, c_int, c_int, P,
+                                  c_size_t, P]),
+    "rtsds_bn_bwd_bits": (c_int, [P, c_long, P, P, P, P, P, P, c_long, c_int, P, P, P, P, c_int, c_int, P, c_size_t, P]),
+    "rtsds_bn_pair_workspace": (c_size_t, [c_long, c_int]),
+    "rtsds_bn_pair_fwd": (c_int, [P, P, P, P, c_long, c_int, ctypes.POINTER(BnParams), ctypes.POINTER(BnParams), c_int, P,
+                                  c_size_t, P]),
+    "rtsds_bn_pair_bwd": (c_int, [P, c_long, P, P, P, P, P, c_long, c_int, ctypes.POINTER(BnParams),
+                                  ctypes.POINTER(BnParams), c_int, P, c_size_t, P]),
     "rtsds_bn_relu_maxpool_fwd": (c_int, [P, P, P] + [c_int] * 7 + [P, P, P, P, P, P, P, c_float, c_float, c_int, P,
                                                                    c_int, c_int, P, c_size_t, P]),
     "rtsds_bn_relu_maxpool_bwd": (c_int, [P, P, P, P, P, P] + [c_int] * 7 + [P, P, P, P, c_int, c_int, c_int, P,

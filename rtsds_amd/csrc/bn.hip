@@ -185,6 +185,23 @@ __global__ void __launch_bounds__(256) bn_finalize_kernel(const float* __restric
   float sc, sh;
   bn_finalize_body(part, nrb, c, rows, gamma, beta, rmean, rvar, smean, sinv, scale, shift, momentum, eps, nbt, wr, sc, sh);
 }
+// The forward finalizes of a residual block's two BatchNorms (bn2 / bn3 and the downsample's, on
+// tensors of one [rows][c] shape) in one launch: blockIdx.y picks the BatchNorm.
+struct BnFin {
+  const float* part;
+  int nrb;
+  const float *gamma, *beta;
+  float *rmean, *rvar, *smean, *sinv, *scale, *shift;
+  float momentum, eps;
+  long long* nbt;
+};
+__global__ void __launch_bounds__(256) bn_finalize_pair_kernel(BnFin fa, BnFin fb, int c, long rows) {
+  __shared__ float wr[4][3];
+  const BnFin f = blockIdx.y ? fb : fa;
+  float sc, sh;
+  bn_finalize_body(f.part, f.nrb, c, rows, f.gamma, f.beta, f.rmean, f.rvar, f.smean, f.sinv, f.scale, f.shift, f.momentum, f.eps,
+                   f.nbt, wr, sc, sh);
+}
 __global__ void bn_eval_coef_kernel(int c, const float* gamma, const float* beta, const float* rmean, const float* rvar,
                                     float* scale, float* shift, float* smean, float* sinv, float eps) {
   const int ch = blockIdx.x * blockDim.x + threadIdx.x;
@@ -295,6 +312,64 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const T* __restrict__ x, 
       v0[j] = act_f(a, act);
     }
     store_vec<T, VEC>(y + r * ldy + ch0, v0, cvalid);
+  }
+}
+
+// Pass 3 (forward) of a training-mode residual BatchNorm + ReLU that keeps mask bits instead of y
+// for its backward: bn_apply_kernel's y = relu(x * scale + shift + res) in its layout, and one byte
+// per channel vector, bits[r][ch0 / VEC] = bn_y_bits of the values stored (c % VEC == 0).
+// PAIR: res is the raw output of the block's downsample conv and scale2 / shift2 its BatchNorm's:
+// the residual is round(res * scale2 + shift2), the value bn_apply_kernel<T, VEC, 0> would have
+// stored as the skip tensor, which is never written.
+template <typename T, int VEC, bool PAIR>
+RT_DEV void bn_res_row(float* v, const float* rv, const float* sc, const float* sh, const float* sc2, const float* sh2) {
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    float r = rv[j];
+    if constexpr (PAIR) r = to_f(from_f<T>(fmaf(r, sc2[j], sh2[j])));
+    float a = fmaf(v[j], sc[j], sh[j]);
+    a += r;
+    v[j] = fmaxf(a, 0.f);
+  }
+}
+template <typename T, int VEC, bool PAIR>
+__global__ void __launch_bounds__(256) bn_apply_bits_kernel(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y,
+                                                             uint8_t* __restrict__ bits, const float* __restrict__ scale,
+                                                             const float* __restrict__ shift, const float* __restrict__ scale2,
+                                                             const float* __restrict__ shift2, long rows, int c) {
+  static_assert(VEC == VecT<T>::N, "whole 16-byte channel vectors");
+  const BnTile<VEC> t(c);
+  if (!t.active) return;
+  float sc[VEC], sh[VEC], sc2[PAIR ? VEC : 1], sh2[PAIR ? VEC : 1];
+  load_coef<VEC>(scale, t.ch0, c, sc);
+  load_coef<VEC>(shift, t.ch0, c, sh);
+  if constexpr (PAIR) {
+    load_coef<VEC>(scale2, t.ch0, c, sc2);
+    load_coef<VEC>(shift2, t.ch0, c, sh2);
+  }
+  const int ch0 = t.ch0, cvalid = t.cvalid;
+  const long step = t.step(), nv = c / VEC, bv = ch0 / VEC;
+  long r = t.row0();
+  for (; r + step < rows; r += 2 * step) {  // two independent rows in flight per thread, as bn_apply_kernel
+    float v0[VEC], v1[VEC], r0[VEC], r1[VEC];
+    load_vec<T, VEC>(x + r * c + ch0, v0, cvalid);
+    load_vec<T, VEC>(x + (r + step) * c + ch0, v1, cvalid);
+    load_vec<T, VEC>(res + r * c + ch0, r0, cvalid);
+    load_vec<T, VEC>(res + (r + step) * c + ch0, r1, cvalid);
+    bn_res_row<T, VEC, PAIR>(v0, r0, sc, sh, sc2, sh2);
+    bn_res_row<T, VEC, PAIR>(v1, r1, sc, sh, sc2, sh2);
+    store_vec<T, VEC>(y + r * c + ch0, v0, cvalid);
+    store_vec<T, VEC>(y + (r + step) * c + ch0, v1, cvalid);
+    bits[r * nv + bv] = (uint8_t)bn_y_bits<T, VEC>(v0);
+    bits[(r + step) * nv + bv] = (uint8_t)bn_y_bits<T, VEC>(v1);
+  }
+  if (r < rows) {
+    float v0[VEC], r0[VEC];
+    load_vec<T, VEC>(x + r * c + ch0, v0, cvalid);
+    load_vec<T, VEC>(res + r * c + ch0, r0, cvalid);
+    bn_res_row<T, VEC, PAIR>(v0, r0, sc, sh, sc2, sh2);
+    store_vec<T, VEC>(y + r * c + ch0, v0, cvalid);
+    bits[r * nv + bv] = (uint8_t)bn_y_bits<T, VEC>(v0);
   }
 }
 
@@ -409,15 +484,22 @@ RT_DEV void bn_bwd_coef(int ch0, int c, const float* gamma, const float* beta, c
 // thread (loads issued before any use).  gout (HAS_Y, may be null): g is also stored.  g_last /
 // xv_last (may be null): receive the last iteration's masked g and its x (rows past the end:
 // g = 0), for a caller that applies from registers.
+// YBITS (HAS_Y): the mask comes from ybits ([rows][c / VEC] bytes, bn_y_bits) instead of y.
+// PAIR: the same g also feeds a second BatchNorm on x2 (the downsample BatchNorm of a residual
+// block, whose incoming gradient is g): sgx2 += g * (x2 - mu2), in the same row order (its sum of
+// g is sg).
 constexpr int kBnU = 2;
-template <typename T, int VEC, bool HAS_Y, class GS>
+template <typename T, int VEC, bool HAS_Y, class GS, bool YBITS = false, bool PAIR = false>
 RT_DEV void bn_bwd_sums(const GS& gs, const T* __restrict__ x, const T* __restrict__ y, T* __restrict__ gout, long r0,
                         long step, long rows, int c, const BnTile<VEC>& t, const BnDx<VEC>& k, int act, float* sg,
-                        float* sgx, float (*g_last)[VEC], float (*xv_last)[VEC]) {
+                        float* sgx, float (*g_last)[VEC], float (*xv_last)[VEC], const uint8_t* __restrict__ ybits = nullptr,
+                        const T* __restrict__ x2 = nullptr, const float* mu2 = nullptr, float* sgx2 = nullptr) {
+  static_assert(HAS_Y || !YBITS, "mask bits stand in for y");
   const int ch0 = t.ch0;
   for (long r = r0; r < rows; r += kBnU * step) {
     // (loop-local: arrays owned by the caller cost bn_bwd_stats_kernel registers)
-    float g[kBnU][VEC], xv[kBnU][VEC], yv[HAS_Y ? kBnU : 1][VEC];
+    float g[kBnU][VEC], xv[kBnU][VEC], yv[HAS_Y ? kBnU : 1][VEC], x2v[PAIR ? kBnU : 1][VEC];
+    unsigned yb[YBITS ? kBnU : 1];
 #pragma unroll
     for (int u = 0; u < kBnU; ++u) {
       // clamped, unconditional loads (all rows in flight together); rows past the end
@@ -425,7 +507,9 @@ RT_DEV void bn_bwd_sums(const GS& gs, const T* __restrict__ x, const T* __restri
       const long rr = min(r + u * step, rows - 1);
       gs.template load<VEC>(rr, ch0, g[u], t.cvalid);
       load_vec<T, VEC>(x + rr * c + ch0, xv[u], t.cvalid);
-      if constexpr (HAS_Y) load_vec<T, VEC>(y + rr * c + ch0, yv[u], t.cvalid);
+      if constexpr (YBITS) yb[u] = ybits[rr * (c / VEC) + ch0 / VEC];
+      else if constexpr (HAS_Y) load_vec<T, VEC>(y + rr * c + ch0, yv[u], t.cvalid);
+      if constexpr (PAIR) load_vec<T, VEC>(x2 + rr * c + ch0, x2v[u], t.cvalid);
     }
 #pragma unroll
     for (int u = 0; u < kBnU; ++u)
@@ -435,12 +519,14 @@ RT_DEV void bn_bwd_sums(const GS& gs, const T* __restrict__ x, const T* __restri
       }
 #pragma unroll
     for (int u = 0; u < kBnU; ++u) {
+      if constexpr (YBITS) bn_bits_y<VEC>(yb[u], yv[u]);
       bn_mask<VEC, HAS_Y>(g[u], yv[HAS_Y ? u : 0], xv[u], k.sc, k.sh, act);
       if (HAS_Y && gout && r + u * step < rows) store_vec<T, VEC>(gout + (r + u * step) * c + ch0, g[u], t.cvalid);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         sg[j] += g[u][j];
         sgx[j] = fmaf(g[u][j], xv[u][j] - k.mu[j], sgx[j]);
+        if constexpr (PAIR) sgx2[j] = fmaf(g[u][j], x2v[u][j] - mu2[j], sgx2[j]);
         if (g_last) { g_last[u][j] = g[u][j]; xv_last[u][j] = xv[u][j]; }
       }
     }
@@ -582,6 +668,55 @@ __global__ void __launch_bounds__(256) bn_bwd_stats_kernel(const GS gs, const T*
     if (t.ch0 + j < c) *(float2*)(part + ((long)blockIdx.x * c + t.ch0 + j) * 2) = make_float2(sg[j], sgx[j]);
 }
 
+// bn_bwd_stats_kernel<T, VEC, true, GS, RTSDS_ACT_RELU> with the mask read from the forward's bits
+// (bn_apply_bits_kernel) instead of y: the same g, gout store and partials from one byte per
+// channel vector in place of a 16-byte read.
+// PAIR: g is also the incoming gradient of the block's downsample BatchNorm (no activation) on x2:
+// part2 receives the partials bn_bwd_stats_kernel<T, VEC, false, GradDirect<T>, 0> forms from the
+// stored g -- the same sum of g, and sum g * (x2 - mean2) in the same order.  g is exactly dy or
+// dy * 0, so the pair's apply pass re-forms it from dy and the bits and gout is not needed.
+template <typename T, int VEC, class GS, bool PAIR>
+__global__ void __launch_bounds__(256) bn_bwd_stats_bits_kernel(const GS gs, const T* __restrict__ x,
+                                                                 const uint8_t* __restrict__ bits, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, const float* __restrict__ mean,
+                                                                 const float* __restrict__ sinv, float* __restrict__ part,
+                                                                 long rows, int c, T* __restrict__ gout,
+                                                                 const T* __restrict__ x2, const float* __restrict__ mean2,
+                                                                 float* __restrict__ part2) {
+  __shared__ float red[2][256][VEC];
+  const BnTile<VEC> t(c);
+  BnDx<VEC> k;
+  float sg[VEC], sgx[VEC], sg2[PAIR ? VEC : 1], sgx2[PAIR ? VEC : 1], mu2[PAIR ? VEC : 1];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) { sg[j] = 0.f; sgx[j] = 0.f; }
+  if constexpr (PAIR) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) { sgx2[j] = 0.f; mu2[j] = mean2[min(t.ch0 + j, c - 1)]; }
+  }
+  if (t.active) {
+    bn_bwd_coef<VEC>(t.ch0, c, gamma, beta, mean, sinv, k);
+    bn_bwd_sums<T, VEC, true, GS, true, PAIR>(gs, x, (const T*)nullptr, gout, t.row0(), t.step(), rows, c, t, k, RTSDS_ACT_RELU, sg,
+                                              sgx, nullptr, nullptr, bits, x2, mu2, sgx2);
+  }
+  if constexpr (PAIR) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) sg2[j] = sg[j];
+  }
+  const bool owner = bn_bwd_block_sum<VEC>(t, red, sg, sgx);
+  if (owner) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+      if (t.ch0 + j < c) *(float2*)(part + ((long)blockIdx.x * c + t.ch0 + j) * 2) = make_float2(sg[j], sgx[j]);
+  }
+  if constexpr (PAIR) {
+    __syncthreads();  // red is reused
+    if (!bn_bwd_block_sum<VEC>(t, red, sg2, sgx2)) return;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+      if (t.ch0 + j < c) *(float2*)(part2 + ((long)blockIdx.x * c + t.ch0 + j) * 2) = make_float2(sg2[j], sgx2[j]);
+  }
+}
+
 // All three backward passes in one launch when the statistics pass has a single row block
 // (bn_bwd_rb == 1: the attention modules' BatchNorms on [N, C] pooled rows): the same statistics
 // loop and reduction as bn_bwd_stats_kernel (grid (1, channel blocks)), the finalize of a single
@@ -681,11 +816,9 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const float* __res
 // block, lane q (0..15) of a channel sums row blocks q, q + 16, ... (8 in flight, 128-B rows of
 // 16 channels per load group), the 16 lane sums added in a fixed tree order; coefficients as
 // bn_bwd_finalize_kernel.
-__global__ void __launch_bounds__(256) bn_bwd_finalize_rb_kernel(const float* __restrict__ part, int nrb, int c, long rows,
-                                                                  const float* gamma, const float* beta, const float* smean,
-                                                                  const float* sinv, float* dgamma, float* dbeta, float* coef,
-                                                                  int training, int accumulate) {
-  __shared__ float wr[16][16][2];
+RT_DEV void bn_bwd_finalize_rb_body(const float* __restrict__ part, int nrb, int c, long rows, const float* gamma,
+                                    const float* beta, const float* smean, const float* sinv, float* dgamma, float* dbeta,
+                                    float* coef, int training, int accumulate, float (*wr)[16][2]) {
   const int cl = threadIdx.x & 15, q = threadIdx.x >> 4, ch = blockIdx.x * 16 + cl;
   const int chc = min(ch, c - 1);
   BnBwdOps ops;
@@ -714,6 +847,26 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_rb_kernel(const float* __
   sg = (t0[0] + t0[1]) + (t0[2] + t0[3]);
   sgx = (t1[0] + t1[1]) + (t1[2] + t1[3]);
   bn_bwd_coef_rows(ops, sg, sgx, ch, c, rows, training, accumulate, dgamma, dbeta, coef);
+}
+__global__ void __launch_bounds__(256) bn_bwd_finalize_rb_kernel(const float* __restrict__ part, int nrb, int c, long rows,
+                                                                  const float* gamma, const float* beta, const float* smean,
+                                                                  const float* sinv, float* dgamma, float* dbeta, float* coef,
+                                                                  int training, int accumulate) {
+  __shared__ float wr[16][16][2];
+  bn_bwd_finalize_rb_body(part, nrb, c, rows, gamma, beta, smean, sinv, dgamma, dbeta, coef, training, accumulate, wr);
+}
+// The backward finalizes of a residual block's two BatchNorms (bn_bwd_stats_bits_kernel<PAIR>'s two
+// partial sets) in one launch: blockIdx.y picks the BatchNorm, each runs bn_bwd_finalize_rb_kernel's
+// body (training mode).
+struct BnBwdFin {
+  const float *part, *gamma, *beta, *smean, *sinv;
+  float *dgamma, *dbeta, *coef;
+  int accumulate;
+};
+__global__ void __launch_bounds__(256) bn_bwd_finalize_pair_kernel(BnBwdFin fa, BnBwdFin fb, int nrb, int c, long rows) {
+  __shared__ float wr[16][16][2];
+  const BnBwdFin f = blockIdx.y ? fb : fa;
+  bn_bwd_finalize_rb_body(f.part, nrb, c, rows, f.gamma, f.beta, f.smean, f.sinv, f.dgamma, f.dbeta, f.coef, 1, f.accumulate, wr);
 }
 
 // Backward pass 3: dx = A*g + B*(x - mean) + C;  dres = g.  Layout as bn_apply_kernel.
@@ -763,6 +916,69 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const GS gs, const T*
     }
   }
   if (r < rows) bn_bwd_row<T, VEC>(gs, x, y, dx, dres, r, c, t, k, act);
+}
+
+// Backward pass 3 of a residual block's two BatchNorms: g = dy * relu'(y) re-formed from dy and
+// the mask bits (the value the separate passes store and read back), then dxa = A*g + B*(xa - mean)
+// + C with bn2's coefficients and dxb likewise with the downsample BatchNorm's -- the two
+// bn_bwd_apply_kernel<T, VEC, GradDirect<T>, 0> launches from one read of g.
+template <typename T, int VEC>
+RT_DEV void bn_bwd_pair_row(T* __restrict__ dxa, T* __restrict__ dxb, long off, const BnDx<VEC>& ka, const BnDx<VEC>& kb,
+                            int cvalid, unsigned yb, float* g, float* xa, float* xb) {
+  float yv[VEC];
+  bn_bits_y<VEC>(yb, yv);
+  bn_mask<VEC, true>(g, yv, xa, ka.sc, ka.sh, RTSDS_ACT_RELU);
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    xa[j] = bn_bwd_dx<VEC>(ka, j, g[j], xa[j]);
+    xb[j] = bn_bwd_dx<VEC>(kb, j, g[j], xb[j]);
+  }
+  store_vec<T, VEC>(dxa + off, xa, cvalid);
+  store_vec<T, VEC>(dxb + off, xb, cvalid);
+}
+template <int VEC>
+RT_DEV void bn_bwd_load_abk(const float* __restrict__ coef, int ch0, int c, BnDx<VEC>& k) {
+  load_coef<VEC>(coef, ch0, c, k.a);
+  load_coef<VEC>(coef + c, ch0, c, k.b);
+  load_coef<VEC>(coef + 2 * c, ch0, c, k.k);
+  load_coef<VEC>(coef + 3 * c, ch0, c, k.mu);
+}
+template <typename T, int VEC, class GS>
+__global__ void __launch_bounds__(256) bn_bwd_apply_pair_kernel(const GS gs, const uint8_t* __restrict__ bits,
+                                                                 const T* __restrict__ xa, const T* __restrict__ xb,
+                                                                 T* __restrict__ dxa, T* __restrict__ dxb,
+                                                                 const float* __restrict__ coefa, const float* __restrict__ coefb,
+                                                                 long rows, int c) {
+  const BnTile<VEC> t(c);
+  if (!t.active) return;
+  BnDx<VEC> ka, kb;
+  bn_bwd_load_abk<VEC>(coefa, t.ch0, c, ka);
+  bn_bwd_load_abk<VEC>(coefb, t.ch0, c, kb);
+  const int ch0 = t.ch0, cvalid = t.cvalid;
+  const long step = t.step(), nv = c / VEC, bv = ch0 / VEC;
+  long r = t.row0();
+  for (; r + step < rows; r += 2 * step) {  // two independent rows in flight per thread
+    const long o0 = r * c + ch0, o1 = o0 + step * c;
+    float g0[VEC], a0[VEC], b0[VEC], g1[VEC], a1[VEC], b1[VEC];
+    gs.template load<VEC>(r, ch0, g0, cvalid);
+    load_vec<T, VEC>(xa + o0, a0, cvalid);
+    load_vec<T, VEC>(xb + o0, b0, cvalid);
+    const unsigned y0 = bits[r * nv + bv];
+    gs.template load<VEC>(r + step, ch0, g1, cvalid);
+    load_vec<T, VEC>(xa + o1, a1, cvalid);
+    load_vec<T, VEC>(xb + o1, b1, cvalid);
+    const unsigned y1 = bits[(r + step) * nv + bv];
+    bn_bwd_pair_row<T, VEC>(dxa, dxb, o0, ka, kb, cvalid, y0, g0, a0, b0);
+    bn_bwd_pair_row<T, VEC>(dxa, dxb, o1, ka, kb, cvalid, y1, g1, a1, b1);
+  }
+  if (r < rows) {
+    const long o0 = r * c + ch0;
+    float g0[VEC], a0[VEC], b0[VEC];
+    gs.template load<VEC>(r, ch0, g0, cvalid);
+    load_vec<T, VEC>(xa + o0, a0, cvalid);
+    load_vec<T, VEC>(xb + o0, b0, cvalid);
+    bn_bwd_pair_row<T, VEC>(dxa, dxb, o0, ka, kb, cvalid, bits[r * nv + bv], g0, a0, b0);
+  }
 }
 
 // ------------------------------------------------------------------ host
@@ -876,6 +1092,15 @@ struct BnArgs {
 // statistics pass (unless a conv epilogue produced the partials), then the finalize; eval: from the
 // running statistics.  apply_too (training, few rows): the finalize's block also applies, and
 // nothing is left to launch.
+// The training forward's partial statistics: the conv epilogue's, else our own pass's (rb of them per channel)
+template <typename T, int VEC>
+static const float* bn_fwd_stats(const BnArgs& a, int& rb) {
+  rb = a.pre_nrb;
+  if (a.pre) return a.pre;
+  rb = bn_rb<VEC>(a.rows, a.c);
+  hipLaunchKernelGGL((bn_stats_kernel<T, VEC>), bn_grid<VEC>(rb, a.c), dim3(256), 0, a.st, (const T*)a.x, a.w.part, a.rows, a.c);
+  return a.w.part;
+}
 template <typename T, int VEC>
 static void bn_fwd_coefs(const BnArgs& a, bool apply_too = false) {
   const int c = a.c;
@@ -885,13 +1110,8 @@ static void bn_fwd_coefs(const BnArgs& a, bool apply_too = false) {
                        shift, a.smean, a.sinv, a.eps);
     return;
   }
-  int rb = a.pre_nrb;
-  const float* part = a.pre;
-  if (!part) {
-    rb = bn_rb<VEC>(a.rows, c);
-    hipLaunchKernelGGL((bn_stats_kernel<T, VEC>), bn_grid<VEC>(rb, c), dim3(256), 0, a.st, (const T*)a.x, a.w.part, a.rows, c);
-    part = a.w.part;
-  }
+  int rb;
+  const float* part = bn_fwd_stats<T, VEC>(a, rb);
   if (apply_too)
     hipLaunchKernelGGL(bn_finalize_apply_kernel<T>, dim3(c), dim3(256), 0, a.st, part, rb, c, a.rows, a.gamma, a.beta, a.rmean,
                        a.rvar, a.smean, a.sinv, scale, shift, a.momentum, a.eps, a.nbt, (const T*)a.x, (const T*)a.res, (T*)a.y,
@@ -1064,6 +1284,145 @@ extern "C" int rtsds_bn_bwd(const void* dy, const void* x, const void* y, void* 
                             size_t ws_bytes, void* stream) {
   return rtsds_bn_bwd_ld(dy, c, x, y, dx, dres, dgamma, dbeta, rows, c, gamma, beta, save_mean, save_invstd, training, act,
                          accumulate_params, dtype, ws, ws_bytes, stream);
+}
+
+// ---- Training-mode residual BatchNorm + ReLU that keeps mask bits instead of y, and the pair of a
+// residual block's last BatchNorm (A) with its downsample BatchNorm (B) on tensors of one shape.
+// Every launch below computes what the separate calls above compute, bit for bit.
+static bool bn_bits_ok(long rows, int c, int dtype) {
+  return rows > 0 && c > 0 && c % 8 == 0 && c <= 65535 * 256 && (dtype == RTSDS_BF16 || dtype == RTSDS_F32);
+}
+extern "C" size_t rtsds_bn_bits_bytes(long rows, int c, int dtype) {
+  if (!bn_bits_ok(rows, c, dtype)) return 0;
+  return (size_t)rows * (c / (dtype == RTSDS_BF16 ? 8 : 4));
+}
+extern "C" size_t rtsds_bn_pair_workspace(long rows, int c) { return 2 * rtsds_bn_workspace(rows, c); }
+// f(BnKind<T, VEC>) with VEC the 16-byte vector of the storage type (c % 8 == 0: always whole)
+template <typename F>
+static int bn_bits_dispatch(int dtype, F f) {
+  if (dtype == RTSDS_BF16) f(BnKind<bf16, 8>());
+  else if (dtype == RTSDS_F32) f(BnKind<float, 4>());
+  else return RTSDS_ERR_UNSUPPORTED;
+  return RTSDS_OK;
+}
+
+static int bn_params_fwd(BnArgs& a, const rtsds_bn_params* p) {
+  return bn_fwd_args(a, p->gamma, p->beta, p->running_mean, p->running_var, p->num_batches_tracked, p->save_mean, p->save_invstd,
+                     p->momentum, p->eps, 1, p->stats_part, p->stats_nrb);
+}
+template <typename T, int VEC>
+static void bn_bits_fwd_launch(const BnArgs& a, const BnArgs* b, uint8_t* bits) {
+  const int c = a.c;
+  const dim3 grid = bn_grid<VEC>(bn_apply_rb<VEC>(a.rows, c), c);
+  if (!b) {
+    bn_fwd_coefs<T, VEC>(a);
+    hipLaunchKernelGGL((bn_apply_bits_kernel<T, VEC, false>), grid, dim3(256), 0, a.st, (const T*)a.x, (const T*)a.res, (T*)a.y, bits,
+                       a.w.coef, a.w.coef + c, (const float*)nullptr, (const float*)nullptr, a.rows, c);
+    return;
+  }
+  BnFin f[2];
+  const BnArgs* ab[2] = {&a, b};
+  for (int i = 0; i < 2; ++i) {
+    const BnArgs& q = *ab[i];
+    int rb;
+    const float* part = bn_fwd_stats<T, VEC>(q, rb);
+    f[i] = BnFin{part, rb, q.gamma, q.beta, q.rmean, q.rvar, q.smean, q.sinv, q.w.coef, q.w.coef + c, q.momentum, q.eps, q.nbt};
+  }
+  hipLaunchKernelGGL(bn_finalize_pair_kernel, dim3(c, 2), dim3(256), 0, a.st, f[0], f[1], c, a.rows);
+  hipLaunchKernelGGL((bn_apply_bits_kernel<T, VEC, true>), grid, dim3(256), 0, a.st, (const T*)a.x, (const T*)b->x, (T*)a.y, bits,
+                     a.w.coef, a.w.coef + c, b->w.coef, b->w.coef + c, a.rows, c);
+}
+template <typename T, int VEC>
+static void bn_bits_bwd_launch(const BnArgs& a, const BnArgs* b, const uint8_t* bits) {
+  const T* x = (const T*)a.x;
+  const long rows = a.rows;
+  const int c = a.c;
+  const GradDirect<T> gs{(const T*)a.dy, (int)(a.ldy ? a.ldy : c)};
+  const int rb = bn_bwd_rb<VEC>(rows, c);
+  const dim3 sgrid = bn_grid<VEC>(rb, c), agrid = bn_grid<VEC>(bn_apply_rb<VEC>(rows, c), c);
+  if (!b) {
+    // as bn_bwd_launch's g_out route: the statistics pass stores g as dres, the apply reads g and x
+    hipLaunchKernelGGL((bn_bwd_stats_bits_kernel<T, VEC, GradDirect<T>, false>), sgrid, dim3(256), 0, a.st, gs, x, bits, a.gamma,
+                       a.beta, a.smean, a.sinv, a.w.part, rows, c, (T*)a.dres, (const T*)nullptr, (const float*)nullptr,
+                       (float*)nullptr);
+    hipLaunchKernelGGL(bn_bwd_finalize_rb_kernel, dim3(rt_cdiv(c, 16)), dim3(256), 0, a.st, a.w.part, rb, c, rows, a.gamma, a.beta,
+                       a.smean, a.sinv, a.dgamma, a.dbeta, a.w.coef, 1, a.accumulate);
+    const GradDirect<T> gg{(const T*)a.dres, c};
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, VEC, GradDirect<T>, RTSDS_ACT_NONE>), agrid, dim3(256), 0, a.st, gg, x,
+                       (const T*)nullptr, (T*)a.dx, (T*)nullptr, a.w.coef, rows, c, 0);
+    return;
+  }
+  hipLaunchKernelGGL((bn_bwd_stats_bits_kernel<T, VEC, GradDirect<T>, true>), sgrid, dim3(256), 0, a.st, gs, x, bits, a.gamma, a.beta,
+                     a.smean, a.sinv, a.w.part, rows, c, (T*)nullptr, (const T*)b->x, b->smean, b->w.part);
+  const BnBwdFin fa{a.w.part, a.gamma, a.beta, a.smean, a.sinv, a.dgamma, a.dbeta, a.w.coef, a.accumulate};
+  const BnBwdFin fb{b->w.part, b->gamma, b->beta, b->smean, b->sinv, b->dgamma, b->dbeta, b->w.coef, b->accumulate};
+  hipLaunchKernelGGL(bn_bwd_finalize_pair_kernel, dim3(rt_cdiv(c, 16), 2), dim3(256), 0, a.st, fa, fb, rb, c, rows);
+  hipLaunchKernelGGL((bn_bwd_apply_pair_kernel<T, VEC, GradDirect<T>>), agrid, dim3(256), 0, a.st, gs, bits, x, (const T*)b->x,
+                     (T*)a.dx, (T*)b->dx, a.w.coef, b->w.coef, rows, c);
+}
+
+extern "C" int rtsds_bn_fwd_bits(const void* x, const void* res, void* y, uint8_t* bits, long rows, int c, const float* gamma,
+                                 const float* beta, float* running_mean, float* running_var, long long* num_batches_tracked,
+                                 float* save_mean, float* save_invstd, float momentum, float eps, const float* stats_part,
+                                 int stats_nrb, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  if (rows <= 0 || c <= 0 || !x || !res || !y || !bits) return RTSDS_ERR_SHAPE;
+  if (!bn_bits_ok(rows, c, dtype)) return RTSDS_ERR_UNSUPPORTED;
+  if (ws_bytes < rtsds_bn_workspace(rows, c)) return RTSDS_ERR_WORKSPACE;
+  BnArgs a(rows, c, ws, stream);
+  if (int rc = bn_fwd_args(a, gamma, beta, running_mean, running_var, num_batches_tracked, save_mean, save_invstd, momentum, eps, 1,
+                           stats_part, stats_nrb))
+    return rc;
+  a.x = x, a.res = res, a.y = y, a.ldy = c, a.act = RTSDS_ACT_RELU;
+  if (int rc = bn_bits_dispatch(dtype, [&](auto k) { bn_bits_fwd_launch<typename decltype(k)::T, decltype(k)::VEC>(a, nullptr, bits); }))
+    return rc;
+  RET_LAUNCH();
+}
+extern "C" int rtsds_bn_bwd_bits(const void* dy, long ldy, const void* x, const uint8_t* bits, void* dx, void* dres, float* dgamma,
+                                 float* dbeta, long rows, int c, const float* gamma, const float* beta, const float* save_mean,
+                                 const float* save_invstd, int accumulate_params, int dtype, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  if (rows <= 0 || c <= 0 || ldy < c || ldy > (1L << 30) || !dy || !x || !bits || !dx || !dres) return RTSDS_ERR_SHAPE;
+  if (!bn_bits_ok(rows, c, dtype)) return RTSDS_ERR_UNSUPPORTED;
+  if (ldy != c && !(dtype == RTSDS_BF16 && ldy % 8 == 0)) return RTSDS_ERR_UNSUPPORTED;
+  if (ws_bytes < rtsds_bn_workspace(rows, c)) return RTSDS_ERR_WORKSPACE;
+  BnArgs a(rows, c, ws, stream);
+  bn_bwd_args(a, x, dx, dgamma, dbeta, gamma, beta, save_mean, save_invstd, 1, RTSDS_ACT_RELU, accumulate_params);
+  a.dy = dy, a.ldy = ldy, a.dres = dres;
+  if (int rc = bn_bits_dispatch(dtype, [&](auto k) { bn_bits_bwd_launch<typename decltype(k)::T, decltype(k)::VEC>(a, nullptr, bits); }))
+    return rc;
+  RET_LAUNCH();
+}
+extern "C" int rtsds_bn_pair_fwd(const void* xa, const void* xb, void* y, uint8_t* bits, long rows, int c,
+                                 const rtsds_bn_params* pa, const rtsds_bn_params* pb, int dtype, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  if (rows <= 0 || c <= 0 || !xa || !xb || !y || !bits || !pa || !pb) return RTSDS_ERR_SHAPE;
+  if (!bn_bits_ok(rows, c, dtype)) return RTSDS_ERR_UNSUPPORTED;
+  if (ws_bytes < rtsds_bn_pair_workspace(rows, c)) return RTSDS_ERR_WORKSPACE;
+  BnArgs a(rows, c, ws, stream), b(rows, c, (char*)ws + rtsds_bn_workspace(rows, c), stream);
+  if (int rc = bn_params_fwd(a, pa)) return rc;
+  if (int rc = bn_params_fwd(b, pb)) return rc;
+  a.x = xa, a.y = y, a.ldy = c, a.act = RTSDS_ACT_RELU, b.x = xb;
+  if (int rc = bn_bits_dispatch(dtype, [&](auto k) { bn_bits_fwd_launch<typename decltype(k)::T, decltype(k)::VEC>(a, &b, bits); }))
+    return rc;
+  RET_LAUNCH();
+}
+extern "C" int rtsds_bn_pair_bwd(const void* dy, long ldy, const void* xa, const void* xb, const uint8_t* bits, void* dxa, void* dxb,
+                                 long rows, int c, const rtsds_bn_params* pa, const rtsds_bn_params* pb, int dtype, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  if (rows <= 0 || c <= 0 || ldy < c || ldy > (1L << 30) || !dy || !xa || !xb || !bits || !dxa || !dxb || !pa || !pb)
+    return RTSDS_ERR_SHAPE;
+  if (!bn_bits_ok(rows, c, dtype)) return RTSDS_ERR_UNSUPPORTED;
+  if (ldy != c && !(dtype == RTSDS_BF16 && ldy % 8 == 0)) return RTSDS_ERR_UNSUPPORTED;
+  if (ws_bytes < rtsds_bn_pair_workspace(rows, c)) return RTSDS_ERR_WORKSPACE;
+  BnArgs a(rows, c, ws, stream), b(rows, c, (char*)ws + rtsds_bn_workspace(rows, c), stream);
+  bn_bwd_args(a, xa, dxa, pa->dgamma, pa->dbeta, pa->gamma, pa->beta, pa->save_mean, pa->save_invstd, 1, RTSDS_ACT_RELU,
+              pa->accumulate);
+  bn_bwd_args(b, xb, dxb, pb->dgamma, pb->dbeta, pb->gamma, pb->beta, pb->save_mean, pb->save_invstd, 1, RTSDS_ACT_NONE,
+              pb->accumulate);
+  a.dy = dy, a.ldy = ldy;
+  if (int rc = bn_bits_dispatch(dtype, [&](auto k) { bn_bits_bwd_launch<typename decltype(k)::T, decltype(k)::VEC>(a, &b, bits); }))
+    return rc;
+  RET_LAUNCH();
 }
 
 // Training-mode BatchNorm + activation of an [n][hw][c] feature whose global average pool is wanted

@@ -51,6 +51,24 @@ RT_DEV void bn_mask(float* g, const float* yv, const float* xv, const float* sc,
   }
 }
 
+// The ReLU mask of a residual BatchNorm kept as bits: one byte per channel vector, bit j =
+// y[ch0 + j] > 0 of the value as stored (rounded to T; +0, -0 and NaN give 0, as act_grad does
+// from y).  bn_bits_y turns a byte back into stand-ins for y (1 or 0) that bn_mask<VEC, true> maps
+// to the same factors 1 / 0 as the stored y.
+template <typename T, int VEC>
+RT_DEV unsigned bn_y_bits(const float* v) {
+  static_assert(VEC <= 8, "one byte per channel vector");
+  unsigned b = 0;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) b |= (to_f(from_f<T>(v[j])) > 0.f ? 1u : 0u) << j;
+  return b;
+}
+template <int VEC>
+RT_DEV void bn_bits_y(unsigned b, float* yv) {
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) yv[j] = (b >> j) & 1u ? 1.f : 0.f;
+}
+
 // A thread's per-channel backward coefficients: dx = a*g + b*(x - mu) + k, and the forward's
 // sc / sh for the mask recomputed from x.
 template <int VEC> struct BnDx {

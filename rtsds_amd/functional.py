@@ -10,7 +10,8 @@ import ctypes
 import numpy as np
 import torch
 
-from ._lib import ACT_RELU, ACT_SIGMOID, INPUT_PADDED, UPCE_SET_CORRECT, WEIGHT_PACKED, ConvDesc, SplitReduceDesc, lib
+from ._lib import (ACT_RELU, ACT_SIGMOID, INPUT_PADDED, UPCE_SET_CORRECT, WEIGHT_PACKED, BnParams, ConvDesc,
+                   SplitReduceDesc, lib)
 from .runtime import (CL, bump_params_epoch, collective, dcode, dp_world, empty_nhwc, nhwc, params_epoch,
                       register_fold, require_hip, side_enabled, side_fork, stream, workspace)
 
@@ -72,8 +73,12 @@ def _sinks(*params):
 def _bn_param_grads(ctx, c, device):
     """(dgamma, dbeta, accumulate) of a BatchNorm backward: the parameters' sinks (accumulate = 1, the
     Function then returns None for both), else fresh fp32 [c] tensors for the gradients wanted."""
-    need_g, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-    sinks = _sinks(ctx.gamma if need_g else None, ctx.beta if need_b else None) if (need_g or need_b) else None
+    return _bn_grads_of(ctx.gamma, ctx.beta, ctx.needs_input_grad[1], ctx.needs_input_grad[2], c, device)
+
+
+def _bn_grads_of(gamma, beta, need_g, need_b, c, device):
+    """_bn_param_grads for the parameters given."""
+    sinks = _sinks(gamma if need_g else None, beta if need_b else None) if (need_g or need_b) else None
     if sinks is not None:
         return sinks[0], sinks[1], 1
     dg = torch.empty(c, dtype=torch.float32, device=device) if need_g else None
@@ -643,6 +648,23 @@ def _bn_bwd_coef(ctx_link, dy, x, dg, db, rows, c, gamma, beta, sm, si, training
     ctx_link.bn = (x, coef, act)
 
 
+# True: the two BatchNorms that end a residual block with a downsample branch run as one
+# BatchNormPairFn (nn.res_block_tail); False: as two BatchNormFns (A/B tests)
+RES_BN_PAIR = True
+# True: every other training-mode residual BatchNorm + ReLU keeps mask bits for its backward instead
+# of its output (rtsds_bn_fwd_bits / rtsds_bn_bwd_bits).  Off: on its own it measured no faster than
+# keeping y.
+RES_BN_BITS = False
+
+
+def _res_bits_ok(x, res, training, act):
+    """Whether a BatchNorm on NHWC ``x`` with residual ``res`` can keep mask bits instead of its output
+    (rtsds_bn_fwd_bits, rtsds_bn_pair_fwd): training mode, ReLU, bf16 / fp32, whole 16-byte channel
+    vectors, one shape."""
+    return (training and res is not None and act == ACT_RELU and x.shape[1] % 8 == 0
+            and x.dtype in (torch.bfloat16, torch.float32) and res.dtype == x.dtype and res.shape == x.shape)
+
+
 class BatchNormFn(torch.autograd.Function):
     """BatchNorm2d (+ residual add) (+ ReLU/LeakyReLU) fused, train or eval statistics."""
 
@@ -668,16 +690,28 @@ class BatchNormFn(torch.autograd.Function):
         sm = torch.empty(c, dtype=torch.float32, device=x.device)
         si = torch.empty(c, dtype=torch.float32, device=x.device)
         ws = workspace(lib.rtsds_bn_workspace(rows, c), x.device)
-        lib.rtsds_bn_fwd_ld(_P(x), _P(res), _P(y), ld, rows, c, _P(gamma), _P(beta), _P(running_mean),
-                            _P(running_var), _P(nbt), _P(sm), _P(si), float(momentum), float(eps), int(training),
-                            act, _P(stats) if training else None, int(stats_nrb or 0), dcode(x), _P(ws),
-                            ws.numel(), stream())
+        # A residual BatchNorm + ReLU whose backward wants both gradients keeps one mask bit per
+        # element instead of y (the backward statistics pass then reads a byte per channel vector
+        # in place of the y vector; same bits everywhere).
+        bits = None
+        if RES_BN_BITS and _res_bits_ok(x, res, training, act) and ctx.needs_input_grad[0] \
+                and ctx.needs_input_grad[3]:
+            bits = torch.empty(lib.rtsds_bn_bits_bytes(rows, c, dcode(x)), dtype=torch.uint8, device=x.device)
+            lib.rtsds_bn_fwd_bits(_P(x), _P(res), _P(y), _P(bits), rows, c, _P(gamma), _P(beta), _P(running_mean),
+                                  _P(running_var), _P(nbt), _P(sm), _P(si), float(momentum), float(eps), _P(stats),
+                                  int(stats_nrb or 0), dcode(x), _P(ws), ws.numel(), stream())
+        else:
+            lib.rtsds_bn_fwd_ld(_P(x), _P(res), _P(y), ld, rows, c, _P(gamma), _P(beta), _P(running_mean),
+                                _P(running_var), _P(nbt), _P(sm), _P(si), float(momentum), float(eps), int(training),
+                                act, _P(stats) if training else None, int(stats_nrb or 0), dcode(x), _P(ws),
+                                ws.numel(), stream())
         ctx.meta = (rows, c, int(training), act, res is not None)
         ctx.gamma, ctx.beta = gamma, beta
         ctx.res_join = res_join
+        ctx.has_bits = bits is not None
         # Without a residual the ReLU/LeakyReLU mask is recomputed from x in the backward
         # (bit-identical pre-activation), so y is neither kept nor re-read.
-        ctx.save_for_backward(x, y if keep_y else None, gamma, beta, sm, si)
+        ctx.save_for_backward(x, bits if bits is not None else (y if keep_y else None), gamma, beta, sm, si)
         ctx.link = None
         if link is not None and BN_BWD_LINK and training and res is None and act in (0, 1, 2) \
                 and x.dtype == torch.bfloat16 and c % 8 == 0:
@@ -707,7 +741,10 @@ class BatchNormFn(torch.autograd.Function):
         dg, db, acc = _bn_param_grads(ctx, c, x.device)
         ws = workspace(lib.rtsds_bn_workspace(rows, c), x.device)
         link = ctx.link
-        if link is not None and link.part is not None and dy.dtype == x.dtype:
+        if ctx.has_bits:  # (y: the mask bits)
+            lib.rtsds_bn_bwd_bits(_P(dy), ldy, _P(x), _P(y), _P(dx), _P(dres), _P(dg), _P(db), rows, c, _P(gamma),
+                                  _P(beta), _P(sm), _P(si), acc, dcode(x), _P(ws), ws.numel(), stream())
+        elif link is not None and link.part is not None and dy.dtype == x.dtype:
             # statistics from the reading conv's data-gradient epilogue
             lib.rtsds_bn_bwd_part(_P(dy), _P(x), _P(dx), _P(dg), _P(db), rows, c, _P(gamma), _P(beta), _P(sm),
                                   _P(si), training, act, acc, _P(link.part), link.nrb, dcode(x), _P(ws), ws.numel(),
@@ -784,6 +821,78 @@ def batch_norm(x, gamma, beta, running_mean, running_var, training, momentum, ep
         wg_link = wg_link.take(x, training and residual is None, act)
     return BatchNormFn.apply(x, gamma, beta, residual, running_mean, running_var, training,
                              momentum, eps, act, stats, nrb, num_batches_tracked, res_join, link, out, wg_link)
+
+
+class BatchNormPairFn(torch.autograd.Function):
+    """relu(bnA(xa) + bnB(xb)) for the end of a residual block with a downsample branch: xa the raw
+    output of the block's last conv, xb of its downsample conv, both [N, C, H, W] of one shape.
+    Stands for BatchNormFn(xb) -> BatchNormFn(xa, residual = that) in training mode with the same
+    bits (rtsds_bn_pair_fwd / rtsds_bn_pair_bwd): three launches per direction instead of six, the
+    skip tensor and its gradient never stored.  ``pa`` / ``pb``: (running_mean, running_var,
+    num_batches_tracked, momentum, eps, stats, stats_nrb) of each BatchNorm."""
+
+    @staticmethod
+    def forward(ctx, xa, xb, ga, ba, gb, bb, pa, pb):
+        require_hip(xa)
+        xa, xb = nhwc(xa), nhwc(xb)
+        n, c, h, w = xa.shape
+        rows = n * h * w
+        y = torch.empty_like(xa, memory_format=CL)
+        bits = torch.empty(lib.rtsds_bn_bits_bytes(rows, c, dcode(xa)), dtype=torch.uint8, device=xa.device)
+        sv = [torch.empty(c, dtype=torch.float32, device=xa.device) for _ in range(4)]
+        ws = workspace(lib.rtsds_bn_pair_workspace(rows, c), xa.device)
+        qa = BnParams(_P(ga), _P(ba), _P(pa[0]), _P(pa[1]), _P(pa[2]), _P(sv[0]), _P(sv[1]), float(pa[3]), float(pa[4]),
+                      _P(pa[5]), int(pa[6] or 0), 0, None, None)
+        qb = BnParams(_P(gb), _P(bb), _P(pb[0]), _P(pb[1]), _P(pb[2]), _P(sv[2]), _P(sv[3]), float(pb[3]), float(pb[4]),
+                      _P(pb[5]), int(pb[6] or 0), 0, None, None)
+        lib.rtsds_bn_pair_fwd(_P(xa), _P(xb), _P(y), _P(bits), rows, c, ctypes.byref(qa), ctypes.byref(qb), dcode(xa),
+                              _P(ws), ws.numel(), stream())
+        ctx.meta = (rows, c)
+        ctx.params = (ga, ba, gb, bb)
+        ctx.save_for_backward(xa, xb, bits, ga, ba, gb, bb, *sv)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xa, xb, bits, ga, ba, gb, bb, sma, sia, smb, sib = ctx.saved_tensors
+        rows, c = ctx.meta
+        ldy = _channel_slice_pitch(dy)
+        if not ldy:
+            dy = nhwc(dy)
+            ldy = c
+        need = ctx.needs_input_grad
+        dxa = torch.empty_like(xa, memory_format=CL)
+        dxb = torch.empty_like(xb, memory_format=CL)
+        dga, dba, acca = _bn_grads_of(ctx.params[0], ctx.params[1], need[2], need[3], c, xa.device)
+        dgb, dbb, accb = _bn_grads_of(ctx.params[2], ctx.params[3], need[4], need[5], c, xa.device)
+        ws = workspace(lib.rtsds_bn_pair_workspace(rows, c), xa.device)
+        qa = BnParams(_P(ga), _P(ba), None, None, None, _P(sma), _P(sia), 0.0, 0.0, None, 0, acca, _P(dga), _P(dba))
+        qb = BnParams(_P(gb), _P(bb), None, None, None, _P(smb), _P(sib), 0.0, 0.0, None, 0, accb, _P(dgb), _P(dbb))
+        lib.rtsds_bn_pair_bwd(_P(dy), ldy, _P(xa), _P(xb), _P(bits), _P(dxa), _P(dxb), rows, c, ctypes.byref(qa),
+                              ctypes.byref(qb), dcode(xa), _P(ws), ws.numel(), stream())
+        if acca:
+            dga = dba = None
+        if accb:
+            dgb = dbb = None
+        return dxa, dxb, dga, dba, dgb, dbb, None, None
+
+
+def batch_norm_pair(xa, bn_a, xb, bn_b, training, act=ACT_RELU):
+    """act(bnA(xa) + bnB(xb)), the two BatchNorms that end a residual block with a downsample
+    branch.  ``bn_a`` / ``bn_b``: (gamma, beta, running_mean, running_var, momentum, eps,
+    num_batches_tracked) of each.  Training mode with ReLU, bf16 / fp32, one shape, c % 8 == 0
+    and gradients wanted for both inputs: one BatchNormPairFn; everything else runs the chain
+    batch_norm(xb) -> batch_norm(xa, residual=...).  The results are the same bits either way."""
+    ga, ba, rma, rva, moma, epsa, nbta = bn_a
+    gb, bb, rmb, rvb, momb, epsb, nbtb = bn_b
+    if RES_BN_PAIR and xa.dim() == 4 and _res_bits_ok(xa, xb, training, act) and torch.is_grad_enabled() \
+            and xa.requires_grad and xb.requires_grad and xa.is_cuda:
+        sa, na = _bn_epilogue_stats(xa, training, rma)
+        sb, nb = _bn_epilogue_stats(xb, training, rmb)
+        return BatchNormPairFn.apply(xa, xb, ga, ba, gb, bb, (rma, rva, nbta, moma, epsa, sa, na),
+                                     (rmb, rvb, nbtb, momb, epsb, sb, nb))
+    skip = batch_norm(xb, gb, bb, rmb, rvb, training, momb, epsb, 0, None, nbtb)
+    return batch_norm(xa, ga, ba, rma, rva, training, moma, epsa, act, skip, nbta)
 
 
 # ----------------------------------------------------------------------------- layout / dtype

@@ -14,7 +14,8 @@ from torch import nn
 
 from rtsds_amd import functional as F
 from rtsds_amd.functional import BnBwdLink
-from rtsds_amd.nn import BatchNorm2d, Conv2d, MaxPool2d, ReLU, conv_bn, conv_bn_relu_maxpool, grad_join
+from rtsds_amd.nn import (BatchNorm2d, Conv2d, MaxPool2d, ReLU, conv_bn, conv_bn_relu_maxpool, downsample_branch, grad_join,
+                          res_block_tail)
 from rtsds_amd.runtime import grad_cut
 
 
@@ -35,14 +36,14 @@ class BasicBlock(nn.Module):
         # x has two readers (conv1 and the identity / downsample branch): their gradients meet
         # in one buffer (the later producer's kernel accumulates) instead of an autograd add
         join = grad_join(x, 2)
-        skip = x
+        skip, ds_bn = x, None
         if self.downsample is not None:
-            skip = conv_bn(self.downsample[0], self.downsample[1], x, join=join)
+            skip, ds_bn = downsample_branch(self.downsample, x, join)
         link = BnBwdLink()  # bn1's output has one reader, conv2: its dgrad yields bn1's backward statistics
         t = conv_bn(self.conv1, self.bn1, x, "relu", join=join, out_link=link)
-        # bn2 + residual add + ReLU in one pass
-        return conv_bn(self.conv2, self.bn2, t, "relu", skip,
-                       res_join=join if self.downsample is None else None, in_link=link)
+        # bn2 (+ the downsample BatchNorm) + residual add + ReLU in one pass
+        return res_block_tail(self.conv2, self.bn2, t, skip, ds_bn,
+                              res_join=join if self.downsample is None else None, in_link=link)
 
 
 class Bottleneck(nn.Module):
@@ -63,14 +64,14 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         join = grad_join(x, 2)  # as BasicBlock
-        skip = x
+        skip, ds_bn = x, None
         if self.downsample is not None:
-            skip = conv_bn(self.downsample[0], self.downsample[1], x, join=join)
+            skip, ds_bn = downsample_branch(self.downsample, x, join)
         l1, l2 = BnBwdLink(), BnBwdLink()  # bn1 -> conv2, bn2 -> conv3 (single readers)
         t = conv_bn(self.conv1, self.bn1, x, "relu", join=join, out_link=l1)
         t = conv_bn(self.conv2, self.bn2, t, "relu", in_link=l1, out_link=l2)
-        return conv_bn(self.conv3, self.bn3, t, "relu", skip,
-                       res_join=join if self.downsample is None else None, in_link=l2)
+        return res_block_tail(self.conv3, self.bn3, t, skip, ds_bn,
+                              res_join=join if self.downsample is None else None, in_link=l2)
 
 
 class ResNet(nn.Module):

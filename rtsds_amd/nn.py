@@ -158,6 +158,47 @@ def conv_bn(conv, bn, x, act=None, residual=None, join=None, res_join=None, in_l
               res_join=res_join, link=out_link, out=out, wg_link=wg)
 
 
+def _bn_pair_args(bn):
+    """A BatchNorm2d's operands as functional.batch_norm_pair takes them (BatchNorm2d.forward's)."""
+    track = bn.track_running_stats
+    return (bn.weight, bn.bias, bn.running_mean if track else None, bn.running_var if track else None, bn.momentum,
+            bn.eps, bn.num_batches_tracked if (bn.training and track) else None)
+
+
+def _bn_pair_ok(conv, bn, x):
+    """Whether ``bn`` after ``conv`` on ``x`` can be one half of functional.batch_norm_pair: batch
+    statistics, gradients wanted, whole 16-byte channel vectors (the Function checks the rest)."""
+    return (F.RES_BN_PAIR and (bn.training or not bn.track_running_stats) and bn.momentum is not None
+            and torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad)
+            and conv.out_channels % 8 == 0 and conv.in_channels != 3 and x.dtype in (torch.bfloat16, torch.float32))
+
+
+def downsample_branch(ds, x, join):
+    """The downsample branch (conv, BatchNorm) of a residual block on the block input ``x``, for
+    res_block_tail: (skip, None), or -- when the BatchNorm is to run paired with the block's last
+    one -- (the raw conv output, the BatchNorm).  Called where the chain calls conv_bn on the
+    branch, before the block's conv1, so the backward reaches the convs in the same order."""
+    conv, bn = ds[0], ds[1]
+    if len(ds) == 2 and _bn_pair_ok(conv, bn, x):
+        return conv(x, bn_stats=True, join=join), bn
+    return conv_bn(conv, bn, x, join=join), None
+
+
+def res_block_tail(conv, bn, t, skip, ds_bn=None, res_join=None, in_link=None):
+    """relu(bn(conv(t)) + skip), the end of a residual block.  ``skip``, ``ds_bn``: the block input
+    (None), or downsample_branch's result; with a BatchNorm still to run, both BatchNorms run as one
+    functional.batch_norm_pair (three launches per direction instead of six, the skip tensor never
+    stored), which computes the same bits."""
+    if ds_bn is None:
+        return conv_bn(conv, bn, t, "relu", skip, res_join=res_join, in_link=in_link)
+    if not _bn_pair_ok(conv, bn, t):
+        return conv_bn(conv, bn, t, "relu", ds_bn(skip), in_link=in_link)
+    xa = conv(t, bn_stats=True, bn_link=in_link)
+    if xa.shape[0] * xa.shape[2] * xa.shape[3] == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(xa.shape)}")
+    return F.batch_norm_pair(xa, _bn_pair_args(bn), skip, _bn_pair_args(ds_bn), True)
+
+
 def conv_bn_relu_maxpool(conv, bn, pool, x):
     """pool(relu(bn(conv(x)))) -- the ResNet stem.  Train-mode (batch statistics) bf16 with a
     3x3 stride-2 pool: the BN apply, ReLU and pool run as one pass (functional.bn_relu_maxpool,
