@@ -756,6 +756,39 @@ int rtsds_fda_spectrum(const uint8_t* img, int c, int h, int w, int b, float* sp
 int rtsds_fda_apply(const uint8_t* src, void* dst, int dst_u8, int c, int h, int w, int b, const float* spec_src,
                     const float* amp_ref_norm, float strength, void* stream);
 
+/* ---------------------------------------------------------------- knowledge distillation
+ * Soft-target loss between two low-resolution class maps (Hinton et al., 2015; no reference
+ * counterpart): student s [n][hs][ws][c] and teacher t [n][ht][wt][c], NHWC, each fp32 or bf16 by
+ * its own dtype code, 2 <= c <= 32.  The teacher is resampled onto the student's grid inside the
+ * kernel: bilinear, align_corners = False, not antialiased, any ratio up or down; scale_h / scale_w
+ * are ATen's source scales ht / hs and wt / ws in fp32, the four taps are blended in fp32 and the
+ * blend is not rounded to a storage type; a tap of weight zero is left out, so equal sizes give the
+ * identity, also for a teacher logit of -inf (a masked class).  Per student
+ * pixel, with a = s * inv_temp, b = u * inv_temp (u the resampled teacher row, inv_temp = fp32(1/T)),
+ * q = softmax(a), p = softmax(b):
+ *   KL = sum_k p_k (log p_k - log q_k)      a term with p_k == 0 contributes 0
+ * Both softmaxes are one expression, so t == s gives exactly 0.  Neither u nor p, q reach memory.
+ * rtsds_distill_fwd: one launch; workgroup i leaves the KL sum of its tile in the workspace, and,
+ *   when want_grad, the residual q - p as fp32 [n][hs][ws][c] behind the partials.  agree (or NULL):
+ *   a device counter that receives += the number of pixels whose first maximum (torch.argmax's rule)
+ *   of s equals that of u; integer atomics only.
+ * rtsds_distill_finish: loss = coef * (sum of the partials), summed in a fixed order in fp64: the
+ *   same bits on every run.  The caller passes coef = T^2 / (n hs ws world).
+ * rtsds_distill_bwd: dx [n][hs][ws][c] (dtype) = cast(fp32(*grad_loss * coef_g) * (q - p)) from the
+ *   residual of a want_grad forward on the same workspace; coef_g = T / (n hs ws world).
+ * None synchronises, allocates or touches the host.  Before any HIP call: RTSDS_ERR_SHAPE for a NULL
+ * tensor, a size < 1, c outside [2, 32], a tensor of 2^31 elements or more, a scale, inv_temp or
+ * coefficient that is not positive and finite; RTSDS_ERR_UNSUPPORTED for another dtype code, a
+ * tensor not aligned to its element, a workspace not 16-B aligned; RTSDS_ERR_WORKSPACE for a NULL or
+ * short workspace (rtsds_distill_workspace bytes; 0 for a shape it refuses).                       */
+size_t rtsds_distill_workspace(int n, int hs, int ws, int c, int ht, int wt);
+int rtsds_distill_fwd(const void* s, int s_dtype, const void* t, int t_dtype, int n, int hs, int ws, int c, int ht, int wt,
+                      float scale_h, float scale_w, float inv_temp, int want_grad, unsigned long long* agree, void* wsp,
+                      size_t ws_bytes, void* stream);
+int rtsds_distill_finish(const void* wsp, size_t ws_bytes, int n, int hs, int ws, double coef, float* loss, void* stream);
+int rtsds_distill_bwd(const void* wsp, size_t ws_bytes, const float* grad_loss, double coef_g, void* dx, int dtype, int n, int hs,
+                      int ws, int c, void* stream);
+
 /* ---------------------------------------------------------------- graph replay
  * Replaces hipGraphLaunch of a captured multi-stream iteration (runtime.GraphedStep /
  * GraphedForward; the reference has no graphs: its train.py:65-113 / 172-284 loop bodies
@@ -828,7 +861,7 @@ int rtsds_bn_bwd_ffm(const void* dr, const void* att, const void* dpooled, int n
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 24
+#define RTSDS_ABI_VERSION 25
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

@@ -8,5 +8,6 @@ torch.distributed (RCCL).
 """
 from .runtime import compute_dtype, precision, set_compute_dtype  # noqa: F401
 from .ema import EMATeacher  # noqa: F401,E402
+from .distill import Distiller  # noqa: F401,E402
 
-__all__ = ["compute_dtype", "precision", "set_compute_dtype", "EMATeacher"]
+__all__ = ["compute_dtype", "precision", "set_compute_dtype", "EMATeacher", "Distiller"]

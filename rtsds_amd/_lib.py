@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSDS_LIB: alternative in-tree build of the same ABI (kernel-variant A/B measurements)
 DEFAULT_LIB_PATH = os.path.join(_HERE, "librtsds_hip.so")
-ABI_VERSION = 24  # include/rtsds_hip.h RTSDS_ABI_VERSION
+ABI_VERSION = 25  # include/rtsds_hip.h RTSDS_ABI_VERSION
 LIB_PATH = os.environ.get("RTSDS_LIB") or DEFAULT_LIB_PATH
 
 F32, BF16 = 0, 1
@@ -24,8 +24,8 @@ WEIGHT_PACKED = 0x800
 UPCE_SET_CORRECT = 2  # rtsds_upce_fwd want_grad flag
 ERRORS = {1: "bad shape", 2: "unsupported configuration", 3: "HIP launch failure", 4: "workspace too small"}
 
-c_int, c_long, c_float, c_size_t, c_void_p = (ctypes.c_int, ctypes.c_long, ctypes.c_float,
-                                              ctypes.c_size_t, ctypes.c_void_p)
+c_int, c_long, c_float, c_double, c_size_t, c_void_p = (ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double,
+                                                        ctypes.c_size_t, ctypes.c_void_p)
 
 
 class ConvDesc(ctypes.Structure):
@@ -179,6 +179,10 @@ SIGNATURES = {
     "rtsds_fda_workspace": (c_size_t, [c_int, c_int, c_int]),
     "rtsds_fda_spectrum": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "rtsds_fda_apply": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_float, P]),
+    "rtsds_distill_workspace": (c_size_t, [c_int] * 6),
+    "rtsds_distill_fwd": (c_int, [P, c_int, P, c_int] + [c_int] * 6 + [c_float, c_float, c_float, c_int, P, P, c_size_t, P]),
+    "rtsds_distill_finish": (c_int, [P, c_size_t, c_int, c_int, c_int, c_double, P, P]),
+    "rtsds_distill_bwd": (c_int, [P, c_size_t, P, c_double, P, c_int, c_int, c_int, c_int, c_int, P]),
     "rtsds_sgd_step": (c_int, [P, P, P, P, c_long, P, c_float, c_float, c_float, c_float, c_int, c_int,
                                c_float, c_int, P]),
     "rtsds_adam_step": (c_int, [P, P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float,

@@ -1843,6 +1843,77 @@ def upsample_cross_entropy(heads, target, geo, ignore_index=-100, correct=None, 
     return total
 
 
+class DistillKLFn(torch.autograd.Function):
+    """distill_kl: rtsds_distill_fwd + rtsds_distill_finish, backward rtsds_distill_bwd from the
+    residual q - p the forward left in its workspace.  A gradient for the student only."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, temperature, agree, nbytes):
+        s, t = nhwc(student), nhwc(teacher)
+        n, c, hs, ws = s.shape
+        ht, wt = t.shape[2:]
+        buf = workspace(nbytes, s.device)
+        loss = torch.empty((), dtype=torch.float32, device=s.device)
+        want = bool(ctx.needs_input_grad[0])
+        pixels = float(n * hs * ws * dp_world())
+        lib.rtsds_distill_fwd(_P(s), dcode(s), _P(t), dcode(t), n, hs, ws, c, ht, wt, _src_scale(ht, hs, None),
+                              _src_scale(wt, ws, None), float(np.float32(1.0 / temperature)), int(want), _P(agree),
+                              _P(buf), buf.numel(), stream())
+        lib.rtsds_distill_finish(_P(buf), buf.numel(), n, hs, ws, temperature * temperature / pixels, _P(loss), stream())
+        if want:
+            ctx.buf, ctx.coef_g, ctx.geo, ctx.dtype = buf, temperature / pixels, (n, c, hs, ws), s.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        n, c, hs, ws = ctx.geo
+        dx = empty_nhwc(n, c, hs, ws, ctx.dtype, ctx.buf.device)
+        g = g.contiguous().float()
+        lib.rtsds_distill_bwd(_P(ctx.buf), ctx.buf.numel(), _P(g), ctx.coef_g, _P(dx), dcode(dx), n, hs, ws, c, stream())
+        return dx, None, None, None, None
+
+
+def distill_kl(student_low, teacher_low, temperature=1.0, agree=None):
+    """Knowledge-distillation loss (Hinton et al., 2015) between two low-resolution class maps, in
+    one fused pass (csrc/distill.hip).  The reference has no distillation; the protocol is this:
+
+    * ``student_low`` [n, c, hs, ws] and ``teacher_low`` [n, c, ht, wt] are the models' main heads
+      before their final resize (forward_lowres), fp32 or bf16 each, NHWC or NCHW memory.  The loss
+      lives on the student's grid, where the student's own gradient does: no bilinear adjoint, and
+      64x fewer pixels than at the label size.
+    * The teacher is resampled onto that grid inside the kernel: bilinear, align_corners=False, not
+      antialiased, any ratio up or down (BiSeNet's 64x128 head from DeepLab's 65x129), blended in
+      fp32 and not rounded to the storage type; equal sizes give the identity.
+    * Per student pixel, a = s/T, b = u/T (u the resampled teacher row), q = softmax(a), p = softmax(b):
+      KL = sum_k p_k (log p_k - log q_k), a term with p_k == 0 counting 0 (torch's xlogy rule);
+      loss = T^2 * sum_pixels KL / (n hs ws world), dloss/ds = g T (q - p) / (n hs ws world) --
+      F.kl_div(log_softmax(s/T), softmax(u/T), 'sum') * T^2 / pixels.  ``world`` is
+      runtime.dp_world(): the ranks' losses and gradients sum to the global batch's, assuming equal
+      shards (BCE's world * local batch rule).
+    * ``agree``: an optional one-element int64 (or uint64) device counter; the number of pixels whose
+      argmax of s equals that of u is added to it.
+    * The teacher gets no gradient.  Two runs give the same bits; no host sync (graph-capture safe)."""
+    require_hip(student_low, teacher_low, agree)
+    if student_low.dim() != 4 or teacher_low.dim() != 4:
+        raise RuntimeError("rtsds_amd.distill_kl: student and teacher must be [n, c, h, w]")
+    if student_low.shape[1] != teacher_low.shape[1]:
+        raise RuntimeError(f"rtsds_amd.distill_kl: student has {student_low.shape[1]} classes, teacher {teacher_low.shape[1]}")
+    if not 2 <= student_low.shape[1] <= 32:
+        raise RuntimeError(f"rtsds_amd.distill_kl: the class count must lie in [2, 32], got {student_low.shape[1]}")
+    if student_low.shape[0] != teacher_low.shape[0]:
+        raise RuntimeError(f"rtsds_amd.distill_kl: batch sizes differ ({student_low.shape[0]} and {teacher_low.shape[0]})")
+    temperature = float(temperature)
+    if not (temperature > 0.0 and np.isfinite(temperature)):
+        raise RuntimeError(f"rtsds_amd.distill_kl: temperature must be positive, got {temperature}")
+    if agree is not None and (agree.numel() != 1 or agree.dtype not in (torch.int64, torch.uint64)):
+        raise RuntimeError("rtsds_amd.distill_kl: agree must be a one-element int64 / uint64 tensor")
+    n, c, hs, ws = student_low.shape
+    nbytes = lib.rtsds_distill_workspace(n, hs, ws, c, *teacher_low.shape[2:])
+    if not nbytes:
+        raise RuntimeError("rtsds_amd.distill_kl: the kernel does not cover these sizes")
+    return DistillKLFn.apply(student_low, teacher_low.detach(), temperature, agree, nbytes)
+
+
 class UpsampleSoftmaxFn(torch.autograd.Function):
     """softmax(interpolate_bilinear(x, geo), dim=1) in one pass (rtsds_upsoftmax_fwd), written
     zero-padded to 32 channels so the discriminator's first conv reads it directly

@@ -60,3 +60,21 @@ class BCEWithLogitsLoss(nn.Module):
         scale = (n / cnt).to(loss.dtype).reshape(())
         self._scale[key] = scale
         return loss * scale
+
+
+class DistillationLoss(nn.Module):
+    """Soft-target loss T^2 * KL(softmax(teacher / T) || softmax(student / T)), averaged over the
+    student's pixels, between two low-resolution heads [N, C, h, w] whose grids may differ: the
+    teacher is resampled onto the student's inside the kernel (functional.distill_kl, which states
+    the whole protocol).  The reference has no counterpart.  ``agree``: optional int64 device
+    counter that receives the number of pixels on which the two argmaxes agree.  Under data
+    parallelism the mean runs over world * local pixels (equal shards)."""
+
+    def __init__(self, temperature=1.0):
+        super().__init__()
+        if not float(temperature) > 0.0:
+            raise ValueError(f"rtsds_amd.DistillationLoss: temperature must be positive, got {temperature}")
+        self.temperature = float(temperature)
+
+    def forward(self, student_low, teacher_low, agree=None):
+        return F.distill_kl(student_low, teacher_low, self.temperature, agree)

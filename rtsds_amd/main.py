@@ -3,7 +3,7 @@ config.yaml, factories main.py:110-231, dispatch main.py:272-374) on the HIP pat
 
     python -m rtsds_amd.main [--config rtsds_amd/config.yaml] [--domain_adaptation]
                              [--model bisenet|deeplab] [--dataset cityscapes|gta5] [--seed 42]
-                             [--self_training]
+                             [--self_training] [--distill]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m rtsds_amd.main --domain_adaptation
 
 Datasets (main.py:46-108): when the configured directories exist, the reference's readers
@@ -244,6 +244,44 @@ def self_training_config(config):
     return st
 
 
+DISTILLATION_KEYS = ("teacher_model", "teacher_weights", "temperature", "weight")
+DISTILLATION_MODELS = ("deeplab", "bisenet")
+
+
+def distillation_config(config):
+    """The training.distillation block (commented out in the shipped config.yaml), complete."""
+    kd = config.training.get("distillation")
+    if kd is None:
+        raise RuntimeError("rtsds_amd: --distill needs the config block training.distillation "
+                           f"(keys: {', '.join(DISTILLATION_KEYS)}); config.yaml ships it commented out")
+    missing = [k for k in DISTILLATION_KEYS if k not in kd]
+    if missing:
+        raise RuntimeError(f"rtsds_amd: training.distillation lacks {', '.join(missing)}")
+    if kd["teacher_model"] not in DISTILLATION_MODELS:
+        raise RuntimeError(f"rtsds_amd: training.distillation.teacher_model must be one of "
+                           f"{', '.join(repr(m) for m in DISTILLATION_MODELS)}, got {kd['teacher_model']!r}")
+    for k, ok in (("temperature", lambda v: v > 0), ("weight", lambda v: v >= 0)):
+        v = kd[k]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v) or not ok(v):
+            raise RuntimeError(f"rtsds_amd: training.distillation.{k} must be a "
+                               f"{'positive' if k == 'temperature' else 'non-negative'} number, got {v!r}")
+    if not isinstance(kd["teacher_weights"], str) or not kd["teacher_weights"]:
+        raise RuntimeError("rtsds_amd: training.distillation.teacher_weights must be the path of a state_dict")
+    return kd
+
+
+def build_distiller(config, kd):
+    """The frozen teacher of the training.distillation block, built as predict.build_model builds
+    its model (DeepLab's ``pretrain`` off, the state_dict read with weights_only=True, nothing
+    fetched), as a distill.Distiller."""
+    from .distill import Distiller
+    from .predict import build_model
+    if not os.path.isfile(kd["teacher_weights"]):
+        raise RuntimeError(f"rtsds_amd: training.distillation.teacher_weights {kd['teacher_weights']} does not exist")
+    teacher = build_model(config, kd["teacher_model"], kd["teacher_weights"])
+    return Distiller(teacher, temperature=kd["temperature"], weight=kd["weight"])
+
+
 def self_train_online(config, st, model, optimizer, criterion, init_lr, power, lr_decay_iter, target_dl, validate,
                       callbacks, source_dl, model_name):
     """Online (mean-teacher) self-training, ``mode: online``: a second model of the branch's
@@ -326,6 +364,9 @@ def argumnet_parser(argv=None):
     p.add_argument("--self_training", action="store_true",
                    help="self-training on the target set after the normal run: class-balanced sweeps, or "
                         "with mode: online an EMA teacher per batch (config block training.self_training)")
+    p.add_argument("--distill", action="store_true",
+                   help="segmentation branch only: add a frozen teacher's soft targets to the loss "
+                        "(config block training.distillation)")
     return p.parse_args(argv)
 
 
@@ -348,6 +389,9 @@ def main(argv=None):
     config = load_config(args.config)
     set_compute_dtype(torch.bfloat16 if getattr(config, "precision", "fp32") == "bf16" else torch.float32)
     st = self_training_config(config) if args.self_training else None
+    if args.distill and args.domain_adaptation:
+        raise RuntimeError("rtsds_amd: --distill applies to the segmentation branch only, not with --domain_adaptation")
+    kd = distillation_config(config) if args.distill else None
     train_dl, val_dl, gta_dl = datasets_loader(config, args.augmented)
     target_dl = train_dl
     callbacks = []
@@ -375,10 +419,18 @@ def main(argv=None):
         model, opt, crit, hp = model_loader(config, False, args.model)
         t = config.training["segmentation"]
         max_iter = t["epochs"] * len(train_dl)
+        if kd is not None:
+            from . import distill
+            distiller = build_distiller(config, kd)
         for epoch in range(t["epochs"]):
-            train(model=model, optimizer=opt, criterion=crit, train_loader=train_dl, epoch=epoch,
-                  init_lr=hp["init_lr"], lr_decay_iter=t["lr_decay_iter"], power=hp["power"],
-                  max_iter=max_iter, callbacks=callbacks, device=config.device)
+            if kd is not None:
+                distill.train(model=model, optimizer=opt, criterion=crit, train_loader=train_dl, epoch=epoch,
+                              init_lr=hp["init_lr"], lr_decay_iter=t["lr_decay_iter"], power=hp["power"],
+                              max_iter=max_iter, callbacks=callbacks, device=config.device, distiller=distiller)
+            else:
+                train(model=model, optimizer=opt, criterion=crit, train_loader=train_dl, epoch=epoch,
+                      init_lr=hp["init_lr"], lr_decay_iter=t["lr_decay_iter"], power=hp["power"],
+                      max_iter=max_iter, callbacks=callbacks, device=config.device)
             val(epoch=epoch, model=model, val_loader=val_dl, num_classes=t["num_classes"],
                 class_names=config.meta["class_names"], detailed_report=True, device=config.device,
                 callbacks=callbacks, scales=t.get("eval_scales"), flip=bool(t.get("eval_flip", False)))
