@@ -413,6 +413,18 @@ int rtsds_ce_fwd(const void* x, long sn, long sc, long shw, const int64_t* targe
 int rtsds_ce_bwd(const void* x, long sn, long sc, long shw, const int64_t* target,
                  const float* grad_loss, const float* count, void* dx, int n, long hw, int c,
                  int ignore_index, int dtype, void* stream);
+/* nn.CrossEntropyLoss(weight, ignore_index): loss = sum w[t] (lse - x[t]) / sum w[t] over the valid
+ * pixels, d loss / dx = w[t] / sum w * (softmax - onehot).  weight: c fp32 values on the device, never
+ * read past c.  Same routes, workspace and rtsds_ce_finish as the unweighted pair; the slot at
+ * ws + 2048 floats holds the weight sum (summed over data-parallel ranks by the caller like the
+ * count).  All-ones weights give the unweighted call's bits.  Before any launch: RTSDS_ERR_SHAPE
+ * for a NULL tensor or weight or c outside [1, 32], RTSDS_ERR_WORKSPACE for a NULL or short ws. */
+int rtsds_ce_weighted_fwd(const void* x, long sn, long sc, long shw, const int64_t* target,
+                          const float* weight, float* loss, int n, long hw, int c, int ignore_index,
+                          int dtype, void* ws, size_t ws_bytes, void* stream);
+int rtsds_ce_weighted_bwd(const void* x, long sn, long sc, long shw, const int64_t* target,
+                          const float* weight, const float* grad_loss, const float* count, void* dx,
+                          int n, long hw, int c, int ignore_index, int dtype, void* stream);
 /* nn.BCEWithLogitsLoss() mean (main.py:131-132), fp32.                                  */
 int rtsds_bce_fwd(const float* x, const float* target, float* loss, int n, void* stream);
 int rtsds_bce_bwd(const float* x, const float* target, const float* grad_loss, float* dx, int n,
@@ -492,6 +504,20 @@ int rtsds_upce_fwd(int nheads, const void* const* logits, const int64_t* target,
  * rtsds_upce_bwd scales by the global count: the ranks' losses and gradients sum to the
  * single-device mean over the gathered batch exactly.                                     */
 int rtsds_upce_finish(int nheads, const void* ws, float* loss, float* loss_sum, void* stream);
+/* rtsds_upce_fwd with class weights (nn.CrossEntropyLoss(weight)): weight holds c fp32 values on
+ * the device and is never read past c.  Per pixel the loss term, the count term (stat[0] becomes
+ * the sum of w[t] over the valid pixels) and the gradient factor are multiplied by w[t]; `correct`
+ * stays the unweighted match count.  The plan -- tiles, auxiliary wave, LDS, workspace layout --
+ * is that of rtsds_upce_fwd at the same geometry (the weights live in registers), so
+ * rtsds_upce_workspace, rtsds_upce_finish and rtsds_upce_bwd serve both, and every geometry the
+ * unweighted call covers is covered.  All-ones weights give the unweighted bits.  Before any
+ * launch: RTSDS_ERR_SHAPE for a NULL logits / target / weight pointer or c outside [1, 32];
+ * otherwise the codes of rtsds_upce_fwd.                                                    */
+int rtsds_upce_weighted_fwd(int nheads, const void* const* logits, const int64_t* target,
+                            const float* weight, int n, int hl, int wl, int c, int H, int W,
+                            float scale_h, float scale_w, int ignore_index, float* loss,
+                            float* loss_sum, unsigned long long* correct, int want_grad, int dtype,
+                            void* ws, size_t ws_bytes, void* stream);
 int rtsds_upce_bwd(int nheads, const float* grad_loss, int grad_stride, void* const* dlogits,
                    int n, int hl, int wl, int c, int H, int W, float scale_h, float scale_w,
                    int dtype, const void* ws, size_t ws_bytes, void* stream);
@@ -858,10 +884,23 @@ int rtsds_bn_bwd_ffm(const void* dr, const void* att, const void* dpooled, int n
                      const float* save_invstd, int training, int act, int accumulate_params, int dtype, void* ws,
                      size_t ws_bytes, void* stream);
 
+/* Label statistics for class weighting (csrc/labelstat.hip).  label: int64 [n][h][w]; per call
+ * count[k] += pixels labelled k and support[k] += valid pixels (label in [0, c)) of the images of
+ * this batch that contain class k, k < c <= 32; a label equal to ignore_index or outside [0, c)
+ * enters neither.  count / support: c uint64 each, accumulated into (the caller zeroes them once).
+ * Integers only: exact, order-independent; no host sync, no memset (graph-capture safe).
+ * RTSDS_ERR_SHAPE: a NULL label / count / support, n outside [1, 65535], h or w < 1, h * w above
+ * 2^32 - 1, c outside [1, 32]; RTSDS_ERR_WORKSPACE: a NULL or short ws (the query returns 0 for a
+ * shape it refuses); all before any launch.                                                   */
+size_t rtsds_label_stats_workspace(int n, int c);
+int rtsds_label_stats(const int64_t* label, int n, int h, int w, int c, int ignore_index,
+                      unsigned long long* count, unsigned long long* support, void* ws, size_t ws_bytes,
+                      void* stream);
+
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 25
+#define RTSDS_ABI_VERSION 26
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSDS_LIB: alternative in-tree build of the same ABI (kernel-variant A/B measurements)
 DEFAULT_LIB_PATH = os.path.join(_HERE, "librtsds_hip.so")
-ABI_VERSION = 25  # include/rtsds_hip.h RTSDS_ABI_VERSION
+ABI_VERSION = 26  # include/rtsds_hip.h RTSDS_ABI_VERSION
 LIB_PATH = os.environ.get("RTSDS_LIB") or DEFAULT_LIB_PATH
 
 F32, BF16 = 0, 1
@@ -144,6 +144,10 @@ SIGNATURES = {
                              c_size_t, P]),
     "rtsds_ce_bwd": (c_int, [P, c_long, c_long, c_long, P, P, P, P, c_int, c_long, c_int, c_int, c_int,
                              P]),
+    "rtsds_ce_weighted_fwd": (c_int, [P, c_long, c_long, c_long, P, P, P, c_int, c_long, c_int, c_int, c_int, P,
+                                      c_size_t, P]),
+    "rtsds_ce_weighted_bwd": (c_int, [P, c_long, c_long, c_long, P, P, P, P, P, c_int, c_long, c_int, c_int, c_int,
+                                      P]),
     "rtsds_bce_fwd": (c_int, [P, P, P, c_int, P]),
     "rtsds_bce_bwd": (c_int, [P, P, P, P, c_int, P]),
     "rtsds_adam_step_dev": (c_int, [P, P, P, P, P, c_long, P, c_float, c_float, c_float, c_float, c_float, c_int, P]),
@@ -196,6 +200,10 @@ SIGNATURES = {
     "rtsds_upce_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float]),
     "rtsds_upce_fwd": (c_int, [c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                c_int, P, P, P, c_int, c_int, P, c_size_t, P]),
+    "rtsds_upce_weighted_fwd": (c_int, [c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
+                                        c_int, P, P, P, c_int, c_int, P, c_size_t, P]),
+    "rtsds_label_stats_workspace": (c_size_t, [c_int, c_int]),
+    "rtsds_label_stats": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "rtsds_upce_bwd": (c_int, [c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                c_int, P, c_size_t, P]),
 }

@@ -642,7 +642,16 @@ extern "C" int rtsds_softmax_bwd(const void* dy, const void* y, int ld, void* dx
 // non-ignored pixels of logsumexp(x) - x[t].  Two passes for the forward (per-block partial
 // (sum, count) -> final), one fused pass for the backward.
 // ws layout: [0, RB) partial sums, [RB, 2RB) partial counts, [2RB] total count, [2RB + 1] total sum.
+// Class weights (nn.CrossEntropyLoss(weight=w), the WT = true instantiations behind
+// rtsds_ce_weighted_*): a pixel's loss term, its "count" term (now w[t]: the count slots hold the
+// weight sum) and its gradient factor g are each multiplied once by w[t].  A label outside [0, c)
+// reads no weight (its loss is NaN already).
 static const int kCeRB = 1024;
+template <bool WT>
+RT_DEV float ce_weight(const float* __restrict__ wgt, long t, int c) {
+  if constexpr (WT) return (t >= 0 && t < c) ? wgt[t] : 1.f;
+  else return 1.f;
+}
 // One non-ignored pixel's loss; a target outside [0, c) gives NaN.
 template <typename R>
 RT_DEV float px_ce_loss(R x, long t, int c) {
@@ -687,22 +696,29 @@ RT_DEV void ce_part_store(float s, float cnt, float* __restrict__ part) {
     part[kCeRB + blockIdx.x] = cnt;
   }
 }
-template <typename T>
+template <typename T, bool WT>
 __global__ void ce_fwd_part_kernel(const T* __restrict__ x, const int64_t* __restrict__ tgt, float* __restrict__ part, int n, long hw, int c,
-                                   long sn, long sc, long shw, int ignore) {
+                                   long sn, long sc, long shw, int ignore, const float* __restrict__ wgt) {
   const long total = (long)n * hw;
   float ls = 0.f, lc = 0.f;
   GRID_STRIDE(p, total) {
     const long t = tgt[p];
     if (t == ignore) continue;
-    ls += px_ce_loss(strided_row(x + pixel_offset(p, hw, sn, shw), sc), t, c);
-    lc += 1.f;
+    const float l = px_ce_loss(strided_row(x + pixel_offset(p, hw, sn, shw), sc), t, c);
+    if constexpr (WT) {
+      const float w = ce_weight<WT>(wgt, t, c);
+      ls += w * l;
+      lc += w;
+    } else {
+      ls += l;
+      lc += 1.f;
+    }
   }
   ce_part_store(ls, lc, part);
 }
-template <typename T>
+template <typename T, bool WT>
 __global__ void __launch_bounds__(256) ce_fwd_part_staged(const T* __restrict__ x, const int64_t* __restrict__ tgt, float* __restrict__ part,
-                                                          long total, int c, int ignore) {
+                                                          long total, int c, int ignore, const float* __restrict__ wgt) {
   T* buf = stage_buf<T>();
   float ls = 0.f, lc = 0.f;
   STAGE_TILES(p0, total) {
@@ -710,8 +726,15 @@ __global__ void __launch_bounds__(256) ce_fwd_part_staged(const T* __restrict__ 
     if ((int)threadIdx.x < np) {
       const long t = tgt[p0 + threadIdx.x];
       if (t != ignore) {
-        ls += px_ce_loss(dense_row((const T*)buf + threadIdx.x * c), t, c);
-        lc += 1.f;
+        const float l = px_ce_loss(dense_row((const T*)buf + threadIdx.x * c), t, c);
+        if constexpr (WT) {
+          const float w = ce_weight<WT>(wgt, t, c);
+          ls += w * l;
+          lc += w;
+        } else {
+          ls += l;
+          lc += 1.f;
+        }
       }
     }
   }
@@ -730,46 +753,64 @@ __global__ void ce_fwd_final_kernel(float* __restrict__ part, int nb, float* __r
 __global__ void ce_finish_kernel(const float* __restrict__ part, float* __restrict__ loss) {
   if (threadIdx.x == 0) loss[0] = part[2 * kCeRB + 1] / part[2 * kCeRB];
 }
-template <typename T>
+template <typename T, bool WT>
 __global__ void ce_bwd_kernel(const T* __restrict__ x, const int64_t* __restrict__ tgt, const float* __restrict__ gout,
                               const float* __restrict__ count, T* __restrict__ dx, int n, long hw, int c, long sn, long sc, long shw,
-                              int ignore) {
+                              int ignore, const float* __restrict__ wgt) {
   const float g = gout[0] / count[0];
   const long total = (long)n * hw;
   GRID_STRIDE(p, total) {
     const long off = pixel_offset(p, hw, sn, shw);
-    px_ce_grad<false>(strided_row(x + off, sc), strided_row(dx + off, sc), tgt[p], c, ignore, g);
+    const long t = tgt[p];
+    px_ce_grad<false>(strided_row(x + off, sc), strided_row(dx + off, sc), t, c, ignore, WT ? g * ce_weight<WT>(wgt, t, c) : g);
   }
 }
-template <typename T>
+template <typename T, bool WT>
 __global__ void __launch_bounds__(256) ce_bwd_staged(const T* __restrict__ x, const int64_t* __restrict__ tgt, const float* __restrict__ gout,
-                                                     const float* __restrict__ count, T* __restrict__ dx, long total, int c, int ignore) {
+                                                     const float* __restrict__ count, T* __restrict__ dx, long total, int c, int ignore,
+                                                     const float* __restrict__ wgt) {
   T* buf = stage_buf<T>();
   const float g = gout[0] / count[0];
   STAGE_TILES(p0, total) {
     const int np = tile_in(buf, p0, total, c, x);
     T* r = buf + threadIdx.x * c;
-    if ((int)threadIdx.x < np) px_ce_grad<true>(dense_row(r), dense_row(r), tgt[p0 + threadIdx.x], c, ignore, g);
+    if ((int)threadIdx.x < np) {
+      const long t = tgt[p0 + threadIdx.x];
+      px_ce_grad<true>(dense_row(r), dense_row(r), t, c, ignore, WT ? g * ce_weight<WT>(wgt, t, c) : g);
+    }
     tile_out(dx, buf, p0, np, c);
   }
 }
 
 extern "C" size_t rtsds_ce_workspace(void) { return (2 * kCeRB + 64) * sizeof(float); }
-extern "C" int rtsds_ce_fwd(const void* x, long sn, long sc, long shw, const int64_t* tgt, float* loss, int n, long hw, int c,
-                            int ignore_index, int dtype, void* ws, size_t ws_bytes, void* stream) {
+// WT: the class-weighted kernels (wgt[c]); the routes and launch shapes are the same
+template <bool WT>
+static int ce_fwd_run(const void* x, long sn, long sc, long shw, const int64_t* tgt, const float* wgt, float* loss, int n, long hw, int c,
+                      int ignore_index, int dtype, void* ws, size_t ws_bytes, void* stream) {
   if (n <= 0 || hw <= 0 || c <= 0) return RTSDS_ERR_SHAPE;
   if (ws_bytes < rtsds_ce_workspace()) return RTSDS_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int nb = std::min<int>(kCeRB, ew_blocks((long)n * hw, kStagePix, kCeRB));
   DISPATCH_T(dtype, {
     if (stage_ok(sn, sc, shw, hw, c))
-      hipLaunchKernelGGL(ce_fwd_part_staged<T>, dim3(nb), dim3(256), kStagePix * c * sizeof(T), st, (const T*)x, tgt, (float*)ws,
-                         (long)n * hw, c, ignore_index);
+      hipLaunchKernelGGL((ce_fwd_part_staged<T, WT>), dim3(nb), dim3(256), kStagePix * c * sizeof(T), st, (const T*)x, tgt, (float*)ws,
+                         (long)n * hw, c, ignore_index, wgt);
     else
-      hipLaunchKernelGGL(ce_fwd_part_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)x, tgt, (float*)ws, n, hw, c, sn, sc, shw, ignore_index);
+      hipLaunchKernelGGL((ce_fwd_part_kernel<T, WT>), dim3(nb), dim3(256), 0, st, (const T*)x, tgt, (float*)ws, n, hw, c, sn, sc, shw,
+                         ignore_index, wgt);
   });
   hipLaunchKernelGGL(ce_fwd_final_kernel, dim3(1), dim3(256), 0, st, (float*)ws, nb, loss);
   RET_LAUNCH();
+}
+extern "C" int rtsds_ce_fwd(const void* x, long sn, long sc, long shw, const int64_t* tgt, float* loss, int n, long hw, int c,
+                            int ignore_index, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  return ce_fwd_run<false>(x, sn, sc, shw, tgt, nullptr, loss, n, hw, c, ignore_index, dtype, ws, ws_bytes, stream);
+}
+extern "C" int rtsds_ce_weighted_fwd(const void* x, long sn, long sc, long shw, const int64_t* tgt, const float* weight, float* loss,
+                                     int n, long hw, int c, int ignore_index, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  if (!weight || !x || !tgt || c < 1 || c > 32) return RTSDS_ERR_SHAPE;
+  if (!ws) return RTSDS_ERR_WORKSPACE;
+  return ce_fwd_run<true>(x, sn, sc, shw, tgt, weight, loss, n, hw, c, ignore_index, dtype, ws, ws_bytes, stream);
 }
 // loss = S / C with C summed by the caller over data-parallel ranks (ws + 2*1024 floats: C, S).
 extern "C" int rtsds_ce_finish(const void* ws, float* loss, void* stream) {
@@ -777,17 +818,30 @@ extern "C" int rtsds_ce_finish(const void* ws, float* loss, void* stream) {
   RET_LAUNCH();
 }
 // count = the valid-pixel count written by rtsds_ce_fwd into its workspace (ws + 2*1024 floats).
-extern "C" int rtsds_ce_bwd(const void* x, long sn, long sc, long shw, const int64_t* tgt, const float* grad_loss, const float* count,
-                            void* dx, int n, long hw, int c, int ignore_index, int dtype, void* stream) {
+template <bool WT>
+static int ce_bwd_run(const void* x, long sn, long sc, long shw, const int64_t* tgt, const float* wgt, const float* grad_loss,
+                      const float* count, void* dx, int n, long hw, int c, int ignore_index, int dtype, void* stream) {
   if (n <= 0 || hw <= 0 || c <= 0) return RTSDS_ERR_SHAPE;
   DISPATCH_T(dtype, {
     if (stage_ok(sn, sc, shw, hw, c))
-      hipLaunchKernelGGL(ce_bwd_staged<T>, dim3(ew_blocks((long)n * hw, kStagePix, 4096)), dim3(256), kStagePix * c * sizeof(T),
-                         (hipStream_t)stream, (const T*)x, tgt, grad_loss, count, (T*)dx, (long)n * hw, c, ignore_index);
+      hipLaunchKernelGGL((ce_bwd_staged<T, WT>), dim3(ew_blocks((long)n * hw, kStagePix, 4096)), dim3(256), kStagePix * c * sizeof(T),
+                         (hipStream_t)stream, (const T*)x, tgt, grad_loss, count, (T*)dx, (long)n * hw, c, ignore_index, wgt);
     else
-      hipLaunchKernelGGL(ce_bwd_kernel<T>, dim3(ew_blocks((long)n * hw)), dim3(256), 0, (hipStream_t)stream, (const T*)x, tgt, grad_loss, count, (T*)dx, n, hw, c, sn, sc, shw, ignore_index);
+      hipLaunchKernelGGL((ce_bwd_kernel<T, WT>), dim3(ew_blocks((long)n * hw)), dim3(256), 0, (hipStream_t)stream, (const T*)x, tgt,
+                         grad_loss, count, (T*)dx, n, hw, c, sn, sc, shw, ignore_index, wgt);
   });
   RET_LAUNCH();
+}
+extern "C" int rtsds_ce_bwd(const void* x, long sn, long sc, long shw, const int64_t* tgt, const float* grad_loss, const float* count,
+                            void* dx, int n, long hw, int c, int ignore_index, int dtype, void* stream) {
+  return ce_bwd_run<false>(x, sn, sc, shw, tgt, nullptr, grad_loss, count, dx, n, hw, c, ignore_index, dtype, stream);
+}
+// count = the weight sum the weighted forward left at ws + 2*1024 floats
+extern "C" int rtsds_ce_weighted_bwd(const void* x, long sn, long sc, long shw, const int64_t* tgt, const float* weight,
+                                     const float* grad_loss, const float* count, void* dx, int n, long hw, int c, int ignore_index,
+                                     int dtype, void* stream) {
+  if (!weight || !x || !tgt || !grad_loss || !count || !dx || c < 1 || c > 32) return RTSDS_ERR_SHAPE;
+  return ce_bwd_run<true>(x, sn, sc, shw, tgt, weight, grad_loss, count, dx, n, hw, c, ignore_index, dtype, stream);
 }
 
 // ------------------------------------------------------------------ BCE with logits

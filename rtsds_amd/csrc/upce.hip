@@ -24,6 +24,16 @@
 // Traffic per head: the low-res logits once, the int64 labels once (L2-resident across the
 // heads of one tile), the low-res gradient partials once; nothing at full resolution is
 // written.
+//
+// Class weights (nn.CrossEntropyLoss(weight=w), the WT = true instantiations): per pixel the loss
+// term, the "count" term (now w[t], so stat[0] is the weight sum) and the gradient factor are each
+// multiplied once by w[t]; head 0's argmax matches stay unweighted.  The weight table is NOT in
+// LDS: lane k of every wave holds w[k] in a register (lanes >= c hold 0 and never read the buffer,
+// which has exactly c floats) and a pixel's w[t] is a cross-lane read issued at the top of the row
+// loop, while all 64 lanes are still active.  So a weighted call has the LDS size, tile sizes,
+// auxiliary-wave decision and workspace layout of the unweighted call of the same geometry, and
+// rtsds_upce_bwd / rtsds_upce_finish, which recompute that plan from the geometry alone, serve
+// both.  With WT = false every weighted statement compiles away.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -52,6 +62,9 @@ struct UpceArgs {
   UpceGeo g;
   int nheads, ignore, want_grad;
 };
+struct UpceWArgs : UpceArgs {
+  const float* weight;  // [c] class weights (the WT instantiations only)
+};
 
 // CP: channel count padded to a multiple of 4 (compile time, so every per-class loop is
 // fully unrolled without guards); padding classes hold -1e30 logits (softmax weight 0).
@@ -75,8 +88,8 @@ struct UpceArgs {
 // longer carries the 20-class argmax on top (a workgroup lasts as long as its slowest wave).
 static constexpr int kUpceOcc = 3;  // workgroups per CU
 enum { UPCE_ALL = 0, UPCE_HEAD = 1, UPCE_AUX = 2 };  // wave roles
-template <typename T, int CP, bool AX>
-__global__ void __launch_bounds__(256, kUpceOcc) upce_fwd_kernel(UpceArgs a) {
+template <typename T, int CP, bool AX, bool WT>
+__global__ void __launch_bounds__(256, kUpceOcc) upce_fwd_kernel(std::conditional_t<WT, UpceWArgs, UpceArgs> a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const UpceGeo& q = a.g;
   const int TH = q.th, TW = q.tw, C = q.c, TW1 = TW + 1, tid = threadIdx.x, nthr = blockDim.x;
@@ -94,6 +107,9 @@ __global__ void __launch_bounds__(256, kUpceOcc) upce_fwd_kernel(UpceArgs a) {
   const int tile_el = (TH + 1) * TW1 * C;  // gradient-partial layout (compact classes)
   const int rowp = TW1 * CP, ltile = (TH + 1) * rowp;
   const int npair = TW1 * C;
+  // class weights, one class per lane (see the header); issued first, consumed in the row loop
+  [[maybe_unused]] float wlane = 0.f;
+  if constexpr (WT) wlane = lane < C ? a.weight[lane] : 0.f;
 
   // LDS: wcol[TW1][wmax] | xj0 | xj1 | xm0 | xm1 [wmax] | xs | xe [TW1] |
   //      per head: lt[TH+1][TW1][CP] (low-res tile) | xrow[64][CP] (x-fold staging) |
@@ -283,6 +299,14 @@ __global__ void __launch_bounds__(256, kUpceOcc) upce_fwd_kernel(UpceArgs a) {
           int i0, i1;
           float l0, l1;
           bil_src(y, q.sh, q.hl, i0, i1, l0, l1);
+          // w[t] by a cross-lane read with every lane active (a label outside [0, C) reads lane 0:
+          // its loss is NaN already)
+          [[maybe_unused]] float wt = 1.f;
+          if constexpr (WT) wt = __shfl(wlane, tb < 253 ? tb : 0, 64);
+          auto wmul = [&](float v) {
+            if constexpr (WT) return wt * v;
+            else return v;
+          };
           if (!xv) continue;
           const bool in_range = tb < 253;
           const bool valid = tb != 254;
@@ -339,18 +363,19 @@ __global__ void __launch_bounds__(256, kUpceOcc) upce_fwd_kernel(UpceArgs a) {
             const float h0 = fmaf(m1, a00, m0 * a01);
             const float h1 = fmaf(m1, a10, m0 * a11);
             const float zt = in_range ? fmaf(l1, h1, l0 * h0) : NAN;
-            lsum += valid ? fmaf(__builtin_amdgcn_logf(se), kLN2, mx) - zt : 0.f;
-            if (h == 0) cnt += valid ? 1.f : 0.f;
+            lsum += valid ? wmul(fmaf(__builtin_amdgcn_logf(se), kLN2, mx) - zt) : 0.f;
+            if (h == 0) cnt += valid ? wmul(1.f) : 0.f;
             if (a.want_grad) {
               // g = softmax (- onehot(t), UPCE_ALL), folded vertically into the two low-res rows
-              const float is = valid ? __builtin_amdgcn_rcpf(se) : 0.f;
+              const float is = valid ? wmul(__builtin_amdgcn_rcpf(se)) : 0.f;
+              const float noh = wmul(-1.f);
               const f2 isv = {is, is}, l0v = {l0, l0}, l1v = {l1, l1};
               const int th1 = (valid && in_range) ? tb : -1;
 #pragma unroll
               for (int k = 0; k < CP2; ++k) {
                 f2 g;
                 if constexpr (kOnehot) {
-                  const f2 oh = {th1 == 2 * k ? -1.f : 0.f, th1 == 2 * k + 1 ? -1.f : 0.f};
+                  const f2 oh = {th1 == 2 * k ? noh : 0.f, th1 == 2 * k + 1 ? noh : 0.f};
                   g = __builtin_elementwise_fma(z[k], isv, oh);
                 } else {
                   g = z[k] * isv;
@@ -362,8 +387,8 @@ __global__ void __launch_bounds__(256, kUpceOcc) upce_fwd_kernel(UpceArgs a) {
           } else if (a.want_grad) {
             // the auxiliary wave: -onehot(t) folded vertically into the label's class only
             if (valid && in_range) {
-              atomicAdd(clo + lane * CP + tb, -l0);
-              atomicAdd(chi + lane * CP + tb, -l1);
+              atomicAdd(clo + lane * CP + tb, -wmul(l0));
+              atomicAdd(chi + lane * CP + tb, -wmul(l1));
             }
           }
         }
@@ -600,15 +625,17 @@ extern "C" size_t rtsds_upce_workspace(int nheads, int n, int hl, int wl, int c,
   return upce_ws_floats(g, nheads) * 4 + 256;
 }
 
-extern "C" int rtsds_upce_fwd(int nheads, const void* const* logits, const int64_t* target, int n, int hl, int wl, int c, int H, int W,
-                              float scale_h, float scale_w, int ignore_index, float* loss, float* loss_sum,
-                              unsigned long long* correct, int want_grad,
-                              int dtype, void* ws, size_t ws_bytes, void* stream) {
+// weight == nullptr: the unweighted kernels; the plan (tiles, auxiliary wave, LDS, workspace) never
+// depends on it
+static int upce_fwd_run(int nheads, const void* const* logits, const int64_t* target, const float* weight, int n, int hl, int wl, int c,
+                        int H, int W, float scale_h, float scale_w, int ignore_index, float* loss, float* loss_sum,
+                        unsigned long long* correct, int want_grad, int dtype, void* ws, size_t ws_bytes, void* stream) {
   UpceGeo g;
   if (nheads <= 0 || nheads > kUpceMaxHeads) return RTSDS_ERR_UNSUPPORTED;
   if (!upce_plan(n, hl, wl, c, H, W, scale_h, scale_w, g)) return RTSDS_ERR_UNSUPPORTED;
   if (ws_bytes < rtsds_upce_workspace(nheads, n, hl, wl, c, H, W, scale_h, scale_w) || !ws) return RTSDS_ERR_WORKSPACE;
-  UpceArgs a;
+  UpceWArgs a;
+  a.weight = weight;
   float* stat = (float*)ws;
   float* f = stat + kUpceStat;
   const size_t te = upce_tile_el(g);
@@ -630,20 +657,47 @@ extern "C" int rtsds_upce_fwd(int nheads, const void* const* logits, const int64
   const size_t lds = upce_lds(g, nheads);
   const dim3 blk(64 * (nheads + (upce_aux(g, nheads) ? 1 : 0)));
   switch (upce_cp(c)) {
-#define UPCE_CASE(CPV)                                                                                      \
-  case CPV:                                                                                                 \
-    DISPATCH_T(dtype, {                                                                                     \
-      if (a.gcorr) hipLaunchKernelGGL((upce_fwd_kernel<T, CPV, true>), dim3(g.nblocks), blk, lds, st, a);   \
-      else hipLaunchKernelGGL((upce_fwd_kernel<T, CPV, false>), dim3(g.nblocks), blk, lds, st, a);          \
-    });                                                                                                     \
+#define UPCE_LAUNCH(CPV, AXV, WTV, ARGS) \
+  hipLaunchKernelGGL((upce_fwd_kernel<T, CPV, AXV, WTV>), dim3(g.nblocks), blk, lds, st, ARGS)
+#define UPCE_CASE(CPV)                                               \
+  case CPV:                                                          \
+    DISPATCH_T(dtype, {                                              \
+      const UpceArgs& ua = a;                                        \
+      if (weight) {                                                  \
+        if (a.gcorr) UPCE_LAUNCH(CPV, true, true, a);                \
+        else UPCE_LAUNCH(CPV, false, true, a);                       \
+      } else {                                                       \
+        if (a.gcorr) UPCE_LAUNCH(CPV, true, false, ua);              \
+        else UPCE_LAUNCH(CPV, false, false, ua);                     \
+      }                                                              \
+    });                                                              \
     break;
     UPCE_CASE(4) UPCE_CASE(8) UPCE_CASE(12) UPCE_CASE(16) UPCE_CASE(20) UPCE_CASE(24) UPCE_CASE(28) UPCE_CASE(32)
 #undef UPCE_CASE
+#undef UPCE_LAUNCH
     default: return RTSDS_ERR_UNSUPPORTED;
   }
   hipLaunchKernelGGL(upce_final_kernel, dim3(1), dim3(256), 0, st, a.lpart, a.cpart, g.nblocks, nheads, loss, loss_sum, stat,
                      a.kpart, correct, (want_grad & RTSDS_UPCE_SET_CORRECT) ? 1 : 0);
   RET_LAUNCH();
+}
+
+extern "C" int rtsds_upce_fwd(int nheads, const void* const* logits, const int64_t* target, int n, int hl, int wl, int c, int H, int W,
+                              float scale_h, float scale_w, int ignore_index, float* loss, float* loss_sum,
+                              unsigned long long* correct, int want_grad,
+                              int dtype, void* ws, size_t ws_bytes, void* stream) {
+  return upce_fwd_run(nheads, logits, target, nullptr, n, hl, wl, c, H, W, scale_h, scale_w, ignore_index, loss, loss_sum, correct,
+                      want_grad, dtype, ws, ws_bytes, stream);
+}
+// nn.CrossEntropyLoss(weight): weight[c] fp32 on the device.  Same workspace, rtsds_upce_bwd and
+// rtsds_upce_finish as the unweighted call; stat[0] is the sum of w[t] over the valid pixels.
+extern "C" int rtsds_upce_weighted_fwd(int nheads, const void* const* logits, const int64_t* target, const float* weight, int n, int hl,
+                                       int wl, int c, int H, int W, float scale_h, float scale_w, int ignore_index, float* loss,
+                                       float* loss_sum, unsigned long long* correct, int want_grad, int dtype, void* ws,
+                                       size_t ws_bytes, void* stream) {
+  if (!weight || !logits || !target || c < 1 || c > kUpceCMax) return RTSDS_ERR_SHAPE;
+  return upce_fwd_run(nheads, logits, target, weight, n, hl, wl, c, H, W, scale_h, scale_w, ignore_index, loss, loss_sum, correct,
+                      want_grad, dtype, ws, ws_bytes, stream);
 }
 
 extern "C" int rtsds_upce_bwd(int nheads, const float* grad_loss, int grad_stride, void* const* dlogits, int n, int hl, int wl, int c, int H, int W,

@@ -62,7 +62,8 @@ def distill_step(model, distiller, criterion, optimizer, inputs, targets):
                            "cross-entropy covers")
     correct = torch.empty(1, dtype=torch.int64, device=inputs.device)  # (overwritten)
     agree = torch.zeros(1, dtype=torch.int64, device=inputs.device)
-    ce = F.upsample_cross_entropy(heads, targets, geo, criterion.ignore_index, correct, set_correct=True)
+    ce = F.upsample_cross_entropy(heads, targets, geo, criterion.ignore_index, correct, set_correct=True,
+                                  weight=criterion.weight)
     main_low = heads[0]
     distiller.low_pixels = main_low.shape[0] * main_low.shape[2] * main_low.shape[3]
     kd = F.distill_kl(main_low, teacher_low, distiller.temperature, agree)

@@ -1676,9 +1676,19 @@ def softmax(x, dim=1):
     return SoftmaxFn.apply(x)
 
 
+def _class_weight(weight, c, device):
+    """``weight`` of a weighted cross-entropy as the kernels take it: float32, c elements,
+    contiguous, on ``device`` (a static device tensor -- no copy, no host sync on the hot path)."""
+    if not (isinstance(weight, torch.Tensor) and weight.dtype == torch.float32 and weight.device == device
+            and tuple(weight.shape) == (c,)):
+        got = (tuple(weight.shape), weight.dtype, weight.device) if isinstance(weight, torch.Tensor) else type(weight)
+        raise RuntimeError(f"rtsds_amd: class weight must be a float32 tensor of {c} elements on {device}, got {got}")
+    return weight.contiguous()
+
+
 class CrossEntropyFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, target, ignore_index):
+    def forward(ctx, x, target, ignore_index, weight=None):
         require_hip(x, target)
         if target.dim() == 4:
             target = target.squeeze(1)
@@ -1691,14 +1701,20 @@ class CrossEntropyFn(torch.autograd.Function):
         sn, sc, shw = _pix_strides(x)
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         ws = workspace(lib.rtsds_ce_workspace(), x.device)
-        lib.rtsds_ce_fwd(_P(x), sn, sc, shw, _P(target), _P(loss), n, h * w, c, ignore_index,
-                         dcode(x), _P(ws), ws.numel(), stream())
-        if dp_world() > 1:  # global-batch mean: local loss sum over the all-reduced count
+        if weight is None:
+            lib.rtsds_ce_fwd(_P(x), sn, sc, shw, _P(target), _P(loss), n, h * w, c, ignore_index,
+                             dcode(x), _P(ws), ws.numel(), stream())
+        else:
+            weight = _class_weight(weight, c, x.device)
+            lib.rtsds_ce_weighted_fwd(_P(x), sn, sc, shw, _P(target), _P(weight), _P(loss), n, h * w, c, ignore_index,
+                                      dcode(x), _P(ws), ws.numel(), stream())
+        if dp_world() > 1:  # global-batch mean: local loss sum over the all-reduced count (weight sum)
             import torch.distributed as dist
             cnt = ws.view(torch.float32)[2048:2049]
             collective(lambda: dist.all_reduce(cnt))
             lib.rtsds_ce_finish(_P(ws), _P(loss), stream())
         ctx.ignore = ignore_index
+        ctx.weight = weight
         ctx.save_for_backward(x, target, ws)
         return loss
 
@@ -1710,13 +1726,24 @@ class CrossEntropyFn(torch.autograd.Function):
         dx = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
         g = g.contiguous().float()
         count = ws.view(torch.float32)[2048:2049]
-        lib.rtsds_ce_bwd(_P(x), sn, sc, shw, _P(target), _P(g), _P(count), _P(dx), n, h * w, c,
-                         ctx.ignore, dcode(x), stream())
-        return dx, None, None
+        if ctx.weight is None:
+            lib.rtsds_ce_bwd(_P(x), sn, sc, shw, _P(target), _P(g), _P(count), _P(dx), n, h * w, c,
+                             ctx.ignore, dcode(x), stream())
+        else:
+            lib.rtsds_ce_weighted_bwd(_P(x), sn, sc, shw, _P(target), _P(ctx.weight), _P(g), _P(count), _P(dx), n, h * w,
+                                      c, ctx.ignore, dcode(x), stream())
+        return dx, None, None, None
 
 
-def cross_entropy(x, target, ignore_index=-100):
-    return CrossEntropyFn.apply(x, target, ignore_index)
+def cross_entropy(x, target, ignore_index=-100, weight=None):
+    """nn.CrossEntropyLoss(weight, ignore_index) mean.  ``weight``: None (today's unweighted calls,
+    untouched) or a float32 device tensor of c class weights: loss = sum w[t] (lse - x[t]) / sum w[t]
+    over the valid pixels.  Under data parallelism nothing else changes: the slot that held the
+    local valid count holds the local weight sum, and the same one-element all-reduce makes it the
+    global one."""
+    if weight is None:
+        return CrossEntropyFn.apply(x, target, ignore_index)
+    return CrossEntropyFn.apply(x, target, ignore_index, weight)
 
 
 class AdaptiveAvgPoolFn(torch.autograd.Function):
@@ -1756,6 +1783,10 @@ class UpsampleCrossEntropyFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, target, geo, ignore_index, correct, set_correct, *heads):
+        return UpsampleCrossEntropyFn.run(ctx, target, geo, ignore_index, correct, set_correct, None, heads, 5)
+
+    @staticmethod
+    def run(ctx, target, geo, ignore_index, correct, set_correct, weight, heads, first):
         n, c, hl, wl, H, W, sh, sw = geo
         xs = [nhwc(h) for h in heads]
         k = len(xs)
@@ -1765,12 +1796,17 @@ class UpsampleCrossEntropyFn(torch.autograd.Function):
         ptrs = (ctypes.c_void_p * k)(*[x.data_ptr() for x in xs])
         per_head = torch.empty(k, dtype=torch.float32, device=xs[0].device)
         total = torch.empty((), dtype=torch.float32, device=xs[0].device)
-        want = any(ctx.needs_input_grad[5:])
+        want = any(ctx.needs_input_grad[first:])
         flags = int(want) | (UPCE_SET_CORRECT if set_correct else 0)
-        lib.rtsds_upce_fwd(k, ptrs, _P(target), n, hl, wl, c, H, W, sh, sw, ignore_index, _P(per_head),
-                           _P(total), _P(correct), flags, dt, _P(ws), ws.numel(), stream())
+        if weight is None:
+            lib.rtsds_upce_fwd(k, ptrs, _P(target), n, hl, wl, c, H, W, sh, sw, ignore_index, _P(per_head),
+                               _P(total), _P(correct), flags, dt, _P(ws), ws.numel(), stream())
+        else:
+            lib.rtsds_upce_weighted_fwd(k, ptrs, _P(target), _P(weight), n, hl, wl, c, H, W, sh, sw, ignore_index,
+                                        _P(per_head), _P(total), _P(correct), flags, dt, _P(ws), ws.numel(), stream())
         if dp_world() > 1:
-            # global-batch mean: this rank's loss sums over the all-reduced valid-pixel count
+            # global-batch mean: this rank's loss sums over the all-reduced valid-pixel count (the
+            # weight sum of a weighted call: stat[0] either way)
             # (its contribution; the ranks' losses and gradients then SUM to the single-device
             # values, see runtime.dp_world)
             import torch.distributed as dist
@@ -1795,6 +1831,19 @@ class UpsampleCrossEntropyFn(torch.autograd.Function):
         return (None, None, None, None, None, *dxs)
 
 
+class WeightedUpsampleCrossEntropyFn(torch.autograd.Function):
+    """UpsampleCrossEntropyFn with class weights (rtsds_upce_weighted_fwd): the same workspace plan
+    and the same backward, which divides by stat[0] -- the weight sum here."""
+
+    @staticmethod
+    def forward(ctx, target, geo, ignore_index, correct, set_correct, weight, *heads):
+        return UpsampleCrossEntropyFn.run(ctx, target, geo, ignore_index, correct, set_correct, weight, heads, 6)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (None, *UpsampleCrossEntropyFn.backward(ctx, g))
+
+
 def interpolate_geometry(x, geo):
     """interpolate_bilinear with a precomputed upsample_geometry()."""
     ho, wo, sh, sw = geo
@@ -1812,7 +1861,10 @@ def upsample_geometry(x, size=None, scale_factor=None):
     return ho, wo, s, s
 
 
-def upsample_cross_entropy_supported(heads, geo, ignore_index):
+def upsample_cross_entropy_supported(heads, geo, ignore_index, weight=None):
+    """Whether the fused upsample + CE covers these heads.  ``weight`` does not change the answer:
+    the weighted kernel keeps its weights in registers and runs the unweighted call's plan, so every
+    covered geometry is covered weighted too."""
     h0 = heads[0]
     n, c, hl, wl = h0.shape
     ho, wo, sh, sw = geo
@@ -1821,11 +1873,15 @@ def upsample_cross_entropy_supported(heads, geo, ignore_index):
     return lib.rtsds_upce_workspace(len(heads), n, hl, wl, c, ho, wo, sh, sw) > 0
 
 
-def upsample_cross_entropy(heads, target, geo, ignore_index=-100, correct=None, set_correct=False):
+def upsample_cross_entropy(heads, target, geo, ignore_index=-100, correct=None, set_correct=False, weight=None):
     """Sum over heads (in order) of cross_entropy(interpolate_bilinear(head, ...), target),
     fused; ``geo`` from upsample_geometry().  ``correct``: optional int64 device counter that
     receives head 0's pixel-accuracy matches (added; ``set_correct``: overwritten, so the
-    caller need not zero it).  Returns the total loss."""
+    caller need not zero it).  ``weight``: None, or a float32 device tensor of c class weights
+    (nn.CrossEntropyLoss(weight=)): each head's loss is sum w[t] (lse - z[t]) / sum w[t]; ``correct``
+    stays the unweighted count.  Under data parallelism nothing new is needed: stat[0] is the local
+    weight sum and the existing one-element all-reduce makes it the global one.  Returns the total
+    loss."""
     require_hip(target, *heads)
     t = target.squeeze(1) if target.dim() == 4 else target
     t = t.contiguous()
@@ -1835,12 +1891,35 @@ def upsample_cross_entropy(heads, target, geo, ignore_index=-100, correct=None, 
     ho, wo, sh, sw = geo
     if tuple(t.shape) != (n, ho, wo):
         raise RuntimeError(f"rtsds_amd: target shape {tuple(t.shape)} != {(n, ho, wo)}")
-    if not upsample_cross_entropy_supported(heads, geo, ignore_index):
+    if not upsample_cross_entropy_supported(heads, geo, ignore_index, weight):
         raise RuntimeError("rtsds_amd: fused upsample+CE does not cover this geometry")
     full = (n, c, hl, wl, ho, wo, sh, sw)
+    if weight is not None:
+        weight = _class_weight(weight, c, heads[0].device)
+        return WeightedUpsampleCrossEntropyFn.apply(t, full, int(ignore_index), correct, bool(set_correct), weight, *heads)
     fn = UpsampleCrossEntropyFn
     total = fn.apply(t, full, int(ignore_index), correct, bool(set_correct), *heads)
     return total
+
+
+def label_stats(labels, num_classes, ignore_index, count, support):
+    """Label statistics for class weighting (rtsds_label_stats): adds to ``count[k]`` the pixels of
+    ``labels`` (int64 [n, h, w] or [n, 1, h, w], on the device) labelled k, and to ``support[k]``
+    the valid pixels (label in [0, num_classes)) of the images that contain class k.  ``count`` /
+    ``support``: int64 device tensors of ``num_classes`` elements, accumulated into over calls.
+    Labels equal to ``ignore_index`` or outside the classes enter neither.  Exact; no host sync."""
+    require_hip(labels, count, support)
+    t = labels.squeeze(1) if labels.dim() == 4 else labels
+    if t.dim() != 3 or t.dtype != torch.int64:
+        raise RuntimeError(f"rtsds_amd: label_stats takes int64 [n, h, w] labels, got {tuple(labels.shape)} {labels.dtype}")
+    t = t.contiguous()
+    c = int(num_classes)
+    for name, v in (("count", count), ("support", support)):
+        if v.dtype != torch.int64 or tuple(v.shape) != (c,) or not v.is_contiguous():
+            raise RuntimeError(f"rtsds_amd: label_stats: {name} must be a contiguous int64 tensor of {c} elements")
+    n, h, w = t.shape
+    ws = workspace(lib.rtsds_label_stats_workspace(n, c), t.device)
+    lib.rtsds_label_stats(_P(t), n, h, w, c, int(ignore_index), _P(count), _P(support), _P(ws), ws.numel(), stream())
 
 
 class DistillKLFn(torch.autograd.Function):

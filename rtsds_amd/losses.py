@@ -1,5 +1,8 @@
 """Loss modules on the HIP kernels: drop-ins for the nn.CrossEntropyLoss(ignore_index) and
 nn.BCEWithLogitsLoss() built by the reference's optimzer_loss_loader (main.py:124-134)."""
+import math
+
+import numpy as np
 import torch
 from torch import nn
 
@@ -7,19 +10,102 @@ from . import functional as F
 from .runtime import dp_world
 
 
+WEIGHT_MODES = ("inverse_log", "median_frequency")
+
+
+def _weight_tensor(weight):
+    """A criterion's ``weight`` (sequence, ndarray or tensor) as a float32 CPU tensor, validated:
+    one dimension, every entry finite and non-negative."""
+    w = weight.detach().cpu() if isinstance(weight, torch.Tensor) else torch.as_tensor(np.asarray(weight))
+    if w.dim() != 1 or w.numel() == 0:
+        raise ValueError(f"rtsds_amd.CrossEntropyLoss: weight must be a 1-D sequence of class weights, got shape "
+                         f"{tuple(w.shape)}")
+    if w.dtype == torch.bool or w.is_complex():
+        raise ValueError(f"rtsds_amd.CrossEntropyLoss: weight must be numeric, got {w.dtype}")
+    w = w.to(torch.float64)
+    for k, v in enumerate(w.tolist()):
+        if not math.isfinite(v) or v < 0.0:
+            raise ValueError(f"rtsds_amd.CrossEntropyLoss: weight[{k}] = {v} is not a finite, non-negative number")
+    return w.to(torch.float32)
+
+
 class CrossEntropyLoss(nn.Module):
-    """Mean over non-ignored pixels of -log softmax(x)[target]; logits [N, C, H, W] (NHWC or
-    NCHW memory), target int64 [N, H, W] (or [N, 1, H, W]).  Under data parallelism the mean
-    runs over every rank's pixels (runtime.dp_world)."""
+    """nn.CrossEntropyLoss(weight, ignore_index), mean reduction; logits [N, C, H, W] (NHWC or
+    NCHW memory), target int64 [N, H, W] (or [N, 1, H, W]).  Unweighted: the mean over non-ignored
+    pixels of -log softmax(x)[target].  ``weight`` (c finite, non-negative numbers: sequence,
+    ndarray or tensor; kept as a float32 buffer, so ``.to(device)`` moves it): sum of
+    w[t] * (-log softmax(x)[t]) over the non-ignored pixels divided by the sum of their w[t].
+    Under data parallelism the mean runs over every rank's pixels (runtime.dp_world): the count --
+    the weight sum of a weighted criterion -- is all-reduced, nothing else."""
 
     def __init__(self, weight=None, ignore_index=-100, reduction="mean"):
         super().__init__()
-        if weight is not None or reduction != "mean":
-            raise NotImplementedError("rtsds_amd.CrossEntropyLoss: unweighted mean only (main.py:130)")
+        if reduction != "mean":
+            raise NotImplementedError("rtsds_amd.CrossEntropyLoss: mean reduction only (main.py:130)")
         self.ignore_index = -100 if ignore_index is None else int(ignore_index)
+        self.register_buffer("weight", None if weight is None else _weight_tensor(weight))
+
+    def set_weight(self, weight):
+        """Install (or, with None, remove) the class weights; the buffer keeps the module's device."""
+        if weight is None:
+            self.weight = None
+            return
+        w = _weight_tensor(weight)
+        dev = next((b.device for b in self.buffers()), None)
+        self.weight = w if dev is None else w.to(dev)
 
     def forward(self, input, target):
-        return F.cross_entropy(input, target, self.ignore_index)
+        w = self.weight
+        if w is not None and w.numel() != input.shape[1]:
+            raise ValueError(f"rtsds_amd.CrossEntropyLoss: {w.numel()} class weights for {input.shape[1]} classes")
+        return F.cross_entropy(input, target, self.ignore_index, w)
+
+
+def class_weights(count, support=None, mode="inverse_log", c=1.02):
+    """Class weights from the exact integer label statistics (functional.label_stats), in float64
+    on the host; returns a float64 ndarray.
+
+    * ``"inverse_log"`` (ENet, Paszke et al. 2016): w_k = 1 / ln(c + p_k), p_k = count_k / sum(count),
+      c = 1.02 (weights in about [1.4, 50]; an absent class gets the largest).
+    * ``"median_frequency"`` (Eigen & Fergus 2015): f_k = count_k / support_k, with support_k the valid
+      pixels of the images that contain class k; w_k = median(f over the present classes) / f_k, and 0
+      for an absent class."""
+    cnt = np.asarray(count, dtype=np.float64)
+    if cnt.ndim != 1 or cnt.size == 0 or (cnt < 0).any():
+        raise ValueError("rtsds_amd.class_weights: count must be a 1-D array of non-negative pixel counts")
+    if cnt.sum() <= 0:
+        raise ValueError("rtsds_amd.class_weights: no labelled pixel")
+    if mode == "inverse_log":
+        return 1.0 / np.log(float(c) + cnt / cnt.sum())
+    if mode == "median_frequency":
+        if support is None:
+            raise ValueError("rtsds_amd.class_weights: median_frequency needs support")
+        sup = np.asarray(support, dtype=np.float64)
+        if sup.shape != cnt.shape:
+            raise ValueError(f"rtsds_amd.class_weights: support has shape {sup.shape}, count {cnt.shape}")
+        present = cnt > 0
+        f = cnt[present] / sup[present]
+        w = np.zeros_like(cnt)
+        w[present] = np.median(f) / f
+        return w
+    raise ValueError(f"rtsds_amd.class_weights: unknown mode {mode!r} (one of {', '.join(WEIGHT_MODES)})")
+
+
+def class_statistics(loader, num_classes, ignore_index, device="cuda"):
+    """One sweep over ``loader`` (batches whose second item is the int64 label map; the images
+    are not touched): (count, support) of functional.label_stats as int64 ndarrays, accumulated on
+    the device and fetched once.  Under data parallelism both are summed over the ranks, so every
+    rank derives the same weights."""
+    count = torch.zeros(int(num_classes), dtype=torch.int64, device=device)
+    support = torch.zeros_like(count)
+    for batch in loader:
+        F.label_stats(batch[1].to(device, non_blocking=True).long(), num_classes, ignore_index, count, support)
+    if dp_world() > 1:
+        import torch.distributed as dist
+        both = torch.stack([count, support])
+        dist.all_reduce(both)
+        count, support = both[0], both[1]
+    return count.cpu().numpy(), support.cpu().numpy()
 
 
 class BCEWithLogitsLoss(nn.Module):

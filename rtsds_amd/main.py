@@ -31,8 +31,30 @@ from .utils import dist_env, forModel
 from .validation import val, val_GTA5
 
 
-def optimzer_loss_loader(model, optimizer_config, loss_config):
-    """main.py:110-136 with the HIP-backed Adam / SGD and losses."""
+def criterion_weight(loss_config, num_classes=None):
+    """The optional ``weight`` key of a CrossEntropy criterion block: None, a list of
+    ``num_classes`` finite non-negative numbers (taken as is), or one of losses.WEIGHT_MODES
+    (computed from the training labels before training: install_class_weights).  Anything else
+    raises at start-up."""
+    w = loss_config.get("weight")
+    if w is None:
+        return None
+    if isinstance(w, str):
+        if w not in losses.WEIGHT_MODES:
+            raise ValueError(f"rtsds_amd: criterion.weight must be a list of class weights or one of "
+                             f"{', '.join(repr(m) for m in losses.WEIGHT_MODES)}, got {w!r}")
+        return w
+    if not isinstance(w, (list, tuple)):
+        raise ValueError(f"rtsds_amd: criterion.weight must be a list of class weights or a mode name, got {w!r}")
+    if num_classes is not None and len(w) != num_classes:
+        raise ValueError(f"rtsds_amd: criterion.weight has {len(w)} entries for {num_classes} classes")
+    return list(w)
+
+
+def optimzer_loss_loader(model, optimizer_config, loss_config, num_classes=None):
+    """main.py:110-136 with the HIP-backed Adam / SGD and losses.  A CrossEntropy criterion takes
+    the list form of ``weight`` directly (moved to the model's device); a mode name is left on the
+    criterion as ``weight_mode`` for install_class_weights."""
     if optimizer_config["name"] == "Adam":
         optimizer = optim.Adam(model.parameters(), lr=optimizer_config["lr"],
                                weight_decay=optimizer_config.get("weight_decay", 0))
@@ -42,7 +64,11 @@ def optimzer_loss_loader(model, optimizer_config, loss_config):
     else:
         raise ValueError("Invalid optimizer name. Please select Adam or SGD")
     if loss_config["name"] == "CrossEntropy":
-        loss = losses.CrossEntropyLoss(ignore_index=loss_config.get("ignore_index"))
+        w = criterion_weight(loss_config, num_classes)
+        loss = losses.CrossEntropyLoss(weight=None if isinstance(w, str) else w, ignore_index=loss_config.get("ignore_index"))
+        loss.weight_mode = w if isinstance(w, str) else None
+        if loss.weight is not None:
+            loss.to(next(model.parameters()).device)
     elif loss_config["name"] == "BCEWithLogits":
         loss = losses.BCEWithLogitsLoss()
     else:
@@ -68,7 +94,8 @@ def model_loader(config, is_adversarial, model_name):
     if is_adversarial:
         adv = model_cfg["adversarial_model"]
         gen = forModel(_generator(model_cfg, adv["generator"]["name"]), config.device)
-        g_opt, g_loss = optimzer_loss_loader(gen, adv["generator"]["optimizer"], adv["generator"]["criterion"])
+        g_opt, g_loss = optimzer_loss_loader(gen, adv["generator"]["optimizer"], adv["generator"]["criterion"],
+                                             model_cfg[adv["generator"]["name"]]["num_classes"])
         g_hp = {"gen_init_lr": adv["generator"]["optimizer"]["lr"], "gen_power": adv["generator"]["power_lr_factor"]}
         dcfg = adv["discriminator"]
         dis = (TinyDomainDiscriminator(num_classes=dcfg["input_channels"]) if dcfg["name"] == "tiny"
@@ -79,8 +106,27 @@ def model_loader(config, is_adversarial, model_name):
         return (gen, g_opt, g_loss, g_hp), (dis, d_opt, d_loss, d_hp)
     cfg = model_cfg["deeplab" if model_name == "deeplab" else "bisenet"]
     model = forModel(_generator(model_cfg, model_name), config.device)
-    opt, loss = optimzer_loss_loader(model, cfg["optimizer"], cfg["criterion"])
+    opt, loss = optimzer_loss_loader(model, cfg["optimizer"], cfg["criterion"], cfg["num_classes"])
     return model, opt, loss, {"init_lr": cfg["optimizer"]["lr"], "power": cfg["power_lr_factor"]}
+
+
+def install_class_weights(criterion, loader, num_classes, class_names, device):
+    """A criterion configured with ``weight: "inverse_log" | "median_frequency"``: one sweep over
+    the (source) training loader's labels on the device (losses.class_statistics, summed over
+    data-parallel ranks), the weights from the exact counts (losses.class_weights), logged beside
+    the class names and installed.  Any other criterion is left alone.  Returns the weights."""
+    mode = getattr(criterion, "weight_mode", None)
+    if mode is None:
+        return None
+    count, support = losses.class_statistics(loader, num_classes, criterion.ignore_index, device)
+    w = losses.class_weights(count, support, mode)
+    names = list(class_names or [])
+    print(f"Class weights ({mode}):")
+    for k in range(num_classes):
+        print(f"  {names[k] if k < len(names) else k}: {w[k]:.4f}  ({int(count[k])} pixels)")
+    criterion.set_weight(w)
+    criterion.to(device)
+    return w
 
 
 class SyntheticLoader:
@@ -398,6 +444,7 @@ def main(argv=None):
     if args.domain_adaptation:
         (g, g_opt, g_loss, g_hp), (d, d_opt, d_loss, d_hp) = model_loader(config, True, args.model)
         t = config.training["domain_adaptation"]
+        install_class_weights(g_loss, gta_dl, t["num_classes"], config.meta["class_names"], config.device)
         adversarial_train(iterations=t["iterations"], epochs=t["epochs"], lambda_=t["lambda"], generator=g,
                           discriminator=d, generator_optimizer=g_opt, discriminator_optimizer=d_opt,
                           generator_loss=g_loss, discriminator_loss=d_loss, source_dataloader=gta_dl,
@@ -418,6 +465,7 @@ def main(argv=None):
             train_dl = gta_dl
         model, opt, crit, hp = model_loader(config, False, args.model)
         t = config.training["segmentation"]
+        install_class_weights(crit, train_dl, t["num_classes"], config.meta["class_names"], config.device)
         max_iter = t["epochs"] * len(train_dl)
         if kd is not None:
             from . import distill

@@ -43,8 +43,8 @@ def _unpack(outputs):
 
 def _fused_heads(model, criterion, inputs):
     """Low-res heads + shared resize geometry when the final resizes can be fused into the
-    cross-entropy (the model exposes forward_lowres, the criterion is the unweighted-mean CE,
-    all heads share one upsample geometry), else None."""
+    cross-entropy (the model exposes forward_lowres, the criterion is the mean CE -- weighted or
+    not: its ``weight`` rides along --, all heads share one upsample geometry), else None."""
     if not (isinstance(criterion, losses.CrossEntropyLoss) and hasattr(model, "forward_lowres")):
         return None
     heads = model.forward_lowres(inputs)
@@ -53,7 +53,7 @@ def _fused_heads(model, criterion, inputs):
         return [F.interpolate_geometry(t, geo) if geo is not None else t for t, geo in heads], None
     geo = geos.pop()
     ts = [t for t, _ in heads]
-    if not F.upsample_cross_entropy_supported(ts, geo, criterion.ignore_index):
+    if not F.upsample_cross_entropy_supported(ts, geo, criterion.ignore_index, criterion.weight):
         return [F.interpolate_geometry(t, geo) for t in ts], None
     return ts, geo
 
@@ -103,7 +103,8 @@ def seg_step(model, criterion, optimizer, inputs, targets):
             outs = _unpack(model(inputs))
     if fused is not None and fused[1] is not None:
         correct = torch.empty(1, dtype=torch.int64, device=fused[0][0].device)  # (overwritten)
-        loss = F.upsample_cross_entropy(fused[0], targets, fused[1], criterion.ignore_index, correct, set_correct=True)
+        loss = F.upsample_cross_entropy(fused[0], targets, fused[1], criterion.ignore_index, correct, set_correct=True,
+                                        weight=criterion.weight)
         _backward(loss, optimizer, cuts)
         optimizer.step()
         return loss.detach(), correct
@@ -172,7 +173,7 @@ def _seg_loss(model, criterion, x, label, correct):
     fused = _fused_heads(model, criterion, x)
     if fused is not None and fused[1] is not None:
         heads, geo = fused
-        loss = F.upsample_cross_entropy(heads, label, geo, criterion.ignore_index, correct)
+        loss = F.upsample_cross_entropy(heads, label, geo, criterion.ignore_index, correct, weight=criterion.weight)
         return loss, heads[0], geo
     if fused is not None:
         outs = fused[0]
