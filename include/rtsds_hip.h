@@ -815,6 +815,45 @@ int rtsds_distill_finish(const void* wsp, size_t ws_bytes, int n, int hs, int ws
 int rtsds_distill_bwd(const void* wsp, size_t ws_bytes, const float* grad_loss, double coef_g, void* dx, int dtype, int n, int hs,
                       int ws, int c, void* stream);
 
+/* ---------------------------------------------------------------- target entropy minimisation
+ * An unsupervised penalty on a low-resolution class map (no reference counterpart): x [n][h][w][c]
+ * dense NHWC, fp32 or bf16, aligned to its element only, 2 <= c <= 32.  Per pixel, with logits z:
+ *   d = z - max z, e = exp d, Z = sum e, p = e / Z, log p = d - log Z
+ *   H = -sum_k p_k log p_k      a term with p_k == 0 counts 0, so a class at -inf gives 0, not NaN
+ *   h = min(H * fp32(1 / ln c), 1)     the normalised entropy, in [0, 1]
+ *   S = sum_k p_k^2
+ *   RTSDS_ENTROPY_ENTROPY      phi = h                     dphi/dz_j = -(1 / ln c) p_j (log p_j + H)
+ *   RTSDS_ENTROPY_ROBUST       phi = (h^2 + 1e-8)^eta      dphi/dz_j = 2 eta h (h^2 + 1e-8)^(eta - 1) * (the line above)
+ *   RTSDS_ENTROPY_MAX_SQUARES  phi = -S / 2                dphi/dz_j = -p_j (p_j - S)
+ * eta == 2 is formed as a product, any other eta with powf; eta is read only by ROBUST.  The
+ * gradient term of a class with p_j == 0 is 0 under every penalty.  The probabilities never reach
+ * memory.
+ * rtsds_entropy_fwd: one launch, a workgroup per 128 consecutive pixels of the flattened [n h w]
+ *   list, two adjacent lanes per pixel (even and odd classes; Z, H and S are the two lanes' sums
+ *   added, a fixed order); workgroup i leaves (sum phi, sum h) of its tile in the workspace and, when want_grad, the
+ *   fp32 term dphi/dz [n][h][w][c] behind the partials (want_grad == 0 writes none).  hmap (or NULL):
+ *   fp32 [n][h][w] that receives h.
+ * rtsds_entropy_finish: *loss = coef * sum phi, *mean_entropy = coef * sum h, both summed in a fixed
+ *   order in fp64: the same bits on every run.  The caller passes coef = 1 / (n h w world).
+ * rtsds_entropy_bwd: dx [n][h][w][c] (dtype) = cast(fp32(*grad_loss * coef_g) * term) from the term
+ *   of a want_grad forward on the same workspace; coef_g = 1 / (n h w world).
+ * None synchronises, allocates, clears memory, uses a float atomic or touches the host.  Before any
+ * HIP call: RTSDS_ERR_SHAPE for a NULL tensor or scalar, a size < 1, c outside [2, 32], 2^31
+ * elements or more, an unknown penalty, an eta or coefficient that is not finite (eta: and
+ * positive); RTSDS_ERR_UNSUPPORTED for another dtype code, a tensor not aligned to its element, a
+ * workspace not 16-B aligned; RTSDS_ERR_WORKSPACE for a NULL or short workspace
+ * (rtsds_entropy_workspace bytes; 0 for a shape it refuses).                                       */
+#define RTSDS_ENTROPY_ENTROPY 0
+#define RTSDS_ENTROPY_ROBUST 1
+#define RTSDS_ENTROPY_MAX_SQUARES 2
+size_t rtsds_entropy_workspace(int n, int h, int w, int c);
+int rtsds_entropy_fwd(const void* x, int dtype, int n, int h, int w, int c, int penalty, float eta, int want_grad, float* hmap,
+                      void* wsp, size_t ws_bytes, void* stream);
+int rtsds_entropy_finish(const void* wsp, size_t ws_bytes, int n, int h, int w, double coef, float* loss, float* mean_entropy,
+                         void* stream);
+int rtsds_entropy_bwd(const void* wsp, size_t ws_bytes, const float* grad_loss, double coef_g, void* dx, int dtype, int n, int h,
+                      int w, int c, void* stream);
+
 /* ---------------------------------------------------------------- graph replay
  * Replaces hipGraphLaunch of a captured multi-stream iteration (runtime.GraphedStep /
  * GraphedForward; the reference has no graphs: its train.py:65-113 / 172-284 loop bodies
@@ -900,7 +939,7 @@ int rtsds_label_stats(const int64_t* label, int n, int h, int w, int c, int igno
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 26
+#define RTSDS_ABI_VERSION 27
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

@@ -9,5 +9,6 @@ torch.distributed (RCCL).
 from .runtime import compute_dtype, precision, set_compute_dtype  # noqa: F401
 from .ema import EMATeacher  # noqa: F401,E402
 from .distill import Distiller  # noqa: F401,E402
+from .entmin import EntropyMinimiser  # noqa: F401,E402
 
-__all__ = ["compute_dtype", "precision", "set_compute_dtype", "EMATeacher", "Distiller"]
+__all__ = ["compute_dtype", "precision", "set_compute_dtype", "EMATeacher", "Distiller", "EntropyMinimiser"]

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSDS_LIB: alternative in-tree build of the same ABI (kernel-variant A/B measurements)
 DEFAULT_LIB_PATH = os.path.join(_HERE, "librtsds_hip.so")
-ABI_VERSION = 26  # include/rtsds_hip.h RTSDS_ABI_VERSION
+ABI_VERSION = 27  # include/rtsds_hip.h RTSDS_ABI_VERSION
 LIB_PATH = os.environ.get("RTSDS_LIB") or DEFAULT_LIB_PATH
 
 F32, BF16 = 0, 1
@@ -187,6 +187,10 @@ SIGNATURES = {
     "rtsds_distill_fwd": (c_int, [P, c_int, P, c_int] + [c_int] * 6 + [c_float, c_float, c_float, c_int, P, P, c_size_t, P]),
     "rtsds_distill_finish": (c_int, [P, c_size_t, c_int, c_int, c_int, c_double, P, P]),
     "rtsds_distill_bwd": (c_int, [P, c_size_t, P, c_double, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "rtsds_entropy_workspace": (c_size_t, [c_int] * 4),
+    "rtsds_entropy_fwd": (c_int, [P, c_int] + [c_int] * 5 + [c_float, c_int, P, P, c_size_t, P]),
+    "rtsds_entropy_finish": (c_int, [P, c_size_t, c_int, c_int, c_int, c_double, P, P, P]),
+    "rtsds_entropy_bwd": (c_int, [P, c_size_t, P, c_double, P, c_int, c_int, c_int, c_int, c_int, P]),
     "rtsds_sgd_step": (c_int, [P, P, P, P, c_long, P, c_float, c_float, c_float, c_float, c_int, c_int,
                                c_float, c_int, P]),
     "rtsds_adam_step": (c_int, [P, P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float,

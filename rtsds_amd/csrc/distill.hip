@@ -4,49 +4,12 @@
 // q - p and the argmax agreement are formed in one pass.  Neither the resampled logits nor the
 // probabilities are written to memory.
 #include "class_row.h"
-#include "ew_common.h"
+#include "row_stage.h"
 
 static const int kKdPix = 128;             // pixels of a tile = threads of a workgroup: one run inside one student row
 static const int kKdCMax = 32;
 static const size_t kKdLdsCap = 64 * 1024;
 static const int kKdRed = 16;              // bytes in front of the tiles: one loss sum per wave
-
-// ------------------------------------------------------------------ 16-B staging of unaligned runs
-// A run of class rows (19 classes: 38 or 76 bytes per pixel) starts anywhere.  Its LDS image keeps
-// the run's offset inside a 16-B chunk (lead, in elements), so every whole chunk of the run moves
-// as one lane-consecutive 16-B access and only the elements before the first and after the last
-// whole chunk move singly.  s is 16-B aligned and holds lead + nel elements.
-template <typename T>
-RT_DEV int kd_lead(const T* g) {
-  return (int)(((uintptr_t)g & 15) / sizeof(T));
-}
-template <typename T, bool IN>
-RT_DEV void kd_move(T* __restrict__ g, T* s, int nel) {
-  constexpr int N = 16 / (int)sizeof(T);
-  const int lead = kd_lead(g);
-  const int head = min(nel, (N - lead) & (N - 1));
-  const int nv = (nel - head) / N, done = head + nv * N;
-  uint4* gv = (uint4*)(g + head);
-  uint4* sv = (uint4*)(s + lead + head);
-  for (int i = threadIdx.x; i < nv; i += blockDim.x) {
-    if constexpr (IN) sv[i] = gv[i];
-    else gv[i] = sv[i];
-  }
-  for (int i = threadIdx.x; i < head + nel - done; i += blockDim.x) {
-    const int j = i < head ? i : done + (i - head);
-    if constexpr (IN) s[lead + j] = g[j];
-    else g[j] = s[lead + j];
-  }
-}
-template <typename T>
-RT_DEV void kd_in(const T* g, T* s, int nel) {
-  kd_move<T, true>(const_cast<T*>(g), s, nel);
-}
-template <typename T>
-RT_DEV void kd_out(T* g, T* s, int nel) {
-  kd_move<T, false>(g, s, nel);
-}
-__host__ __device__ static inline size_t kd_lds_row(size_t nel, size_t elem) { return ((nel + 16 / elem) * elem + 15) & ~(size_t)15; }
 
 // common.h bil_mix with a tap of weight zero left out: for finite taps the same bits (0 * p + 1 * q
 // is q), and a teacher's -inf (a masked class) under a zero weight -- every second tap of equal
@@ -55,31 +18,6 @@ RT_DEV float kd_mix(float p00, float p01, float p10, float p11, float lh0, float
   const float t0 = lw1 == 0.f ? p00 : fmaf(lw1, p01, lw0 * p00);
   const float t1 = lw1 == 0.f ? p10 : fmaf(lw1, p11, lw0 * p10);
   return lh1 == 0.f ? t0 : fmaf(lh1, t1, lh0 * t0);
-}
-
-// ------------------------------------------------------------------ the softened row
-// v = logits * inv_temp in place, then d = v - max(v) in v, e = exp(d), z = sum e (class order),
-// lz = log z: probability k is e[k] / z, its logarithm v[k] - lz.  The student's and the teacher's
-// rows go through this one function, and the products and differences are kept from fusing with
-// their neighbours, so equal rows give equal bits.
-template <int MAXC>
-RT_DEV void kd_soften(float (&v)[MAXC], float (&e)[MAXC], int c, float inv_temp, float& z, float& lz) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < MAXC; ++k)
-    if (k < c) {
-      v[k] = __fmul_rn(v[k], inv_temp);
-      m = fmaxf(m, v[k]);
-    }
-  z = 0.f;
-#pragma unroll
-  for (int k = 0; k < MAXC; ++k)
-    if (k < c) {
-      v[k] = __fsub_rn(v[k], m);
-      e[k] = expf(v[k]);
-      z = __fadd_rn(z, e[k]);
-    }
-  lz = logf(z);
 }
 
 struct KdArgs {
@@ -110,9 +48,9 @@ __global__ void __launch_bounds__(kKdPix) kd_fwd_kernel(KdArgs a) {
   float* red = stage_buf<float>();
   char* lds = (char*)red + kKdRed;
   Ts* sbuf = (Ts*)lds;
-  float* rbuf = (float*)(lds + kd_lds_row((size_t)kKdPix * c, sizeof(Ts)));
-  Tt* tbuf0 = (Tt*)((char*)rbuf + kd_lds_row((size_t)kKdPix * c, sizeof(float)));
-  Tt* tbuf1 = (Tt*)((char*)tbuf0 + kd_lds_row((size_t)a.cap * c, sizeof(Tt)));
+  float* rbuf = (float*)(lds + rs_lds_row((size_t)kKdPix * c, sizeof(Ts)));
+  Tt* tbuf0 = (Tt*)((char*)rbuf + rs_lds_row((size_t)kKdPix * c, sizeof(float)));
+  Tt* tbuf1 = (Tt*)((char*)tbuf0 + rs_lds_row((size_t)a.cap * c, sizeof(Tt)));
 
   int ih0, ih1, c0, c1, unused;
   float lh0, lh1, lu0, lu1;
@@ -125,13 +63,13 @@ __global__ void __launch_bounds__(kKdPix) kd_fwd_kernel(KdArgs a) {
   const Ts* sg = (const Ts*)a.s + ((long)row * a.ws + x0) * c;
   const Tt* tg0 = (const Tt*)a.t + (((long)img * a.ht + ih0) * a.wt) * c;  // the source rows, column 0
   const Tt* tg1 = (const Tt*)a.t + (((long)img * a.ht + ih1) * a.wt) * c;
-  kd_in(sg, sbuf, np * c);
+  rs_in(sg, sbuf, np * c);
   if (staged) {
-    kd_in(tg0 + (long)c0 * c, tbuf0, nsp * c);
-    kd_in(tg1 + (long)c0 * c, tbuf1, nsp * c);
+    rs_in(tg0 + (long)c0 * c, tbuf0, nsp * c);
+    rs_in(tg1 + (long)c0 * c, tbuf1, nsp * c);
   }
   float* rg = a.resid + ((long)row * a.ws + x0) * c;
-  const int rlead = kd_lead(rg);
+  const int rlead = rs_lead(rg);
   __syncthreads();
 
   float kl = 0.f;
@@ -140,7 +78,7 @@ __global__ void __launch_bounds__(kKdPix) kd_fwd_kernel(KdArgs a) {
     int iw0, iw1;
     float lw0, lw1;
     bil_src(x0 + tid, a.sw, a.wt, iw0, iw1, lw0, lw1);
-    const Ts* sp = sbuf + kd_lead(sg) + tid * c;
+    const Ts* sp = sbuf + rs_lead(sg) + tid * c;
     float va[MAXC], vb[MAXC], ea[MAXC], eb[MAXC];
     // r0 / r1: the two source rows at column `first`, in LDS or in memory
     auto rows = [&](const Tt* r0, const Tt* r1, int first) {
@@ -150,7 +88,7 @@ __global__ void __launch_bounds__(kKdPix) kd_fwd_kernel(KdArgs a) {
       for (int k = 0; k < MAXC; ++k)
         if (k < c) vb[k] = kd_mix(to_f(p00[k]), to_f(p01[k]), to_f(p10[k]), to_f(p11[k]), lh0, lh1, lw0, lw1);
     };
-    if (staged) rows(tbuf0 + kd_lead(tg0 + (long)c0 * c), tbuf1 + kd_lead(tg1 + (long)c0 * c), c0);
+    if (staged) rows(tbuf0 + rs_lead(tg0 + (long)c0 * c), tbuf1 + rs_lead(tg1 + (long)c0 * c), c0);
     else rows(tg0, tg1, 0);
 #pragma unroll
     for (int k = 0; k < MAXC; ++k)
@@ -158,8 +96,8 @@ __global__ void __launch_bounds__(kKdPix) kd_fwd_kernel(KdArgs a) {
     float best;
     same = first_max<MAXC>([&](int k) { return va[k]; }, c, best) == first_max<MAXC>([&](int k) { return vb[k]; }, c, best);
     float za, lza, zb, lzb;
-    kd_soften<MAXC>(va, ea, c, a.inv_temp, za, lza);
-    kd_soften<MAXC>(vb, eb, c, a.inv_temp, zb, lzb);
+    rs_soften<MAXC>(va, ea, c, a.inv_temp, za, lza);
+    rs_soften<MAXC>(vb, eb, c, a.inv_temp, zb, lzb);
     float* rp = rbuf + rlead + tid * c;
 #pragma unroll
     for (int k = 0; k < MAXC; ++k)
@@ -179,45 +117,7 @@ __global__ void __launch_bounds__(kKdPix) kd_fwd_kernel(KdArgs a) {
   }
   __syncthreads();  // also: the residual tile is complete
   if (tid == 0) a.part[blockIdx.x] = red[0] + red[1];
-  if (a.want_grad) kd_out(rg, rbuf, np * c);
-}
-
-// loss = coef * (the partials' sum): each thread adds every 256th partial, the 256 sums meet in a
-// fixed tree, all in fp64 -- the same bits on every run.
-__global__ void __launch_bounds__(256) kd_finish_kernel(const float* __restrict__ part, int nparts, double coef, float* loss) {
-  __shared__ double red[256];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 256) acc += (double)part[i];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *loss = (float)(coef * red[0]);
-}
-
-// dx = cast(scale * resid), scale = fp32(g * coef_g).  A thread owns one 16-B chunk of dx (chunks
-// counted from dx's own 16-B boundaries); a chunk cut by either end of the tensor is stored singly.
-template <typename T>
-__global__ void __launch_bounds__(256) kd_bwd_kernel(const float* __restrict__ resid, const float* __restrict__ g, double coef_g,
-                                                     T* __restrict__ dx, long total) {
-  constexpr int N = VecT<T>::N;
-  const int lead = kd_lead(dx);
-  const float scale = (float)((double)*g * coef_g);
-  const long chunks = (total + lead + N - 1) / N;
-  GRID_STRIDE(j, chunks) {
-    const long e0 = j * N - lead;
-    if (e0 >= 0 && e0 + N <= total) {
-      typename VecT<T>::v16 v;
-#pragma unroll
-      for (int i = 0; i < N; ++i) v[i] = from_f<T>(scale * resid[e0 + i]);
-      *(typename VecT<T>::v16*)(dx + e0) = v;
-    } else {
-      for (int i = 0; i < N; ++i)
-        if (e0 + i >= 0 && e0 + i < total) dx[e0 + i] = from_f<T>(scale * resid[e0 + i]);
-    }
-  }
+  if (a.want_grad) rs_out(rg, rbuf, np * c);
 }
 
 // ------------------------------------------------------------------ host
@@ -241,13 +141,13 @@ static KdPlan kd_plan(int n, int hs, int ws, int c, int wt, float scale_w, size_
   p.blocks = n * hs * p.tiles_x;
   p.part_bytes = ((size_t)p.blocks * sizeof(float) + 15) & ~(size_t)15;
   p.resid_bytes = (size_t)n * hs * ws * c * sizeof(float);
-  const size_t own = kKdRed + kd_lds_row((size_t)kKdPix * c, s_elem) + kd_lds_row((size_t)kKdPix * c, sizeof(float));
+  const size_t own = kKdRed + rs_lds_row((size_t)kKdPix * c, s_elem) + rs_lds_row((size_t)kKdPix * c, sizeof(float));
   const double span = std::ceil((double)scale_w * (std::min(ws, kKdPix) - 1)) + 4.0;
   p.cap = (int)std::min<double>(wt, span);
-  p.lds = own + 2 * kd_lds_row((size_t)p.cap * c, t_elem);
+  p.lds = own + 2 * rs_lds_row((size_t)p.cap * c, t_elem);
   if (p.lds > kKdLdsCap) {
     p.cap = 0;
-    p.lds = own + 2 * kd_lds_row(0, t_elem);
+    p.lds = own + 2 * rs_lds_row(0, t_elem);
   }
   return p;
 }
@@ -302,7 +202,7 @@ extern "C" int rtsds_distill_finish(const void* wsp, size_t ws_bytes, int n, int
   if ((uintptr_t)wsp & 15) return RTSDS_ERR_UNSUPPORTED;
   const int blocks = n * hs * rt_cdiv(ws, kKdPix);
   if (!wsp || ws_bytes < (size_t)blocks * sizeof(float)) return RTSDS_ERR_WORKSPACE;
-  hipLaunchKernelGGL(kd_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)wsp, blocks, coef, loss);
+  hipLaunchKernelGGL(rs_finish_kernel<1>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)wsp, blocks, coef, RsOuts<1>{{loss}});
   RET_LAUNCH();
 }
 
@@ -316,7 +216,7 @@ extern "C" int rtsds_distill_bwd(const void* wsp, size_t ws_bytes, const float* 
   const float* resid = (const float*)((const char*)wsp + p.part_bytes);
   const long total = (long)n * hs * ws * c;
   hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(kd_bwd_kernel<T>, dim3(ew_blocks(total / VecT<T>::N + 2)), dim3(256), 0, st, resid, grad_loss,
+  DISPATCH_T(dtype, hipLaunchKernelGGL(rs_bwd_kernel<T>, dim3(ew_blocks(total / VecT<T>::N + 2)), dim3(256), 0, st, resid, grad_loss,
                                        coef_g, (T*)dx, total));
   RET_LAUNCH();
 }

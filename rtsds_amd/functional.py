@@ -1993,6 +1993,84 @@ def distill_kl(student_low, teacher_low, temperature=1.0, agree=None):
     return DistillKLFn.apply(student_low, teacher_low.detach(), temperature, agree, nbytes)
 
 
+ENTROPY_PENALTIES = {"entropy": 0, "robust": 1, "max_squares": 2}  # include/rtsds_hip.h RTSDS_ENTROPY_*
+
+
+class EntropyLossFn(torch.autograd.Function):
+    """entropy_loss: rtsds_entropy_fwd + rtsds_entropy_finish, backward rtsds_entropy_bwd from the
+    gradient term the forward left in its workspace.  Returns (loss, mean_entropy); the second
+    carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, penalty, eta, hmap, nbytes):
+        x = nhwc(x)
+        n, c, h, w = x.shape
+        buf = workspace(nbytes, x.device)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        ment = torch.empty((), dtype=torch.float32, device=x.device)
+        want = bool(ctx.needs_input_grad[0])
+        coef = 1.0 / float(n * h * w * dp_world())
+        lib.rtsds_entropy_fwd(_P(x), dcode(x), n, h, w, c, penalty, eta, int(want), _P(hmap), _P(buf), buf.numel(), stream())
+        lib.rtsds_entropy_finish(_P(buf), buf.numel(), n, h, w, coef, _P(loss), _P(ment), stream())
+        if want:
+            ctx.buf, ctx.coef_g, ctx.geo, ctx.dtype = buf, coef, (n, c, h, w), x.dtype
+        ctx.mark_non_differentiable(ment)
+        return loss, ment
+
+    @staticmethod
+    def backward(ctx, g, _):
+        n, c, h, w = ctx.geo
+        dx = empty_nhwc(n, c, h, w, ctx.dtype, ctx.buf.device)
+        g = g.contiguous().float()
+        lib.rtsds_entropy_bwd(_P(ctx.buf), ctx.buf.numel(), _P(g), ctx.coef_g, _P(dx), dcode(dx), n, h, w, c, stream())
+        return dx, None, None, None, None
+
+
+def entropy_loss(low, penalty="entropy", eta=2.0, entropy_map=None):
+    """Entropy minimisation on a low-resolution class map, in one fused pass (csrc/entropy.hip):
+    the direct unsupervised loss on a target prediction.  The reference has none; the protocol is this:
+
+    * ``low`` [n, c, h, w] is the model's main head before its final resize (forward_lowres(x,
+      main_only=True)), fp32 or bf16, NHWC or NCHW memory, 2 <= c <= 32.  The loss lives on that
+      grid, where the head's own gradient does: no bilinear adjoint, and 64x fewer pixels than at
+      the label size.
+    * Per pixel, with logits z: d = z - max z, e = exp d, Z = sum e (a fixed order), p = e / Z,
+      log p = d - log Z; H = -sum_k p_k log p_k, a term with p_k == 0 counting 0 (torch's xlogy
+      rule: a masked class at -inf gives 0, not NaN); h = H / ln c in [0, 1]; S = sum_k p_k^2.
+    * ``penalty``: ``"entropy"`` (ADVENT MinEnt, Vu et al. 2019) phi = h, dphi/dz_j =
+      -(1 / ln c) p_j (log p_j + H); ``"robust"`` (FDA, Yang & Soatto 2020) phi = (h^2 + 1e-8)^eta,
+      dphi/dz_j = 2 eta h (h^2 + 1e-8)^(eta - 1) times the former, eta > 0 (eta == 2 is formed as a
+      product, any other with powf); ``"max_squares"`` (Chen et al. 2019) phi = -S / 2, dphi/dz_j =
+      -p_j (p_j - S).  The gradient term of a class with p_j == 0 is 0.
+    * loss = sum_pixels phi / (n h w world), dloss/dz = g dphi/dz / (n h w world); ``world`` is
+      runtime.dp_world(): the ranks' losses and gradients sum to the global batch's, assuming equal
+      shards (distill_kl's and BCE's rule).
+    * Returns (loss, mean_entropy), both 0-dim fp32: ``loss`` carries the gradient, ``mean_entropy``
+      = sum_pixels h / (n h w world) is for logs and carries none, whatever the penalty.
+    * ``entropy_map``: an optional contiguous fp32 [n, h, w] device tensor that receives h per pixel.
+    * Two runs give the same bits; no host sync, no memset (graph-capture safe)."""
+    require_hip(low, entropy_map)
+    if low.dim() != 4:
+        raise RuntimeError("rtsds_amd.entropy_loss: the class map must be [n, c, h, w]")
+    if not 2 <= low.shape[1] <= 32:
+        raise RuntimeError(f"rtsds_amd.entropy_loss: the class count must lie in [2, 32], got {low.shape[1]}")
+    if penalty not in ENTROPY_PENALTIES:
+        raise RuntimeError(f"rtsds_amd.entropy_loss: penalty must be one of {', '.join(repr(p) for p in ENTROPY_PENALTIES)}, "
+                           f"got {penalty!r}")
+    eta = float(eta)
+    if not (eta > 0.0 and np.isfinite(eta)):
+        raise RuntimeError(f"rtsds_amd.entropy_loss: eta must be positive, got {eta}")
+    dcode(low)
+    n, c, h, w = low.shape
+    if entropy_map is not None and (entropy_map.dtype != torch.float32 or tuple(entropy_map.shape) != (n, h, w)
+                                    or not entropy_map.is_contiguous()):
+        raise RuntimeError(f"rtsds_amd.entropy_loss: entropy_map must be a contiguous fp32 tensor of shape {(n, h, w)}")
+    nbytes = lib.rtsds_entropy_workspace(n, h, w, c)
+    if not nbytes:
+        raise RuntimeError("rtsds_amd.entropy_loss: the kernel does not cover these sizes")
+    return EntropyLossFn.apply(low, ENTROPY_PENALTIES[penalty], float(np.float32(eta)), entropy_map, nbytes)
+
+
 class UpsampleSoftmaxFn(torch.autograd.Function):
     """softmax(interpolate_bilinear(x, geo), dim=1) in one pass (rtsds_upsoftmax_fwd), written
     zero-padded to 32 channels so the discriminator's first conv reads it directly

@@ -164,3 +164,26 @@ class DistillationLoss(nn.Module):
 
     def forward(self, student_low, teacher_low, agree=None):
         return F.distill_kl(student_low, teacher_low, self.temperature, agree)
+
+
+class EntropyLoss(nn.Module):
+    """Entropy minimisation on a low-resolution head [N, C, h, w] (functional.entropy_loss, which
+    states the whole protocol): the mean over the pixels of ``penalty`` -- ``"entropy"`` the
+    normalised Shannon entropy h of the softmax (ADVENT MinEnt), ``"robust"`` (h^2 + 1e-8)^eta
+    (FDA), ``"max_squares"`` minus half the sum of the squared probabilities (Maximum Squares).
+    The reference has no counterpart.  ``last_entropy``: the mean normalised entropy of the last
+    forward, a 0-dim device tensor without gradient.  Under data parallelism the mean runs over
+    world * local pixels (equal shards)."""
+
+    def __init__(self, penalty="entropy", eta=2.0):
+        super().__init__()
+        if penalty not in F.ENTROPY_PENALTIES:
+            raise ValueError(f"rtsds_amd.EntropyLoss: penalty must be one of {', '.join(F.ENTROPY_PENALTIES)}, got {penalty!r}")
+        if not float(eta) > 0.0:
+            raise ValueError(f"rtsds_amd.EntropyLoss: eta must be positive, got {eta}")
+        self.penalty, self.eta = penalty, float(eta)
+        self.last_entropy = None
+
+    def forward(self, low):
+        loss, self.last_entropy = F.entropy_loss(low, self.penalty, self.eta)
+        return loss

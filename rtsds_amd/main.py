@@ -3,7 +3,7 @@ config.yaml, factories main.py:110-231, dispatch main.py:272-374) on the HIP pat
 
     python -m rtsds_amd.main [--config rtsds_amd/config.yaml] [--domain_adaptation]
                              [--model bisenet|deeplab] [--dataset cityscapes|gta5] [--seed 42]
-                             [--self_training] [--distill]
+                             [--self_training] [--distill] [--entropy_min]
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m rtsds_amd.main --domain_adaptation
 
 Datasets (main.py:46-108): when the configured directories exist, the reference's readers
@@ -12,6 +12,10 @@ resize, normalize, augmentation, label clamp as HIP kernels); otherwise syntheti
 the configured shapes are used (ImageNet-normalised 0-255 images, labels 0..19 with
 19 = ignore), sharded per rank.  Deviations from the reference (documented in DESIGN.md): DA accepts a
 DeepLab generator; validation accepts class_names / detailed_report.
+
+--entropy_min (with --dataset gta5; config block training.entropy_minimisation, rtsds_amd/entmin.py):
+the segmentation branch trains on labelled GTA5 batches and adds an unsupervised entropy penalty on
+unlabelled Cityscapes train batches -- ADVENT's MinEnt, FDA's robust entropy or Maximum Squares.
 """
 import argparse
 import os
@@ -22,6 +26,7 @@ import torch
 import yaml
 
 from . import losses, optim
+from .functional import ENTROPY_PENALTIES
 from .models.bisenet import build_bisenet
 from .models.deeplabv2 import deeplabv2
 from .models.domain_shift.adversarial.model import DomainDiscriminator, TinyDomainDiscriminator
@@ -328,6 +333,29 @@ def build_distiller(config, kd):
     return Distiller(teacher, temperature=kd["temperature"], weight=kd["weight"])
 
 
+ENTROPY_MINIMISATION_KEYS = ("penalty", "weight", "eta")
+
+
+def entropy_minimisation_config(config):
+    """The training.entropy_minimisation block (commented out in the shipped config.yaml), complete."""
+    em = config.training.get("entropy_minimisation")
+    if em is None:
+        raise RuntimeError("rtsds_amd: --entropy_min needs the config block training.entropy_minimisation "
+                           f"(keys: {', '.join(ENTROPY_MINIMISATION_KEYS)}); config.yaml ships it commented out")
+    missing = [k for k in ENTROPY_MINIMISATION_KEYS if k not in em]
+    if missing:
+        raise RuntimeError(f"rtsds_amd: training.entropy_minimisation lacks {', '.join(missing)}")
+    if em["penalty"] not in ENTROPY_PENALTIES:
+        raise RuntimeError(f"rtsds_amd: training.entropy_minimisation.penalty must be one of "
+                           f"{', '.join(repr(p) for p in ENTROPY_PENALTIES)}, got {em['penalty']!r}")
+    for k, ok in (("eta", lambda v: v > 0), ("weight", lambda v: v >= 0)):
+        v = em[k]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v) or not ok(v):
+            raise RuntimeError(f"rtsds_amd: training.entropy_minimisation.{k} must be a "
+                               f"{'positive' if k == 'eta' else 'non-negative'} number, got {v!r}")
+    return em
+
+
 def self_train_online(config, st, model, optimizer, criterion, init_lr, power, lr_decay_iter, target_dl, validate,
                       callbacks, source_dl, model_name):
     """Online (mean-teacher) self-training, ``mode: online``: a second model of the branch's
@@ -413,6 +441,9 @@ def argumnet_parser(argv=None):
     p.add_argument("--distill", action="store_true",
                    help="segmentation branch only: add a frozen teacher's soft targets to the loss "
                         "(config block training.distillation)")
+    p.add_argument("--entropy_min", action="store_true",
+                   help="segmentation branch only, with --dataset gta5: add an entropy penalty on unlabelled "
+                        "Cityscapes batches to the loss (config block training.entropy_minimisation)")
     return p.parse_args(argv)
 
 
@@ -437,7 +468,15 @@ def main(argv=None):
     st = self_training_config(config) if args.self_training else None
     if args.distill and args.domain_adaptation:
         raise RuntimeError("rtsds_amd: --distill applies to the segmentation branch only, not with --domain_adaptation")
+    if args.entropy_min and args.domain_adaptation:
+        raise RuntimeError("rtsds_amd: --entropy_min applies to the segmentation branch only, not with --domain_adaptation")
+    if args.entropy_min and args.distill:
+        raise RuntimeError("rtsds_amd: --entropy_min and --distill are separate loops; give one of them")
+    if args.entropy_min and args.dataset != "gta5":
+        raise RuntimeError("rtsds_amd: --entropy_min needs --dataset gta5: the labelled source is GTA5 and the target is "
+                           "the Cityscapes train set (else source and target would be the same set)")
     kd = distillation_config(config) if args.distill else None
+    em =entropy_minimisation_config(config) if args.entropy_min else None
     train_dl, val_dl, gta_dl = datasets_loader(config, args.augmented)
     target_dl = train_dl
     callbacks = []
@@ -470,8 +509,16 @@ def main(argv=None):
         if kd is not None:
             from . import distill
             distiller = build_distiller(config, kd)
+        if em is not None:
+            from . import entmin
+            minimiser = entmin.EntropyMinimiser(penalty=em["penalty"], eta=em["eta"], weight=em["weight"])
         for epoch in range(t["epochs"]):
-            if kd is not None:
+            if em is not None:
+                entmin.train(model=model, optimizer=opt, criterion=crit, train_loader=train_dl, epoch=epoch,
+                             init_lr=hp["init_lr"], lr_decay_iter=t["lr_decay_iter"], power=hp["power"],
+                             max_iter=max_iter, callbacks=callbacks, device=config.device, target_loader=target_dl,
+                             minimiser=minimiser)
+            elif kd is not None:
                 distill.train(model=model, optimizer=opt, criterion=crit, train_loader=train_dl, epoch=epoch,
                               init_lr=hp["init_lr"], lr_decay_iter=t["lr_decay_iter"], power=hp["power"],
                               max_iter=max_iter, callbacks=callbacks, device=config.device, distiller=distiller)
