@@ -13,6 +13,11 @@ a multiple of it, else 1; tpr = min(ceil(c / VEC), 256) threads per row, rpi = 2
 per block iteration; need = ceil(rows / rpi); backward row blocks rb = min(need, 512,
 ceil(need / 8)); rb == 1 takes the one-launch kernel, whose statistics stay in registers when
 rows <= 2 * rpi).
+
+The same cases are compared with a float64 statement of each operation: host_inputs builds the inputs
+without a device, run_case_outputs hands back what the launches of run_case wrote (same order of
+allocations and launches, same sentinel check), tests/bn_route_ref.py states what that must be and
+tests/test_bn_route_ref_gpu.py compares the two.
 """
 import hashlib
 
@@ -123,14 +128,20 @@ class _Outputs:
     def view(self, name):
         return self.items[name][1]
 
-    def digests(self):
+    def host(self):
+        """{output name: its elements on the host}, after the sentinel check."""
         torch.cuda.synchronize()
         out = {}
         for name, (arena, view, sent) in self.items.items():
             host = arena.cpu()
             guard = torch.cat([host[:LEAD], host[LEAD + view.numel():]])
             assert torch.equal(guard, torch.full_like(guard, sent)), f"{name}: store outside the output"
-            body = host[LEAD:LEAD + view.numel()].contiguous()
+            out[name] = host[LEAD:LEAD + view.numel()].contiguous()
+        return out
+
+    def digests(self):
+        out = {}
+        for name, body in self.host().items():
             assert not body.is_floating_point() or torch.isfinite(body.float()).all(), f"{name}: not finite"
             out[name] = hashlib.sha256(body.view(torch.uint8).numpy().tobytes()).hexdigest()
         return out
@@ -147,18 +158,18 @@ def _params(c):
     return gamma, beta, mean, invstd, rmean, rvar
 
 
-def _x(n, dt):
-    return _dev(50 + pattern(n, 1), _tdt(dt))  # large mean: the shifted sums matter
+def _x(n):
+    return 50 + pattern(n, 1)  # large mean: the shifted sums matter
 
 
-def _y(n, dt, act):
+def _y(n, act):
     """A stored output as the activation would have left it (the backward's mask source)."""
     v = pattern(n, 3)
     if act == RELU:
         v = np.maximum(v, 0)
     elif act == SIGMOID:
         v = (v + 8) / 16
-    return _dev(v, _tdt(dt))
+    return v
 
 
 def _ws(lib, rows, c):
@@ -191,22 +202,32 @@ def _fwd_stats(rows, c, nrb):
     st[:, :, 0] = cnt[None, :]
     st[:, :, 1] = 50 + pattern(c * nrb, 21).reshape(c, nrb) / 8
     st[:, :, 2] = cnt[None, :] * (1 + (pattern(c * nrb, 22).reshape(c, nrb) + 8) / 8)
-    return _dev(st)
+    return st
 
 
-def _run_fwd(lib, k):
-    rows, c, dt = k["rows"], k["c"], k["dt"]
+def _in_fwd(k):
+    rows, c = k["rows"], k["c"]
     gamma, beta, _, _, rmean, rvar = _params(c)
-    x = _x(rows * c, dt)
-    res = _dev(pattern(rows * c, 2), _tdt(dt)) if k["res"] else None
-    g, b = _dev(gamma), _dev(beta)
-    stats = _fwd_stats(rows, c, k["nrb"]) if k["nrb"] else None
+    return dict(x=_x(rows * c), res=pattern(rows * c, 2) if k["res"] else None, gamma=gamma, beta=beta, rmean=rmean, rvar=rvar,
+                stats=_fwd_stats(rows, c, k["nrb"]) if k["nrb"] else None)
+
+
+def _opt(v, dtype=torch.float32):
+    return None if v is None else _dev(v, dtype)
+
+
+def _launch_fwd(lib, k, h):
+    rows, c, dt = k["rows"], k["c"], k["dt"]
+    x = _dev(h["x"], _tdt(dt))
+    res = _opt(h["res"], _tdt(dt))
+    g, b = _dev(h["gamma"]), _dev(h["beta"])
+    stats = _opt(h["stats"])
     out = _Outputs()
-    y, sm, si, rm, rv, nbt = _fwd_outputs(out, rows * c, c, dt, rmean, rvar)
+    y, sm, si, rm, rv, nbt = _fwd_outputs(out, rows * c, c, dt, h["rmean"], h["rvar"])
     ws = _ws(lib, rows, c)
     lib.rtsds_bn_fwd_ld(_P(x), _P(res), y, c, rows, c, _P(g), _P(b), rm, rv, nbt, sm, si, MOMENTUM, EPS, k["training"],
                         k["act"], _P(stats), k["nrb"], dt, _P(ws), ws.numel(), _stream())
-    return out.digests()
+    return out, ()
 
 
 def _bwd_outputs(out, n, c, dt, dx, dres, acc):
@@ -215,57 +236,99 @@ def _bwd_outputs(out, n, c, dt, dx, dres, acc):
             out.add("dbeta", c, torch.float32, pattern(c, 32) if acc else None))
 
 
-def _run_bwd(lib, k):
-    rows, c, dt = k["rows"], k["c"], k["dt"]
+def _in_bwd(k):
+    rows, c = k["rows"], k["c"]
     gamma, beta, mean, invstd, _, _ = _params(c)
-    x, dy = _x(rows * c, dt), _dev(pattern(rows * c, 4) / 4, _tdt(dt))
-    y = _y(rows * c, dt, k["act"]) if k["y"] else None
-    g, b, sm, si = _dev(gamma), _dev(beta), _dev(mean), _dev(invstd)
+    h = dict(x=_x(rows * c), dy=pattern(rows * c, 4) / 4, y=_y(rows * c, k["act"]) if k.get("y") else None, gamma=gamma,
+             beta=beta, mean=mean, invstd=invstd)
+    if k["acc"]:
+        h.update(dgamma0=pattern(c, 31), dbeta0=pattern(c, 32))
+    if k["kind"] == "part":
+        h["part"] = pattern(c * k["nrb"] * 2, 23)  # [c][nrb][sum g, sum g (x - mean)]
+    return h
+
+
+def _launch_bwd(lib, k, h):
+    rows, c, dt = k["rows"], k["c"], k["dt"]
+    x, dy = _dev(h["x"], _tdt(dt)), _dev(h["dy"], _tdt(dt))
+    y = _opt(h["y"], _tdt(dt))
+    g, b, sm, si = _dev(h["gamma"]), _dev(h["beta"]), _dev(h["mean"]), _dev(h["invstd"])
     out = _Outputs()
     dx, dres, dg, db = _bwd_outputs(out, rows * c, c, dt, k["dx"], k["dres"], k["acc"])
     ws = _ws(lib, rows, c)
     lib.rtsds_bn_bwd_ld(_P(dy), c, _P(x), _P(y), dx, dres, dg, db, rows, c, _P(g), _P(b), _P(sm), _P(si), k["training"],
                         k["act"], k["acc"], dt, _P(ws), ws.numel(), _stream())
-    return out.digests()
+    return out, ()
 
 
-def _run_part(lib, k):
+def _launch_part(lib, k, h):
     rows, c, dt, nrb = k["rows"], k["c"], k["dt"], k["nrb"]
-    gamma, beta, mean, invstd, _, _ = _params(c)
-    x, dy = _x(rows * c, dt), _dev(pattern(rows * c, 4) / 4, _tdt(dt))
-    g, b, sm, si = _dev(gamma), _dev(beta), _dev(mean), _dev(invstd)
-    part = _dev(pattern(c * nrb * 2, 23))  # [c][nrb][sum g, sum g (x - mean)]
+    x, dy = _dev(h["x"], _tdt(dt)), _dev(h["dy"], _tdt(dt))
+    g, b, sm, si = _dev(h["gamma"]), _dev(h["beta"]), _dev(h["mean"]), _dev(h["invstd"])
+    part = _dev(h["part"])
     out = _Outputs()
     dx, _, dg, db = _bwd_outputs(out, rows * c, c, dt, True, False, k["acc"])
     ws = _ws(lib, rows, c)
     lib.rtsds_bn_bwd_part(_P(dy), _P(x), dx, dg, db, rows, c, _P(g), _P(b), _P(sm), _P(si), 1, k["act"], k["acc"],
                           _P(part), nrb, dt, _P(ws), ws.numel(), _stream())
-    return out.digests()
+    return out, ()
 
 
-def _run_pool(lib, k):
+def pool_geo(k):
+    """(ho, wo, rows, pooled elements) of a pool case."""
     n, h, w, c, p = k["n"], k["h"], k["w"], k["c"], k["p"]
     ho, wo = (h + 2 * p - 3) // 2 + 1, (w + 2 * p - 3) // 2 + 1
-    rows, npool = n * h * w, n * ho * wo * c
+    return ho, wo, n * h * w, n * ho * wo * c
+
+
+def _in_pool(k):
+    c = k["c"]
+    _, _, rows, npool = pool_geo(k)
     gamma, beta, mean, invstd, rmean, rvar = _params(c)
-    x = _x(rows * c, BF16)
-    g, b = _dev(gamma), _dev(beta)
+    return dict(x=_x(rows * c), gamma=gamma, beta=beta, mean=mean, invstd=invstd, rmean=rmean, rvar=rvar,
+                dyp=pattern(npool, 4) / 4)
+
+
+def _launch_pool(lib, k, hin):
+    n, h, w, c, p = k["n"], k["h"], k["w"], k["c"], k["p"]
+    ho, wo, rows, npool = pool_geo(k)
+    x = _dev(hin["x"], torch.bfloat16)
+    g, b = _dev(hin["gamma"]), _dev(hin["beta"])
     out = _Outputs()
-    y, sm, si, rm, rv, nbt = _fwd_outputs(out, npool, c, BF16, rmean, rvar)
+    y, sm, si, rm, rv, nbt = _fwd_outputs(out, npool, c, BF16, hin["rmean"], hin["rvar"])
     idx = out.add("idx", npool, torch.uint8)
     ws = _ws(lib, rows, c)
     lib.rtsds_bn_relu_maxpool_fwd(_P(x), y, idx, n, h, w, c, ho, wo, p, _P(g), _P(b), rm, rv, nbt, sm, si, MOMENTUM, EPS,
                                   1, None, 0, BF16, _P(ws), ws.numel(), _stream())
     # the backward gathers through the forward's argmax bytes; statistics as given
-    dyp = _dev(pattern(npool, 4) / 4, torch.bfloat16)
-    smg, sig = _dev(mean), _dev(invstd)
+    dyp = _dev(hin["dyp"], torch.bfloat16)
+    smg, sig = _dev(hin["mean"]), _dev(hin["invstd"])
     dx, _, dg, db = _bwd_outputs(out, rows * c, c, BF16, True, False, 0)
     lib.rtsds_bn_relu_maxpool_bwd(_P(dyp), idx, _P(x), dx, dg, db, n, h, w, c, ho, wo, p, _P(g), _P(b), _P(smg), _P(sig),
                                   1, 0, BF16, _P(ws), ws.numel(), _stream())
-    return out.digests()
+    return out, ()
+
+
+_INPUTS = {"fwd": _in_fwd, "bwd": _in_bwd, "part": _in_bwd, "pool": _in_pool}
+_LAUNCH = {"fwd": _launch_fwd, "bwd": _launch_bwd, "part": _launch_part, "pool": _launch_pool}
+
+
+def host_inputs(case):
+    """The host inputs of one case as numpy arrays (fp32 values; a bf16 case rounds them on the way to the
+    device), by name.  No device, no library: the references and the tolerance recorder use them too."""
+    return _INPUTS[case["kind"]](case)
 
 
 def run_case(case):
     """{output name: SHA-256 of its bytes} of one case; asserts the sentinels around every output."""
     from rtsds_amd._lib import lib
-    return {"fwd": _run_fwd, "bwd": _run_bwd, "part": _run_part, "pool": _run_pool}[case["kind"]](lib, case)
+    return _LAUNCH[case["kind"]](lib, case, host_inputs(case))[0].digests()
+
+
+def run_case_outputs(case):
+    """(host inputs, {output name: host tensor}, return codes) of one case, the same launches as run_case;
+    asserts the sentinels around every output.  tests/bn_route_ref.py states what the outputs must be."""
+    from rtsds_amd._lib import lib
+    h = host_inputs(case)
+    out, rcs = _LAUNCH[case["kind"]](lib, case, h)
+    return h, out.host(), rcs

@@ -15,6 +15,11 @@ the output pitch is c); nchw has sc = hw, shw = 1; slice reads c channels at off
 (1024; 4096 for argmax): the large c = 3 cases are one tile / one pixel group of 44 past that.
 The cross-entropy workspace and the losses are pinned as raw 32-bit words: the cases with a target
 out of range ("bad") and with every pixel ignored ("none") hold NaN; every other loss is finite.
+
+The same cases are compared with a float64 statement of each operation: host_inputs builds the inputs
+without a device, run_case_outputs hands back what the launches of run_case wrote (same order of
+allocations and launches, same sentinel check) and the return codes, tests/chan_route_ref.py states what
+that must be and tests/test_chan_route_ref_gpu.py compares the two.
 """
 import numpy as np
 import torch
@@ -89,9 +94,7 @@ assert len(set(IDS)) == len(IDS)
 
 
 def _done(out, *rcs):
-    d = out.digests()
-    d["rc"] = ",".join(str(rc) for rc in rcs)
-    return d
+    return out, rcs
 
 
 def _lay(k):
@@ -108,8 +111,13 @@ def _at(t, off):
     return t.data_ptr() + off * t.element_size()
 
 
-def _in(nel, off, salt, dt, scale=1.0, shift=0.0):
-    t = _dev((pattern(nel + off, salt) + shift) * scale, _tdt(dt))
+def _vals(nel, off, salt, scale=1.0, shift=0.0):
+    """Host values of an input of nel elements that starts ``off`` elements into its allocation."""
+    return (pattern(nel + off, salt) + shift) * scale
+
+
+def _in(values, off, dt):
+    t = _dev(values, _tdt(dt))
     return t, _at(t, off)
 
 
@@ -119,23 +127,34 @@ def _out_at(out, name, nel, off, dt):
     return p + off * out.view(name).element_size()
 
 
-def _run_smf(lib, k):
+def _in_smf(k):
+    _, _, _, nel, off = _lay(k)
+    return dict(x=_vals(nel, off, 1))
+
+
+def _run_smf(lib, k, h):
     n, hw, c, dt = k["n"], k["hw"], k["c"], k["dt"]
     sn, sc, shw, nel, off = _lay(k)
     ld = k["ld"] or c
-    x, xp = _in(nel, off, 1, dt)
+    x, xp = _in(h["x"], off, dt)
     out = _Outputs()
     y = out.add("y", n * hw * ld, _tdt(dt))
     rc = lib.rtsds_softmax_fwd(xp, sn, sc, shw, y, ld, n, hw, c, dt, _stream())
     return _done(out, rc)
 
 
-def _run_smb(lib, k):
+def _in_smb(k):
+    n, hw, c = k["n"], k["hw"], k["c"]
+    ld, io = k["ld"] or c, k["off"]
+    return dict(dy=_vals(n * hw * ld, io, 4, 0.25), y=_vals(n * hw * ld, io, 6, 1 / 64, 8))  # y probability-sized, [0, 0.25)
+
+
+def _run_smb(lib, k, h):
     n, hw, c, dt = k["n"], k["hw"], k["c"], k["dt"]
     sn, sc, shw, nel, off = _lay(k)
     ld, io = k["ld"] or c, k["off"]
-    dy, dyp = _in(n * hw * ld, io, 4, dt, 0.25)
-    y, yp = _in(n * hw * ld, io, 6, dt, 1 / 64, 8)  # probability-sized, [0, 0.25)
+    dy, dyp = _in(h["dy"], io, dt)
+    y, yp = _in(h["y"], io, dt)
     out = _Outputs()
     dx = _out_at(out, "dx", nel, off if k["lay"] == "slice" else 0, dt)
     rc = lib.rtsds_softmax_bwd(dyp, yp, ld, dx, sn, sc, shw, n, hw, c, dt, _stream())
@@ -152,25 +171,30 @@ def _targets(pix, c, mode="idx"):
         t[pix // 2] = 25
     elif mode == "none":
         t[:] = IGNORE
-    return torch.from_numpy(t).cuda()
+    return t
 
 
 def _words(out, name):
     return out.view(name).view(torch.float32)
 
 
-def _run_ce(lib, k):
+def _in_ce(k):
+    _, _, _, nel, off = _lay(k)
+    return dict(x=_vals(nel, off, 1), tgt=_targets(k["n"] * k["hw"], k["c"], k["tgt"]), gl=np.array([2.0], dtype=np.float32))
+
+
+def _run_ce(lib, k, h):
     n, hw, c, dt = k["n"], k["hw"], k["c"], k["dt"]
     sn, sc, shw, nel, off = _lay(k)
-    x, xp = _in(nel, off, 1, dt)
-    tgt = _targets(n * hw, c, k["tgt"])
+    x, xp = _in(h["x"], off, dt)
+    tgt = torch.from_numpy(h["tgt"]).cuda()
     nws = lib.rtsds_ce_workspace() // 4
     unread = np.full(nws, -1, dtype=np.int32)  # 0xffffffff: a word nobody wrote reads as NaN
     out = _Outputs()
     ws = out.add("ws", nws, torch.int32, unread)
     loss = out.add("loss", 1, torch.int32)
     rcs = [lib.rtsds_ce_fwd(xp, sn, sc, shw, _P(tgt), loss, n, hw, c, IGNORE, dt, ws, nws * 4, _stream())]
-    gl = _dev(np.array([2.0], dtype=np.float32))
+    gl = _dev(h["gl"])
     dx = out.add("dx", nel, _tdt(dt))
     rcs.append(lib.rtsds_ce_bwd(xp, sn, sc, shw, _P(tgt), _P(gl), ws + 2 * CE_RB * 4, dx, n, hw, c, IGNORE, dt, _stream()))
     # the data-parallel finish: C replaced (as if summed over ranks), loss = S / C
@@ -182,9 +206,8 @@ def _run_ce(lib, k):
     return _done(out, *rcs)
 
 
-def _run_am(lib, k):
-    n, hw, c, dt = k["n"], k["hw"], k["c"], k["dt"]
-    sn, sc, shw, nel, off = _lay(k)
+def _in_am(k):
+    n, hw, c = k["n"], k["hw"], k["c"]
     pix = n * hw
     r = pattern(pix * c, 1).reshape(pix, c)  # [pixel][class]
     if c > 12:
@@ -193,8 +216,15 @@ def _run_am(lib, k):
         r[np.ix_(p % 11 == 5, (7, 12))] = np.nan   # NaNs after numbers: the first of them wins
         r[np.ix_(p % 11 == 8, (5, 11))] = 9.0      # a tie above every other value
     v = r.reshape(n, hw, c).transpose(0, 2, 1) if k["lay"] == "nchw" else r
-    x = _dev(v, _tdt(dt))
-    tgt = None if k["null"] == "tgt" else _targets(pix, c)
+    return dict(x=np.ascontiguousarray(v), tgt=None if k["null"] == "tgt" else _targets(pix, c))
+
+
+def _run_am(lib, k, h):
+    n, hw, c, dt = k["n"], k["hw"], k["c"], k["dt"]
+    sn, sc, shw, nel, off = _lay(k)
+    pix = n * hw
+    x = _dev(h["x"], _tdt(dt))
+    tgt = None if h["tgt"] is None else torch.from_numpy(h["tgt"]).cuda()
     out = _Outputs()
     o = None if k["null"] == "out" else out.add("out", pix, torch.int64)
     cor = None if k["null"] == "correct" else out.add("correct", 1, torch.int64, np.array([5], dtype=np.int64))
@@ -202,22 +232,33 @@ def _run_am(lib, k):
     return _done(out, rc)
 
 
-def _run_bce(lib, k):
+def _in_bce(k):
     n = k["n"]
-    x, t, gl = _dev(pattern(n, 1)), _dev((pattern(n, 2) + 8) / 16), _dev(np.array([2.0], dtype=np.float32))
+    return dict(x=pattern(n, 1), t=(pattern(n, 2) + 8) / 16, gl=np.array([2.0], dtype=np.float32))
+
+
+def _run_bce(lib, k, h):
+    n = k["n"]
+    x, t, gl = _dev(h["x"]), _dev(h["t"]), _dev(h["gl"])
     out = _Outputs()
     loss, dx = out.add("loss", 1, torch.float32), out.add("dx", n, torch.float32)
     rcs = [lib.rtsds_bce_fwd(_P(x), _P(t), loss, n, _stream()), lib.rtsds_bce_bwd(_P(x), _P(t), _P(gl), dx, n, _stream())]
     return _done(out, *rcs)
 
 
-def _run_conf(lib, k):
+def _in_conf(k):
     total, nc = k["total"], k["nc"]
     i = np.arange(total, dtype=np.int64)
-    label = torch.from_numpy((i * 7 + 3) % (nc + 4) - 2).cuda()  # -2 .. nc + 1
-    pred = torch.from_numpy((i * 5 + 1) % nc).cuda()
+    return dict(label=(i * 7 + 3) % (nc + 4) - 2, pred=(i * 5 + 1) % nc,  # labels -2 .. nc + 1
+                hist0=np.arange(nc * nc, dtype=np.int64))
+
+
+def _run_conf(lib, k, h):
+    total, nc = k["total"], k["nc"]
+    label = torch.from_numpy(h["label"]).cuda()
+    pred = torch.from_numpy(h["pred"]).cuda()
     out = _Outputs()
-    hist = out.add("hist", nc * nc, torch.int64, np.arange(nc * nc, dtype=np.int64))
+    hist = out.add("hist", nc * nc, torch.int64, h["hist0"])
     rc = lib.rtsds_confusion(_P(label), _P(pred), hist, total, nc, _stream())
     return _done(out, rc)
 
@@ -227,9 +268,13 @@ def _ws(nbytes):
     return torch.full((nbytes,), 0xFF, dtype=torch.uint8, device="cuda")
 
 
-def _run_gapf(lib, k):
+def _in_gapf(k):
+    return dict(x=pattern(k["n"] * k["hw"] * k["c"], 1))
+
+
+def _run_gapf(lib, k, h):
     n, hw, c, dt = k["n"], k["hw"], k["c"], k["dt"]
-    x = _dev(pattern(n * hw * c, 1), _tdt(dt))
+    x = _dev(h["x"], _tdt(dt))
     out = _Outputs()
     y = out.add("y", n * c, _tdt(dt))
     ws = _ws(lib.rtsds_gap_workspace(n, hw, c))
@@ -237,28 +282,38 @@ def _run_gapf(lib, k):
     return _done(out, rc)
 
 
-def _run_gapb(lib, k):
+def _in_gapb(k):
+    n, hw, c = k["n"], k["hw"], k["c"]
+    return dict(dy=pattern(n * c, 4) / 4, dx0=pattern(n * hw * c, 5) / 8 if k["acc"] else None)
+
+
+def _run_gapb(lib, k, h):
     n, hw, c, dt = k["n"], k["hw"], k["c"], k["dt"]
-    dy = _dev(pattern(n * c, 4) / 4, _tdt(dt))
+    dy = _dev(h["dy"], _tdt(dt))
     out = _Outputs()
-    dx = out.add("dx", n * hw * c, _tdt(dt), pattern(n * hw * c, 5) / 8 if k["acc"] else None)
+    dx = out.add("dx", n * hw * c, _tdt(dt), h["dx0"])
     rc = lib.rtsds_gap_bwd(_P(dy), dx, n, hw, c, k["acc"], dt, _stream())
     return _done(out, rc)
 
 
-def _run_csf(lib, k):
+def _in_cs(k):
+    n, hw, c = k["n"], k["hw"], k["c"]
+    return dict(dy=pattern(n * hw * c, 4) / 4, x=pattern(n * hw * c, 1), a=(pattern(n * c, 2) + 8) / 16)
+
+
+def _run_csf(lib, k, h):
     n, hw, c, dt = k["n"], k["hw"], k["c"], k["dt"]
-    x, a = _dev(pattern(n * hw * c, 1), _tdt(dt)), _dev((pattern(n * c, 2) + 8) / 16, _tdt(dt))
+    x, a = _dev(h["x"], _tdt(dt)), _dev(h["a"], _tdt(dt))
     out = _Outputs()
     y = out.add("y", n * hw * c, _tdt(dt))
     rc = lib.rtsds_chscale_fwd(_P(x), _P(a), y, n, hw, c, k["mode"], dt, _stream())
     return _done(out, rc)
 
 
-def _run_csb(lib, k):
+def _run_csb(lib, k, h):
     n, hw, c, dt = k["n"], k["hw"], k["c"], k["dt"]
-    dy, x = _dev(pattern(n * hw * c, 4) / 4, _tdt(dt)), _dev(pattern(n * hw * c, 1), _tdt(dt))
-    a = _dev((pattern(n * c, 2) + 8) / 16, _tdt(dt))
+    dy, x = _dev(h["dy"], _tdt(dt)), _dev(h["x"], _tdt(dt))
+    a = _dev(h["a"], _tdt(dt))
     out = _Outputs()
     dx = out.add("dx", n * hw * c, _tdt(dt)) if k["outs"] == "dx" else None
     da = out.add("da", n * c, _tdt(dt)) if k["outs"] == "da" else None
@@ -267,11 +322,17 @@ def _run_csb(lib, k):
     return _done(out, rc)
 
 
-def _run_ffm(lib, k):
+def _in_ffm(k):
+    n, hw, c = k["n"], k["hw"], k["c"]
+    return dict(f=pattern(n * hw * c, 1) / 4, w=[pattern(c * c, 11 + i) / 16 for i in range(3)],
+                b=[pattern(c, 21 + i) / 8 for i in range(3)])
+
+
+def _run_ffm(lib, k, h):
     n, hw, c, dt = k["n"], k["hw"], k["c"], k["dt"]
-    f = _dev(pattern(n * hw * c, 1) / 4, _tdt(dt))
-    w = [_dev(pattern(c * c, 11 + i) / 16, _tdt(dt)) for i in range(3)]
-    b = [_dev(pattern(c, 21 + i) / 8) for i in range(3)]
+    f = _dev(h["f"], _tdt(dt))
+    w = [_dev(v, _tdt(dt)) for v in h["w"]]
+    b = [_dev(v) for v in h["b"]]
     out = _Outputs()
     y = out.add("out", n * hw * c, _tdt(dt))
     ws = _ws(lib.rtsds_ffm_head_eval_workspace(n, hw, c))
@@ -284,8 +345,33 @@ _RUN = {"smf": _run_smf, "smb": _run_smb, "ce": _run_ce, "am": _run_am, "bce": _
         "gapb": _run_gapb, "csf": _run_csf, "csb": _run_csb, "ffm": _run_ffm}
 
 
-def run_case(case):
-    """{output name: SHA-256 of its bytes, "rc": return codes} of one case; asserts the sentinels."""
+_INPUTS = {"smf": _in_smf, "smb": _in_smb, "ce": _in_ce, "am": _in_am, "bce": _in_bce, "conf": _in_conf, "gapf": _in_gapf,
+           "gapb": _in_gapb, "csf": _in_cs, "csb": _in_cs, "ffm": _in_ffm}
+
+
+def host_inputs(case):
+    """The host inputs of one case as numpy arrays (fp32 values; a bf16 case rounds them on the way to the
+    device), by name.  No device, no library: the references and the tolerance recorder use them too."""
+    return _INPUTS[case["kind"]](case)
+
+
+def _launch(case):
     from rtsds_amd._lib import load
     lib = load()  # the raw entry points: a nonzero return code is recorded, not raised
-    return _RUN[case["kind"]](lib, case)
+    h = host_inputs(case)
+    return (h,) + _RUN[case["kind"]](lib, case, h)
+
+
+def run_case(case):
+    """{output name: SHA-256 of its bytes, "rc": return codes} of one case; asserts the sentinels."""
+    _, out, rcs = _launch(case)
+    d = out.digests()
+    d["rc"] = ",".join(str(rc) for rc in rcs)
+    return d
+
+
+def run_case_outputs(case):
+    """(host inputs, {output name: host tensor}, return codes) of one case, the same launches as run_case;
+    asserts the sentinels.  tests/chan_route_ref.py states what the outputs must be."""
+    h, out, rcs = _launch(case)
+    return h, out.host(), rcs

@@ -10,6 +10,11 @@ case also records the entry point's return code.
 Sizes are (hi, wi) -> (ho, wo) of the forward resize; the backward cases read dy at (ho, wo)
 and write dx at (hi, wi).  V = 8 (bf16) / 4 (fp32) is the 16-byte vector width.  Every case
 runs in both dtypes.
+
+The same cases are compared with a float64 statement of each operation: host_inputs builds the inputs
+without a device, run_case_outputs hands back what the launch of run_case wrote (same order of
+allocations, same sentinel check) and the return code, tests/resize_route_ref.py states what that must be
+and tests/test_resize_route_ref_gpu.py compares the two.
 """
 import numpy as np
 import torch
@@ -122,20 +127,24 @@ def _geo(k):
 
 
 def _done(out, rc):
-    d = out.digests()
-    d["rc"] = str(rc)
-    return d
+    return out, rc
 
 
-def _run_fwd(lib, k):
+def _in_fwd(k):
+    n, hi, wi, c = k["n"], k["hi"], k["wi"], k["c"]
+    return dict(x=pattern(n * hi * wi * c, 1), s1=1 + pattern(n * c, 2) / 16 if k["s"] else None,
+                s2=1 + pattern(n * c, 3) / 16 if k["s"] == 2 else None)
+
+
+def _run_fwd(lib, k, h):
     n, hi, wi, c, ho, wo, sh, sw = _geo(k)
     dt, ld = k["dt"], k["ld"] or c
-    x = _dev(pattern(n * hi * wi * c, 1), _tdt(dt))
+    x = _dev(h["x"], _tdt(dt))
     out = _Outputs()
     y = out.add("y", n * ho * wo * ld, _tdt(dt))
     if k["s"]:
-        s1 = _dev(1 + pattern(n * c, 2) / 16, _tdt(dt))
-        s2 = _dev(1 + pattern(n * c, 3) / 16, _tdt(dt)) if k["s"] == 2 else None
+        s1 = _dev(h["s1"], _tdt(dt))
+        s2 = _dev(h["s2"], _tdt(dt)) if k["s"] == 2 else None
         rc = lib.rtsds_bilinear_fwd_scaled(_P(x), _P(s1), _P(s2), y, n, hi, wi, c, ho, wo, sh, sw, k["ld"], k["off"], dt,
                                            _stream())
     else:
@@ -148,10 +157,14 @@ def _ws(nbytes):
     return torch.full((nbytes,), 0xFF, dtype=torch.uint8, device="cuda")
 
 
-def _run_bwd(lib, k):
+def _in_bwd(k):
+    return dict(dy=pattern(k["n"] * k["ho"] * k["wo"] * (k["ld"] or k["c"]), 4) / 4)
+
+
+def _run_bwd(lib, k, h):
     n, hi, wi, c, ho, wo, sh, sw = _geo(k)
     dt, ld = k["dt"], k["ld"] or c
-    dy = _dev(pattern(n * ho * wo * ld, 4) / 4, _tdt(dt))
+    dy = _dev(h["dy"], _tdt(dt))
     out = _Outputs()
     dx = out.add("dx", n * hi * wi * c, _tdt(dt))
     ws = _ws(lib.rtsds_bilinear_bwd_workspace(n, hi, wi, c, ho, wo))
@@ -159,32 +172,42 @@ def _run_bwd(lib, k):
     return _done(out, rc)
 
 
-def _run_usf(lib, k):
+def _in_us(k):
+    n, hi, wi, c, ho, wo = k["n"], k["hi"], k["wi"], k["c"], k["ho"], k["wo"]
+    return dict(x=pattern(n * hi * wi * c, 1), acc0=(pattern(n * ho * wo * c, 5) + 8) / 16 if k.get("acc") else None)
+
+
+def _run_usf(lib, k, h):
     n, hi, wi, c, ho, wo, sh, sw = _geo(k)
     dt = k["dt"]
-    x = _dev(pattern(n * hi * wi * c, 1), _tdt(dt))
+    x = _dev(h["x"], _tdt(dt))
     out = _Outputs()
     y = out.add("y", n * ho * wo * k["yld"], _tdt(dt))
     rc = lib.rtsds_upsoftmax_fwd(_P(x), y, n, hi, wi, c, ho, wo, sh, sw, k["yld"], dt, _stream())
     return _done(out, rc)
 
 
-def _run_usa(lib, k):
+def _run_usa(lib, k, h):
     n, hi, wi, c, ho, wo, sh, sw = _geo(k)
     dt = k["dt"]
-    x = _dev(pattern(n * hi * wi * c, 1), _tdt(dt))
+    x = _dev(h["x"], _tdt(dt))
     out = _Outputs()
-    acc = out.add("acc", n * ho * wo * c, torch.float32, (pattern(n * ho * wo * c, 5) + 8) / 16 if k["acc"] else None)
+    acc = out.add("acc", n * ho * wo * c, torch.float32, h["acc0"])
     pred = out.add("pred", n * ho * wo, torch.int64) if k["pred"] else None
     rc = lib.rtsds_upsoftmax_acc(_P(x), acc, pred, n, hi, wi, c, ho, wo, sh, sw, k["flip"], k["acc"], dt, _stream())
     return _done(out, rc)
 
 
-def _run_usb(lib, k):
+def _in_usb(k):
+    pix = k["n"] * k["ho"] * k["wo"]
+    return dict(dy=pattern(pix * k["dyld"], 4) / 4, p=(pattern(pix * k["yld"], 6) + 8) / 64)  # p probability-sized, [0, 0.25)
+
+
+def _run_usb(lib, k, h):
     n, hi, wi, c, ho, wo, sh, sw = _geo(k)
     dt, pix = k["dt"], n * ho * wo
-    dy = _dev(pattern(pix * k["dyld"], 4) / 4, _tdt(dt))
-    p = _dev((pattern(pix * k["yld"], 6) + 8) / 64, _tdt(dt))  # probability-sized, [0, 0.25)
+    dy = _dev(h["dy"], _tdt(dt))
+    p = _dev(h["p"], _tdt(dt))
     out = _Outputs()
     dx = out.add("dx", n * hi * wi * c, _tdt(dt))
     ws = _ws(lib.rtsds_upsoftmax_bwd_workspace(n, hi, wi, c, ho, wo))
@@ -193,8 +216,33 @@ def _run_usb(lib, k):
     return _done(out, rc)
 
 
-def run_case(case):
-    """{output name: SHA-256 of its bytes, "rc": return code} of one case; asserts the sentinels."""
+_INPUTS = {"fwd": _in_fwd, "bwd": _in_bwd, "usf": _in_us, "usa": _in_us, "usb": _in_usb}
+_RUN = {"fwd": _run_fwd, "bwd": _run_bwd, "usf": _run_usf, "usa": _run_usa, "usb": _run_usb}
+
+
+def host_inputs(case):
+    """The host inputs of one case as numpy arrays (fp32 values; a bf16 case rounds them on the way to the
+    device), by name.  No device, no library: the references and the tolerance recorder use them too."""
+    return _INPUTS[case["kind"]](case)
+
+
+def _launch(case):
     from rtsds_amd._lib import load
     lib = load()  # the raw entry points: a nonzero return code is recorded, not raised
-    return {"fwd": _run_fwd, "bwd": _run_bwd, "usf": _run_usf, "usa": _run_usa, "usb": _run_usb}[case["kind"]](lib, case)
+    h = host_inputs(case)
+    return (h,) + _RUN[case["kind"]](lib, case, h)
+
+
+def run_case(case):
+    """{output name: SHA-256 of its bytes, "rc": return code} of one case; asserts the sentinels."""
+    _, out, rc = _launch(case)
+    d = out.digests()
+    d["rc"] = str(rc)
+    return d
+
+
+def run_case_outputs(case):
+    """(host inputs, {output name: host tensor}, return code) of one case, the same launches as run_case;
+    asserts the sentinels.  tests/resize_route_ref.py states what the outputs must be."""
+    h, out, rc = _launch(case)
+    return h, out.host(), (rc,)
