@@ -535,6 +535,38 @@ int rtsds_upsoftmax_bwd(const void* dy, int dy_ld, const void* y, int y_ld, void
                         int wi, int c, int ho, int wo, float scale_h, float scale_w, int dtype,
                         void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- discriminator input, AdvEnt form
+ * The weighted self-information maps of ADVENT (Vu et al., CVPR 2019: prob_2_entropy,
+ * -p log2(p + 1e-30) / log2(c), here without the epsilon) of the resized head, in
+ * rtsds_upsoftmax_fwd's layout: x NHWC [n][hi][wi][c], y NHWC [n][ho][wo][y_ld], c <= y_ld <= 32,
+ * channels c..y_ld-1 exact zeros.  Per output pixel, z = the bilinear resize (align_corners =
+ * False) rounded to the activation dtype T exactly as rtsds_bilinear_fwd stores it (the logits
+ * rtsds_upsoftmax_fwd starts from, bit for bit), then in fp32
+ *   d_k = z_k - max z    e_k = expf(d_k)    S = sum_k e_k (class order)    p_k = e_k * (1 / S)
+ *   L_k = logf(S) - d_k                     (= -ln p_k >= 0: one logf per pixel, none per class)
+ *   I_k = p_k * L_k * fp32(1 / ln c)        and I_k = 0 where e_k == 0 (a class at -inf: 0, not NaN)
+ * and y_k = I_k rounded to T; 0 <= I_k <= 1 / (e ln c).
+ * rtsds_upselfinfo_bwd, given dy (c channels, row pitch dy_ld) and the same x:
+ *   a_k = (L_k - 1) * fp32(1 / ln c)        (= dI_k / dp_k; 0 where e_k == 0)
+ *   u_k = dy_k * a_k
+ *   dz_j = p_j * (u_j - sum_k p_k u_k)      (sum in class order)
+ *   dx   = resize adjoint of dz             (width adjoint, then the vertical pass of
+ *                                            rtsds_bilinear_bwd)
+ * p and L are formed again from x by the forward's own code (I does not determine p: -p ln p is
+ * not monotone), so nothing of the forward's output is read; dz stays fp32 until the adjoint has
+ * summed it and only dx is rounded to T.  Fixed summation order, no atomics, no memset, no host
+ * synchronisation: two runs give equal bits and both entries capture into a graph.
+ * RTSDS_ERR_SHAPE: c outside [2, 32], y_ld outside [c, 32], dy_ld < c, an empty tensor;
+ * RTSDS_ERR_WORKSPACE: ws_bytes below the query; RTSDS_ERR_UNSUPPORTED: another dtype, more
+ * than INT_MAX tiles, or (backward) an upsampling so steep that the tile of a single input
+ * column exceeds the kernel's LDS (some 370 output columns per input column at 32 classes). */
+int rtsds_upselfinfo_fwd(const void* x, void* y, int n, int hi, int wi, int c, int ho, int wo,
+                         float scale_h, float scale_w, int y_ld, int dtype, void* stream);
+size_t rtsds_upselfinfo_bwd_workspace(int n, int hi, int wi, int c, int ho, int wo);
+int rtsds_upselfinfo_bwd(const void* dy, int dy_ld, const void* x, void* dx, int n, int hi, int wi,
+                         int c, int ho, int wo, float scale_h, float scale_w, int dtype, void* ws,
+                         size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- multi-scale / flip evaluation
  * One pass of the summed-probability evaluation protocol: p = softmax(interpolate_bilinear(x))
  * exactly as rtsds_upsoftmax_fwd forms it (same geometries, c <= 32), kept in fp32 (fp32 mode:
@@ -939,7 +971,7 @@ int rtsds_label_stats(const int64_t* label, int n, int h, int w, int c, int igno
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 27
+#define RTSDS_ABI_VERSION 28
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

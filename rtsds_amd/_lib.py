@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSDS_LIB: alternative in-tree build of the same ABI (kernel-variant A/B measurements)
 DEFAULT_LIB_PATH = os.path.join(_HERE, "librtsds_hip.so")
-ABI_VERSION = 27  # include/rtsds_hip.h RTSDS_ABI_VERSION
+ABI_VERSION = 28  # include/rtsds_hip.h RTSDS_ABI_VERSION
 LIB_PATH = os.environ.get("RTSDS_LIB") or DEFAULT_LIB_PATH
 
 F32, BF16 = 0, 1
@@ -155,6 +155,10 @@ SIGNATURES = {
     "rtsds_upsoftmax_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "rtsds_upsoftmax_bwd": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                     c_int, P, c_size_t, P]),
+    "rtsds_upselfinfo_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, P]),
+    "rtsds_upselfinfo_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "rtsds_upselfinfo_bwd": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, P,
+                                     c_size_t, P]),
     "rtsds_upsoftmax_acc": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int,
                                     c_int, P]),
     "rtsds_conf_hist": (c_int, [P, P, P, P, c_long, c_int, c_int, c_float, P]),

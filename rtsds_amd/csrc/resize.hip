@@ -599,15 +599,16 @@ struct UpsmTile {
   float lh0, lh1;
   const T *r0, *r1;
 };
+// the same for any run of output pixels [ow0, ow0 + np) of output row `row` (the self-information
+// backward's tiles are runs of the output columns that a tile of input columns receives from)
 template <typename T, bool STAGED>
-RT_DEV UpsmTile<T> upsm_tile(const T* __restrict__ x, float* src, int hi, int wi, int c, int ho, int wo, float sh, float sw,
-                             int tiles) {
+RT_DEV UpsmTile<T> upsm_span(const T* __restrict__ x, float* src, long row, int ow0, int np, int hi, int wi, int c, int ho, float sh,
+                             float sw) {
   UpsmTile<T> t;
-  const int tile = blockIdx.x % tiles;
-  t.row = blockIdx.x / tiles;
+  t.row = row;
   const int oh = (int)(t.row % ho), img = (int)(t.row / ho);
-  t.ow0 = tile * kUpsmPix;
-  t.np = min(kUpsmPix, wo - t.ow0);
+  t.ow0 = ow0;
+  t.np = np;
   int h0, h1;
   bil_src(oh, sh, hi, h0, h1, t.lh0, t.lh1);
   t.r0 = x + ((long)img * hi + h0) * wi * c;
@@ -624,6 +625,12 @@ RT_DEV UpsmTile<T> upsm_tile(const T* __restrict__ x, float* src, int hi, int wi
     bil_stage_rows(t.r0 + (long)t.wlo * c, t.r1 + (long)t.wlo * c, src, t.n1);
   }
   return t;
+}
+template <typename T, bool STAGED>
+RT_DEV UpsmTile<T> upsm_tile(const T* __restrict__ x, float* src, int hi, int wi, int c, int ho, int wo, float sh, float sw,
+                             int tiles) {
+  const int ow0 = blockIdx.x % tiles * kUpsmPix;
+  return upsm_span<T, STAGED>(x, src, blockIdx.x / tiles, ow0, min(kUpsmPix, wo - ow0), hi, wi, c, ho, sh, sw);
 }
 // class k of one output pixel's resized logits, upsm_probs' z[k] ahead of its exp: bil_mix of the
 // four taps (column taps w0 / w1 of the staged rows, or of r0 / r1), rounded to T as
@@ -649,8 +656,12 @@ RT_DEV float upsm_logit(const T* __restrict__ r0, const T* __restrict__ r1, cons
   return to_f(from_f<T>(bil_mix(p00, p01, p10, p11, lh0, lh1, lw0, lw1)));
 }
 // one output pixel's blend + softmax, shared by upsoftmax_fwd_kernel and upsoftmax_acc_kernel:
-// on return the probability of class k is the fp32 product z[k] * iz
-template <typename T, bool STAGED, int CC>
+// on return the probability of class k is the fp32 product z[k] * iz.  With LOGITS it stops ahead of
+// the exponentials: z[k] is the resized logit of class k, rounded to T as rtsds_bilinear_fwd stores
+// it, and iz their maximum (upsm_logits).  One function with a switch, not a blend that this one
+// calls: that split gave every staged runtime-c kernel 90 more instructions (the second row's LDS
+// addresses formed per class), the same sensitivity as upsm_logit's above.
+template <typename T, bool STAGED, int CC, bool LOGITS = false>
 RT_DEV void upsm_probs(const T* __restrict__ r0, const T* __restrict__ r1, const float* src, int wlo, int n1, int c_, int ow,
                        float sw, int wi, float lh0, float lh1, float (&z)[kUpsmMaxC], float& iz) {
   const int c = CC > 0 ? CC : c_;
@@ -677,6 +688,10 @@ RT_DEV void upsm_probs(const T* __restrict__ r0, const T* __restrict__ r1, const
       m = fmaxf(m, z[k]);
     }
   }
+  if (LOGITS) {
+    iz = m;
+    return;
+  }
   float sum = 0.f;  // exp(z - m) evaluated once per class (softmax_fwd_staged evaluates the same
                     // expf twice: identical values)
 #pragma unroll
@@ -687,16 +702,48 @@ RT_DEV void upsm_probs(const T* __restrict__ r0, const T* __restrict__ r1, const
     }
   iz = 1.f / sum;
 }
-// one output pixel of upsoftmax_fwd_kernel: blend, softmax, padded row into the LDS tile
+// one output pixel's resized logits z[k] (upsm_probs' values ahead of the exponentials); returns their maximum
 template <typename T, bool STAGED, int CC>
-RT_DEV void upsm_pixel(const T* __restrict__ r0, const T* __restrict__ r1, const float* src, T* o, int wlo, int n1, int c_, int ow,
-                       float sw, int wi, float lh0, float lh1, int yld) {
+RT_DEV float upsm_logits(const T* __restrict__ r0, const T* __restrict__ r1, const float* src, int wlo, int n1, int c_, int ow,
+                         float sw, int wi, float lh0, float lh1, float (&z)[kUpsmMaxC]) {
+  float m;
+  upsm_probs<T, STAGED, CC, true>(r0, r1, src, wlo, n1, c_, ow, sw, wi, lh0, lh1, z, m);
+  return m;
+}
+// one output pixel's self-information terms (rtsds_upselfinfo_fwd / _bwd, include/rtsds_hip.h): from
+// the resized logits z and their maximum m (upsm_logits), e_k = expf(z_k - m), iz = 1 / S and
+// ls = logf(S) with S = sum_k e_k in class order, so that p_k = e_k * iz and L_k = ls - (z_k - m) =
+// -ln p_k >= 0: one logf per pixel, none per class.  e_k is held beside z_k: evaluating expf again
+// where it is used (one 32-float array per lane instead of two, as softmax_fwd_staged does) measured
+// the same in both kernels and both dtypes (profiles/advent/README.md).
+struct UpsiRow {
+  float z[kUpsmMaxC], e[kUpsmMaxC];
+  float m, iz, ls;
+  RT_DEV float d(int k) const { return z[k] - m; }
+};
+template <int CC>
+RT_DEV void upsi_sums(UpsiRow& r, int c_) {
   const int c = CC > 0 ? CC : c_;
-  float z[kUpsmMaxC];
-  float iz;
-  upsm_probs<T, STAGED, CC>(r0, r1, src, wlo, n1, c_, ow, sw, wi, lh0, lh1, z, iz);
-  // the padded row goes through LDS so the tile leaves as lane-consecutive 16-B chunks (the
-  // tile's rows are contiguous in y): full-line writes instead of 64-B-strided partial ones
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < kUpsmMaxC; ++k)
+    if (k < c) {
+      r.e[k] = expf(r.z[k] - r.m);
+      sum += r.e[k];
+    }
+  r.iz = 1.f / sum;
+  r.ls = logf(sum);
+}
+// I_k = p_k L_k / ln c; a class with e_k == 0 (a logit at -inf, or one underflowed) gives 0, not 0 * inf
+RT_DEV float upsi_info(const UpsiRow& r, int k, float inv_lnc) {
+  const float e = r.e[k];
+  return e == 0.f ? 0.f : e * r.iz * (r.ls - r.d(k)) * inv_lnc;
+}
+// the padded row of one output pixel, val(k) for k < c and zeros behind, into the LDS tile.  The row
+// goes through LDS so the tile leaves as lane-consecutive 16-B chunks (the tile's rows are contiguous
+// in y): full-line writes instead of 64-B-strided partial ones
+template <typename T, typename V>
+RT_DEV void upsm_row_out(T* o, int ow, int c, int yld, V val) {
   if (sizeof(T) == 2 && yld == 32) {  // 4 x 16-B LDS writes, chunk q at slot q ^ (pixel & 3)
     typedef typename VecT<T>::v16 V16;
     const int sw4 = ow & 3;
@@ -704,18 +751,36 @@ RT_DEV void upsm_pixel(const T* __restrict__ r0, const T* __restrict__ r1, const
     for (int q = 0; q < 4; ++q) {
       V16 v;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = from_f<T>(q * 8 + j < c ? z[q * 8 + j] * iz : 0.f);
+      for (int j = 0; j < 8; ++j) v[j] = from_f<T>(q * 8 + j < c ? val(q * 8 + j) : 0.f);
       *(V16*)(o + (q ^ sw4) * 8) = v;
     }
   } else {
 #pragma unroll
     for (int k = 0; k < kUpsmMaxC; ++k)
-      if (k < yld) o[k] = from_f<T>(k < c ? z[k] * iz : 0.f);
+      if (k < yld) o[k] = from_f<T>(k < c ? val(k) : 0.f);
   }
 }
-template <typename T, bool STAGED, int CC>  // CC > 0: compile-time class count (19), 0: runtime c
-__global__ void __launch_bounds__(256) upsoftmax_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int hi, int wi, int c_,
-                                                            int ho, int wo, float sh, float sw, int yld, int tiles) {
+// one output pixel of the forward tile: blend, softmax (SI: self-information on top), padded row into the LDS tile
+template <typename T, bool STAGED, int CC, bool SI>
+RT_DEV void upsm_pixel(const T* __restrict__ r0, const T* __restrict__ r1, const float* src, T* o, int wlo, int n1, int c_, int ow,
+                       float sw, int wi, float lh0, float lh1, int yld, float inv_lnc) {
+  const int c = CC > 0 ? CC : c_;
+  if (SI) {
+    UpsiRow r;
+    r.m = upsm_logits<T, STAGED, CC>(r0, r1, src, wlo, n1, c_, ow, sw, wi, lh0, lh1, r.z);
+    upsi_sums<CC>(r, c_);
+    upsm_row_out(o, ow, c, yld, [&](int k) { return upsi_info(r, k, inv_lnc); });
+  } else {
+    float z[kUpsmMaxC];
+    float iz;
+    upsm_probs<T, STAGED, CC>(r0, r1, src, wlo, n1, c_, ow, sw, wi, lh0, lh1, z, iz);
+    upsm_row_out(o, ow, c, yld, [&](int k) { return z[k] * iz; });
+  }
+}
+// the forward tile of rtsds_upsoftmax_fwd and rtsds_upselfinfo_fwd (SI)
+template <typename T, bool STAGED, int CC, bool SI>
+RT_DEV void upsm_fwd_tile(const T* __restrict__ x, T* __restrict__ y, int hi, int wi, int c_, int ho, int wo, float sh, float sw,
+                          int yld, int tiles, float inv_lnc) {
   const int c = CC > 0 ? CC : c_;
   extern __shared__ __attribute__((aligned(16))) float src[];  // STAGED: [2][ncols][c]
   const int tid = threadIdx.x;
@@ -724,7 +789,8 @@ __global__ void __launch_bounds__(256) upsoftmax_fwd_kernel(const T* __restrict_
   if (STAGED) __syncthreads();
   T* outbuf = (T*)(src + ((2 * tl.n1 + 3) & ~3));  // [256][yld], 16-B aligned
   if (tid < np)
-    upsm_pixel<T, STAGED, CC>(tl.r0, tl.r1, src, outbuf + tid * yld, tl.wlo, tl.n1, c, ow0 + tid, sw, wi, tl.lh0, tl.lh1, yld);
+    upsm_pixel<T, STAGED, CC, SI>(tl.r0, tl.r1, src, outbuf + tid * yld, tl.wlo, tl.n1, c, ow0 + tid, sw, wi, tl.lh0, tl.lh1, yld,
+                                  inv_lnc);
   __syncthreads();  // every lane reaches the same barrier (no early exit)
   T* dst = y + (tl.row * wo + ow0) * yld;
   if (sizeof(T) == 2 && yld == 32) {  // un-swizzle: LDS read linear, global chunk q = slot ^ (pixel & 3)
@@ -736,6 +802,16 @@ __global__ void __launch_bounds__(256) upsoftmax_fwd_kernel(const T* __restrict_
   } else {
     stage_out(dst, outbuf, np * yld);
   }
+}
+template <typename T, bool STAGED, int CC>  // CC > 0: compile-time class count (19), 0: runtime c
+__global__ void __launch_bounds__(256) upsoftmax_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int hi, int wi, int c_,
+                                                            int ho, int wo, float sh, float sw, int yld, int tiles) {
+  upsm_fwd_tile<T, STAGED, CC, false>(x, y, hi, wi, c_, ho, wo, sh, sw, yld, tiles, 0.f);
+}
+template <typename T, bool STAGED, int CC>
+__global__ void __launch_bounds__(256) upselfinfo_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int hi, int wi, int c_,
+                                                             int ho, int wo, float sh, float sw, int yld, int tiles, float inv_lnc) {
+  upsm_fwd_tile<T, STAGED, CC, true>(x, y, hi, wi, c_, ho, wo, sh, sw, yld, tiles, inv_lnc);
 }
 // ------------------------------------------------------------------ multi-scale / flip evaluation
 // One pass of the summed-probability protocol (validation.predict_multiscale): the
@@ -1030,6 +1106,53 @@ __global__ void __launch_bounds__(256) slide_paint_kernel(const T* __restrict__ 
     upsm_tile_copy<false>(dst, tbuf, nel, head);
   }
 }
+// one tile of the fused backward kernels' width pass (blockIdx.x = row * tiles + tile): input
+// columns [iw0, iw0 + nw) of row `row` = img * ho + oh, and the output columns [olo, olo + cnt)
+// their width adjoint reads (cnt <= cap, the host's exact maximum over the tiles)
+struct UpsmBwdTile {
+  long row;
+  int iw0, nw, olo, cnt;
+};
+RT_DEV UpsmBwdTile upsm_bwd_tile(int wi, int wo, float sw, int tw, int tiles) {
+  UpsmBwdTile t;
+  const int tile = blockIdx.x % tiles;
+  t.row = blockIdx.x / tiles;
+  t.iw0 = tile * tw;
+  const int iw1 = min(wi, t.iw0 + tw) - 1;
+  t.nw = iw1 - t.iw0 + 1;
+  int ohi;
+  bil_adj_range(t.iw0, iw1, sw, wo, t.olo, ohi);
+  t.cnt = ohi - t.olo + 1;
+  return t;
+}
+// the tile's dy segment -> LDS [cnt][c] (as T, or widened to fp32), coalesced (rows of pitch c;
+// contiguous in memory when dyld == c); the caller places the barrier
+template <typename T, typename S>
+RT_DEV void upsm_bwd_stage(const T* __restrict__ dy, int dyld, S* seg, const UpsmBwdTile& t, int wo, int c) {
+  const int tid = threadIdx.x;
+  const T* gseg = dy + (t.row * wo + t.olo) * dyld;
+  if (dyld == c) {
+    for (int e = tid; e < t.cnt * c; e += 256) seg[e] = (S)gseg[e];
+  } else {
+    for (int e = tid; e < t.cnt * c; e += 256) {
+      const int q = e / c;
+      seg[e] = (S)gseg[(long)q * dyld + (e - q * c)];
+    }
+  }
+}
+// the width adjoint of the tile's LDS segment into tmp: the tile's bilinear weights tabulated in wt /
+// wlo (the barrier behind the segment's last writes is bil_table_build's), then thread per (input
+// column, class), classes inner, with bil_gather
+template <typename S>
+RT_DEV void upsm_bwd_gather(const S* seg, float* wt, int* wlo, float* __restrict__ tmp, const UpsmBwdTile& t, int wi, int c, int wo,
+                            float sw, int maxw) {
+  bil_table_build(wt, wlo, t.iw0, t.nw, wi, wo, sw, maxw, t.olo);  // wlo: relative to the staged segment
+  for (int e = threadIdx.x; e < t.nw * c; e += 256) {
+    const int il = e / c, k = e - il * c;
+    const float* w = wt + il * maxw;
+    tmp[(t.row * wi + t.iw0) * c + e] = bil_gather(seg + wlo[il] * c + k, c, maxw, [&](int j) { return w[j]; });
+  }
+}
 template <typename T, int CC>  // CC > 0: compile-time class count (19), 0: runtime c
 __global__ void __launch_bounds__(256) upsoftmax_bwd_w_kernel(const T* __restrict__ dy, int dyld, const T* __restrict__ y,
                                                               int yld, float* __restrict__ tmp, int wi, int c_, int wo, float sw,
@@ -1040,22 +1163,10 @@ __global__ void __launch_bounds__(256) upsoftmax_bwd_w_kernel(const T* __restric
   int* wlo = (int*)(wt + tw * maxw);     // [tw]
   T* sgt = (T*)(wlo + tw);               // [cap][c]: dy, then the softmax backward in place
   const int tid = threadIdx.x;
-  const int tile = blockIdx.x % tiles;
-  const long row = blockIdx.x / tiles;  // img * ho + oh
-  const int iw0 = tile * tw, iw1 = min(wi, iw0 + tw) - 1, nw = iw1 - iw0 + 1;
-  int olo, ohi;
-  bil_adj_range(iw0, iw1, sw, wo, olo, ohi);
-  const int cnt = ohi - olo + 1;  // <= cap (host: exact maximum over the tiles)
-  // dy segment -> LDS as T, coalesced (rows of pitch c; contiguous in memory when dyld == c)
-  const T* gseg = dy + (row * wo + olo) * dyld;
-  if (dyld == c) {
-    for (int e = tid; e < cnt * c; e += 256) sgt[e] = gseg[e];
-  } else {
-    for (int e = tid; e < cnt * c; e += 256) {
-      const int q = e / c;
-      sgt[e] = gseg[(long)q * dyld + (e - q * c)];
-    }
-  }
+  const UpsmBwdTile t = upsm_bwd_tile(wi, wo, sw, tw, tiles);
+  const long row = t.row;
+  const int olo = t.olo, cnt = t.cnt;
+  upsm_bwd_stage(dy, dyld, sgt, t, wo, c);
   __syncthreads();
   // thread per output pixel: p row (16-B vectors when the pitch allows), softmax backward in place
   for (int q = tid; q < cnt; q += 256) {
@@ -1088,25 +1199,64 @@ __global__ void __launch_bounds__(256) upsoftmax_bwd_w_kernel(const T* __restric
     for (int k = 0; k < kUpsmMaxC; ++k)
       if (k < c) g[k] = from_f<T>(pv[k] * (gv[k] - dot));
   }
-  bil_table_build(wt, wlo, iw0, nw, wi, wo, sw, maxw, olo);  // wlo: relative to the staged segment
-  for (int e = tid; e < nw * c; e += 256) {  // (input column, class) items, classes inner
-    const int il = e / c, k = e - il * c;
-    const float* w = wt + il * maxw;
-    tmp[(row * wi + iw0) * c + e] = bil_gather(sgt + wlo[il] * c + k, c, maxw, [&](int j) { return w[j]; });
-  }
+  upsm_bwd_gather(sgt, wt, wlo, tmp, t, wi, c, wo, sw, maxw);
 }
-// columns of the low-res rows one forward tile stages (taps monotone in ow)
+// rtsds_upselfinfo_bwd's width pass, upsoftmax_bwd_w_kernel's tile: the dy segment is staged as
+// fp32, and beside it the columns of the two low-resolution source rows that the segment's output
+// pixels tap (upsm_span: the forward's staging).  Thread per output pixel: the forward's logits
+// again (upsm_logits, upsi_sums: bit for bit the forward's z, p and L), then
+// dz_j = p_j (u_j - sum_k p_k u_k), u_k = dy_k (L_k - 1) / ln c, in place as fp32; the width adjoint
+// reads that.  Nothing of the forward's output is read.
+template <typename T, int CC>  // CC > 0: compile-time class count (19), 0: runtime c
+__global__ void __launch_bounds__(256) upselfinfo_bwd_w_kernel(const T* __restrict__ dy, int dyld, const T* __restrict__ x,
+                                                               float* __restrict__ tmp, int hi, int wi, int c_, int ho, int wo,
+                                                               float sh, float sw, int tw, int tiles, int cap, int maxw, int srcf,
+                                                               float inv_lnc) {
+  const int c = CC > 0 ? CC : c_;
+  extern __shared__ __attribute__((aligned(16))) float smf[];
+  float* src = smf;                      // [2][columns][c] (srcf floats: the host's bound)
+  float* dz = src + srcf;                // [cap][c]: dy, then dz in place
+  float* wt = dz + cap * c;              // [tw][maxw]
+  int* wlo = (int*)(wt + tw * maxw);     // [tw]
+  const UpsmBwdTile t = upsm_bwd_tile(wi, wo, sw, tw, tiles);
+  const UpsmTile<T> tl = upsm_span<T, true>(x, src, t.row, t.olo, t.cnt, hi, wi, c, ho, sh, sw);
+  upsm_bwd_stage(dy, dyld, dz, t, wo, c);
+  __syncthreads();
+  for (int q = threadIdx.x; q < t.cnt; q += 256) {
+#pragma clang fp contract(off)  // u_k is the rounded product: contracted into u_j - dot, a row with p_j = 1 would not give dz_j = 0
+    UpsiRow r;
+    r.m = upsm_logits<T, true, CC>(tl.r0, tl.r1, src, tl.wlo, tl.n1, c, t.olo + q, sw, wi, tl.lh0, tl.lh1, r.z);
+    upsi_sums<CC>(r, c);
+    float* g = dz + q * c;
+    float dot = 0.f;
+#pragma unroll
+    for (int k = 0; k < kUpsmMaxC; ++k)
+      if (k < c) {  // z[k] <- p_k, e[k] <- u_k
+        const float e = r.e[k], a = e == 0.f ? 0.f : (r.ls - r.d(k) - 1.f) * inv_lnc;
+        r.z[k] = e * r.iz;
+        r.e[k] = g[k] * a;
+        dot = fmaf(r.e[k], r.z[k], dot);
+      }
+#pragma unroll
+    for (int k = 0; k < kUpsmMaxC; ++k)
+      if (k < c) g[k] = r.z[k] * (r.e[k] - dot);
+  }
+  upsm_bwd_gather(dz, wt, wlo, tmp, t, wi, c, wo, sw, maxw);
+}
+// columns of the low-res rows that output columns [ow0, ow1] tap (taps monotone in ow), as the host's
+// float arithmetic gives them: the device's own rounding may move either end by one
+static int upsm_tap_cols(int wi, float sw, int ow0, int ow1) {
+  float src0 = sw * ((float)ow0 + 0.5f) - 0.5f, src1 = sw * ((float)ow1 + 0.5f) - 0.5f;
+  int a = src0 < 0.f ? 0 : (int)src0, b = src1 < 0.f ? 0 : (int)src1;
+  a = std::min(a, wi - 1);
+  b = std::min(b, wi - 1);
+  b = b + (b < wi - 1 ? 1 : 0);
+  return b - a + 1;
+}
+// columns of the low-res rows one forward tile stages
 static int upsm_fwd_cols(int wi, int wo, float sw) {
   int cols = 0;
-  for (int ow0 = 0; ow0 < wo; ow0 += kUpsmPix) {
-    const int ow1 = std::min(wo, ow0 + kUpsmPix) - 1;
-    float src0 = sw * ((float)ow0 + 0.5f) - 0.5f, src1 = sw * ((float)ow1 + 0.5f) - 0.5f;
-    int a = src0 < 0.f ? 0 : (int)src0, b = src1 < 0.f ? 0 : (int)src1;
-    a = std::min(a, wi - 1);
-    b = std::min(b, wi - 1);
-    b = b + (b < wi - 1 ? 1 : 0);
-    cols = std::max(cols, b - a + 1);
-  }
+  for (int ow0 = 0; ow0 < wo; ow0 += kUpsmPix) cols = std::max(cols, upsm_tap_cols(wi, sw, ow0, std::min(wo, ow0 + kUpsmPix) - 1));
   return cols + 2;  // margin: the device computes the tap columns with its own float rounding
 }
 // shape guard and sizing of the forward tiles (upsoftmax_fwd / upsoftmax_acc): tiles per row, grid,
@@ -1137,9 +1287,11 @@ static void upsm_dispatch(bool staged, int c, F f) {
   if (staged) upsm_with_cc(c, [&](auto cc) { f(std::true_type(), cc); });
   else f(std::false_type(), std::integral_constant<int, 0>());
 }
-extern "C" int rtsds_upsoftmax_fwd(const void* x, void* y, int n, int hi, int wi, int c, int ho, int wo, float scale_h,
-                                   float scale_w, int y_ld, int dtype, void* stream) {
-  if (y_ld < c || y_ld > kUpsmMaxC) return RTSDS_ERR_SHAPE;
+// rtsds_upsoftmax_fwd and (SI) rtsds_upselfinfo_fwd: one guard, one choice of route, one LDS size
+template <bool SI>
+static int upsm_fwd_entry(const void* x, void* y, int n, int hi, int wi, int c, int ho, int wo, float scale_h, float scale_w,
+                          int y_ld, int dtype, void* stream) {
+  if (y_ld < c || y_ld > kUpsmMaxC || (SI && c < 2)) return RTSDS_ERR_SHAPE;  // SI: 1 / ln c
   UpsmPlan p;
   if (const int rc = upsm_plan(n, hi, wi, c, ho, wo, scale_w, p)) return rc;
   const bool staged = p.taps <= (size_t)kUpsmLds;
@@ -1147,10 +1299,23 @@ extern "C" int rtsds_upsoftmax_fwd(const void* x, void* y, int n, int hi, int wi
   const size_t lds = (staged ? p.taps + 16 : 0) + outb;
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_T(dtype, upsm_dispatch(staged, c, [&](auto s, auto cc) {
-    hipLaunchKernelGGL((upsoftmax_fwd_kernel<T, decltype(s)::value, decltype(cc)::value>), dim3(p.blocks), dim3(256), lds, st,
-                       (const T*)x, (T*)y, hi, wi, c, ho, wo, scale_h, scale_w, y_ld, p.tiles);
+    if constexpr (SI)
+      hipLaunchKernelGGL((upselfinfo_fwd_kernel<T, decltype(s)::value, decltype(cc)::value>), dim3(p.blocks), dim3(256), lds, st,
+                         (const T*)x, (T*)y, hi, wi, c, ho, wo, scale_h, scale_w, y_ld, p.tiles,
+                         (float)(1.0 / std::log((double)c)));
+    else
+      hipLaunchKernelGGL((upsoftmax_fwd_kernel<T, decltype(s)::value, decltype(cc)::value>), dim3(p.blocks), dim3(256), lds, st,
+                         (const T*)x, (T*)y, hi, wi, c, ho, wo, scale_h, scale_w, y_ld, p.tiles);
   }));
   RET_LAUNCH();
+}
+extern "C" int rtsds_upsoftmax_fwd(const void* x, void* y, int n, int hi, int wi, int c, int ho, int wo, float scale_h,
+                                   float scale_w, int y_ld, int dtype, void* stream) {
+  return upsm_fwd_entry<false>(x, y, n, hi, wi, c, ho, wo, scale_h, scale_w, y_ld, dtype, stream);
+}
+extern "C" int rtsds_upselfinfo_fwd(const void* x, void* y, int n, int hi, int wi, int c, int ho, int wo, float scale_h,
+                                    float scale_w, int y_ld, int dtype, void* stream) {
+  return upsm_fwd_entry<true>(x, y, n, hi, wi, c, ho, wo, scale_h, scale_w, y_ld, dtype, stream);
 }
 extern "C" int rtsds_upsoftmax_acc(const void* x, float* acc, int64_t* pred, int n, int hi, int wi, int c, int ho, int wo,
                                    float scale_h, float scale_w, int flip, int accumulate, int dtype, void* stream) {
@@ -1258,9 +1423,23 @@ extern "C" int rtsds_slide_paint(const void* x, const int* win, int nwin, const 
 extern "C" size_t rtsds_upsoftmax_bwd_workspace(int n, int hi, int wi, int c, int ho, int wo) {
   return rtsds_bilinear_bwd_workspace(n, hi, wi, c, ho, wo);
 }
-// widest tile (<= 64 input columns) whose staged segment + weight table fit kUpsmLds; cap =
-// its exact largest segment, maxw = the most output columns any input column reads
-static bool upsm_tiling(int wi, int wo, int c, float sw, size_t esz, int& tw, int& cap, int& maxw) {
+// tiles of tw input columns: cap = the exact largest segment of output columns any of them reads, cols =
+// the most low-res columns any tile's segment taps (upsm_tap_cols + its margin)
+static void upsm_tile_span(int wi, int wo, float sw, int tw, int& cap, int& cols) {
+  cap = cols = 0;
+  for (int iw0 = 0; iw0 < wi; iw0 += tw) {
+    int lo, hi;
+    bil_adj_range(iw0, std::min(wi, iw0 + tw) - 1, sw, wo, lo, hi);
+    cap = std::max(cap, hi - lo + 1);
+    cols = std::max(cols, upsm_tap_cols(wi, sw, lo, hi) + 2);
+  }
+}
+// widest tile (64 input columns, narrowed by halves) whose staged segment + weight table fit kUpsmLds;
+// cap = its exact largest segment, maxw = the most output columns any input column reads
+// extra(tw, cols): what else the kernel keeps in LDS beside a segment of esz-byte elements and the
+// table, cols = the most low-res columns any tile's segment taps (upsm_tap_cols + its margin)
+template <typename X>
+static bool upsm_tiling(int wi, int wo, int c, float sw, size_t esz, int& tw, int& cap, int& maxw, int& cols, X extra) {
   maxw = 0;
   for (int iw = 0; iw < wi; ++iw) {
     int lo, hi;
@@ -1268,13 +1447,8 @@ static bool upsm_tiling(int wi, int wo, int c, float sw, size_t esz, int& tw, in
     maxw = std::max(maxw, hi - lo + 1);
   }
   for (tw = 64; tw >= 1; tw /= 2) {
-    cap = 0;
-    for (int iw0 = 0; iw0 < wi; iw0 += tw) {
-      int lo, hi;
-      bil_adj_range(iw0, std::min(wi, iw0 + tw) - 1, sw, wo, lo, hi);
-      cap = std::max(cap, hi - lo + 1);
-    }
-    if ((size_t)cap * c * esz + (size_t)tw * (maxw + 1) * 4 <= (size_t)kUpsmLds) return true;
+    upsm_tile_span(wi, wo, sw, tw, cap, cols);
+    if ((size_t)cap * c * esz + (size_t)tw * (maxw + 1) * 4 + extra(tw, cols) <= (size_t)kUpsmLds) return true;
   }
   return false;
 }
@@ -1287,8 +1461,9 @@ extern "C" int rtsds_upsoftmax_bwd(const void* dy, int dy_ld, const void* y, int
   hipStream_t st = (hipStream_t)stream;
   float* tmp = (float*)ws;
   DISPATCH_T(dtype, {
-    int tw, cap, maxw;
-    if (!upsm_tiling(wi, wo, c, scale_w, sizeof(T), tw, cap, maxw)) return RTSDS_ERR_UNSUPPORTED;
+    int tw, cap, maxw, cols;
+    if (!upsm_tiling(wi, wo, c, scale_w, sizeof(T), tw, cap, maxw, cols, [](int, int) { return (size_t)0; }))
+      return RTSDS_ERR_UNSUPPORTED;
     const int tiles = rt_cdiv(wi, tw);
     const long blocks = (long)n * ho * tiles;
     if (blocks > INT_MAX) return RTSDS_ERR_UNSUPPORTED;
@@ -1296,6 +1471,55 @@ extern "C" int rtsds_upsoftmax_bwd(const void* dy, int dy_ld, const void* y, int
     upsm_with_cc(c, [&](auto cc) {
       hipLaunchKernelGGL((upsoftmax_bwd_w_kernel<T, decltype(cc)::value>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)dy,
                          dy_ld, (const T*)y, y_ld, tmp, wi, c, wo, scale_w, tw, tiles, cap, maxw);
+    });
+    bil_bwd_h_launch(tmp, (T*)dx, n, hi, wi, c, ho, scale_h, st);
+  });
+  RET_LAUNCH();
+}
+extern "C" size_t rtsds_upselfinfo_bwd_workspace(int n, int hi, int wi, int c, int ho, int wo) {
+  return rtsds_bilinear_bwd_workspace(n, hi, wi, c, ho, wo);
+}
+// The self-information backward's tile keeps, beside rtsds_upsoftmax_bwd's table, the segment as fp32
+// (dy, then dz) and the two staged source rows [2][cols][c] as fp32.  The tile narrows from 64 input
+// columns by halves until that fits kUpsmLds; a geometry whose single-column tile does not fit (one
+// input column spreading over some 370 output columns at 32 classes) is unsupported.
+// The per-pixel recomputation, the kernel's main cost, takes the segment 256 pixels at a pass, so a
+// segment just over a multiple of 256 (x8: 8 tw + 12 pixels, 268 at tw = 32) spends a whole pass on a
+// few lanes.  upsi_trim narrows the tile further to the widest width whose segment needs one pass
+// less, where that lowers the passes per input column (32 -> 30 at x8 and 19 classes: 1 pass per 30
+// columns instead of 2 per 32); narrower tiles need no more LDS.
+static void upsi_trim(int wi, int wo, float sw, int& tw, int& cap, int& cols) {
+  const int passes = rt_cdiv(cap, kUpsmPix);
+  if (passes < 2) return;
+  for (int t2 = tw - 1; (passes - 1) * tw < passes * t2; --t2) {  // (passes - 1) / t2 < passes / tw
+    int cap2, cols2;
+    upsm_tile_span(wi, wo, sw, t2, cap2, cols2);
+    if (cap2 <= kUpsmPix * (passes - 1) && cols2 <= cols) {
+      tw = t2, cap = cap2, cols = cols2;
+      return;
+    }
+  }
+}
+extern "C" int rtsds_upselfinfo_bwd(const void* dy, int dy_ld, const void* x, void* dx, int n, int hi, int wi, int c, int ho,
+                                    int wo, float scale_h, float scale_w, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  const long total = (long)n * hi * wi * c;
+  if (total <= 0 || ho <= 0 || wo <= 0 || c < 2 || c > kUpsmMaxC || dy_ld < c) return RTSDS_ERR_SHAPE;
+  if (ws_bytes < rtsds_upselfinfo_bwd_workspace(n, hi, wi, c, ho, wo)) return RTSDS_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  float* tmp = (float*)ws;
+  const auto rows = [c](int, int cols) { return (size_t)2 * cols * c * sizeof(float); };
+  int tw, cap, maxw, cols;
+  if (!upsm_tiling(wi, wo, c, scale_w, sizeof(float), tw, cap, maxw, cols, rows)) return RTSDS_ERR_UNSUPPORTED;
+  upsi_trim(wi, wo, scale_w, tw, cap, cols);
+  const int tiles = rt_cdiv(wi, tw);
+  const long blocks = (long)n * ho * tiles;
+  if (blocks > INT_MAX) return RTSDS_ERR_UNSUPPORTED;
+  const size_t lds = (size_t)tw * (maxw + 1) * 4 + (size_t)cap * c * sizeof(float) + rows(tw, cols);
+  DISPATCH_T(dtype, {
+    upsm_with_cc(c, [&](auto cc) {
+      hipLaunchKernelGGL((upselfinfo_bwd_w_kernel<T, decltype(cc)::value>), dim3((unsigned)blocks), dim3(256), lds, st, (const T*)dy,
+                         dy_ld, (const T*)x, tmp, hi, wi, c, ho, wo, scale_h, scale_w, tw, tiles, cap, maxw, 2 * cols * c,
+                         (float)(1.0 / std::log((double)c)));
     });
     bil_bwd_h_launch(tmp, (T*)dx, n, hi, wi, c, ho, scale_h, st);
   });

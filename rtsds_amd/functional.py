@@ -2113,6 +2113,51 @@ def upsample_softmax(x, geo):
     return y
 
 
+class UpsampleSelfInformationFn(torch.autograd.Function):
+    """ADVENT's weighted self-information maps -p log p / log c of the resized head in one pass
+    (rtsds_upselfinfo_fwd), in UpsampleSoftmaxFn's padded layout.  -p log p does not determine p,
+    so the backward (rtsds_upselfinfo_bwd) forms p again from the saved low-resolution head with
+    the forward's own code instead of reading the full-resolution output."""
+
+    @staticmethod
+    def forward(ctx, x, geo):
+        require_hip(x)
+        x = nhwc(x)
+        n, c, hi, wi = x.shape
+        if not 2 <= c <= 32:
+            raise RuntimeError(f"rtsds_amd.upsample_self_information: the class count must lie in [2, 32], got {c}")
+        ho, wo, sh, sw = geo
+        cp = 32
+        buf = torch.empty((n, ho, wo, cp), dtype=x.dtype, device=x.device)
+        lib.rtsds_upselfinfo_fwd(_P(x), _P(buf), n, hi, wi, c, ho, wo, sh, sw, cp, dcode(x), stream())
+        ctx.geo = geo
+        ctx.save_for_backward(x)
+        return buf.permute(0, 3, 1, 2)[:, :c]
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        n, c, hi, wi = x.shape
+        ho, wo, sh, sw = ctx.geo
+        dy = nhwc(dy)
+        if dy.dtype != x.dtype:
+            dy = cast(dy, x.dtype)
+        dx = empty_nhwc(n, c, hi, wi, x.dtype, x.device)
+        ws = workspace(lib.rtsds_upselfinfo_bwd_workspace(n, hi, wi, c, ho, wo), x.device)
+        lib.rtsds_upselfinfo_bwd(_P(dy), c, _P(x), _P(dx), n, hi, wi, c, ho, wo, sh, sw, dcode(x), _P(ws), ws.numel(), stream())
+        return dx, None
+
+
+def upsample_self_information(x, geo):
+    """The discriminator input of AdvEnt (Vu et al., CVPR 2019): I_k = -p_k log p_k / log c with
+    p = softmax over classes of the resized head, as upsample_softmax's zero-padded tensor
+    (functional.is_padded_input).  x [n, c, hi, wi], 2 <= c <= 32, fp32 or bf16, NHWC or NCHW memory;
+    include/rtsds_hip.h states the arithmetic.  HIP only, no CPU fallback."""
+    y = UpsampleSelfInformationFn.apply(x, geo)
+    y._rt_cpad = 32
+    return y
+
+
 def upsample_softmax_accumulate(x, geo, acc, flip=False, accumulate=True, pred=None):
     """One pass of multi-scale / flip evaluation (rtsds_upsoftmax_acc): the fp32 probabilities
     softmax(interpolate_bilinear(x, geo), dim=1) are stored into (``accumulate=False``) or added

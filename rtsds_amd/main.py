@@ -16,6 +16,10 @@ DeepLab generator; validation accepts class_names / detailed_report.
 --entropy_min (with --dataset gta5; config block training.entropy_minimisation, rtsds_amd/entmin.py):
 the segmentation branch trains on labelled GTA5 batches and adds an unsupervised entropy penalty on
 unlabelled Cityscapes train batches -- ADVENT's MinEnt, FDA's robust entropy or Maximum Squares.
+
+--domain_adaptation with the config key training.domain_adaptation.discriminator_input: self_information
+plays the adversarial game on ADVENT's self-information maps -p log p / log c (AdvEnt) instead of the
+probabilities (softmax, the default: the reference's AdaptSegNet form); train.da_step's d_input.
 """
 import argparse
 import os
@@ -31,7 +35,7 @@ from .models.bisenet import build_bisenet
 from .models.deeplabv2 import deeplabv2
 from .models.domain_shift.adversarial.model import DomainDiscriminator, TinyDomainDiscriminator
 from .runtime import set_compute_dtype
-from .train import adversarial_train, train
+from .train import D_INPUTS, adversarial_train, train
 from .utils import dist_env, forModel
 from .validation import val, val_GTA5
 
@@ -356,6 +360,16 @@ def entropy_minimisation_config(config):
     return em
 
 
+def discriminator_input_config(config):
+    """training.domain_adaptation.discriminator_input: what the discriminator sees of the generator's
+    output, ``softmax`` (absent: the same) or ``self_information`` (AdvEnt); train.da_step's d_input."""
+    v = config.training["domain_adaptation"].get("discriminator_input", "softmax")
+    if not isinstance(v, str) or v not in D_INPUTS:
+        raise RuntimeError(f"rtsds_amd: training.domain_adaptation.discriminator_input must be one of "
+                           f"{', '.join(D_INPUTS)}, got {v!r}")
+    return v
+
+
 def self_train_online(config, st, model, optimizer, criterion, init_lr, power, lr_decay_iter, target_dl, validate,
                       callbacks, source_dl, model_name):
     """Online (mean-teacher) self-training, ``mode: online``: a second model of the branch's
@@ -431,7 +445,10 @@ def argumnet_parser(argv=None):
     p.add_argument("--config", type=str, default=os.path.join(os.path.dirname(__file__), "config.yaml"))
     p.add_argument("--dataset", type=str, default="cityscapes")
     p.add_argument("--augmented", action="store_true")
-    p.add_argument("--domain_adaptation", action="store_true")
+    p.add_argument("--domain_adaptation", action="store_true",
+                   help="adversarial training against a domain discriminator; the config key "
+                        "training.domain_adaptation.discriminator_input chooses what it sees: softmax "
+                        "(AdaptSegNet, the default) or self_information (AdvEnt)")
     p.add_argument("--model", type=str, default="bisenet")
     p.add_argument("--wandb", action="store_true")
     p.add_argument("--seed", type=int, default=42)
@@ -477,6 +494,7 @@ def main(argv=None):
                            "the Cityscapes train set (else source and target would be the same set)")
     kd = distillation_config(config) if args.distill else None
     em =entropy_minimisation_config(config) if args.entropy_min else None
+    d_input = discriminator_input_config(config) if args.domain_adaptation else None
     train_dl, val_dl, gta_dl = datasets_loader(config, args.augmented)
     target_dl = train_dl
     callbacks = []
@@ -492,7 +510,7 @@ def main(argv=None):
                           gen_power=g_hp["gen_power"], dis_power=d_hp["dis_power"],
                           num_classes=t["num_classes"], class_names=config.meta["class_names"],
                           val_loader=val_dl, do_validation=t["do_validation"], when_print=t["when_print"],
-                          callbacks=callbacks, device=config.device)
+                          callbacks=callbacks, device=config.device, d_input=d_input)
         if st is not None:
             self_train(config, st, g, g_opt, g_loss, g_hp["gen_init_lr"], g_hp["gen_power"], t["lr_decay_iter"],
                        t["num_classes"], target_dl,

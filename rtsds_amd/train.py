@@ -190,6 +190,10 @@ def _seg_loss(model, criterion, x, label, correct):
     return loss, outs[0], None
 
 
+# da_step's d_input: the fused op (of rtsds_amd.functional) that turns a low-resolution head into
+# the discriminator's input
+D_INPUTS = {"softmax": "upsample_softmax", "self_information": "upsample_self_information"}
+
 # da_step (fused path, single process): target forward on a second stream during the source
 # backward (see _da_step_fused); False = strictly serial issue (A/B tests)
 DA_OVERLAP = True
@@ -206,11 +210,23 @@ def _full(t, geo):
 
 def da_step(generator, discriminator, generator_optimizer, discriminator_optimizer,
             generator_loss, discriminator_loss, source_image, source_label, target_image,
-            lambda_, iterations):
+            lambda_, iterations, d_input="softmax"):
     """One adversarial_train iteration body (train.py:174-275, LR scheduling excluded).
     Returns device tensors (l_seg, l_adv, l_dsrc, l_dtgt, correct).  The source heads' resizes
     run fused into their cross-entropy; the discriminator consumes the detached main output,
-    so it is resized without a gradient graph."""
+    so it is resized without a gradient graph.  ``d_input``: what the discriminator sees of a
+    resized head, ``"softmax"`` (AdaptSegNet, the reference) or ``"self_information"`` (AdvEnt,
+    Vu et al. 2019: the maps -p log p / log c, functional.upsample_self_information); the latter
+    exists on the fused path only and raises where that path does not apply."""
+    if d_input not in D_INPUTS:
+        raise ValueError(f"rtsds_amd.da_step: d_input must be one of {', '.join(repr(k) for k in D_INPUTS)}, got {d_input!r}")
+    if d_input != "softmax":  # no unfused form: what is known before any work is refused before any work
+        why = ("the discriminator does not read the padded class maps (accepts_padded_probs)"
+               if not getattr(discriminator, "accepts_padded_probs", False) else
+               "the generator has no forward_lowres" if not hasattr(generator, "forward_lowres") else None)
+        if why is not None:
+            raise RuntimeError(f"rtsds_amd.da_step: d_input={d_input!r} runs on the fused path only, and {why}; "
+                               "there is no unfused form")
     generator_optimizer.zero_grad()
     discriminator_optimizer.zero_grad()
     # the discriminator is frozen while the generator trains (train.py:192-193)
@@ -223,7 +239,14 @@ def da_step(generator, discriminator, generator_optimizer, discriminator_optimiz
             hasattr(generator, "forward_lowres") and main.shape[1] <= 32:
         return _da_step_fused(generator, discriminator, generator_optimizer, discriminator_optimizer,
                               discriminator_loss, main, geo, target_image, lambda_, iterations, loss_seg,
-                              correct)
+                              correct, d_input)
+    if d_input != "softmax":  # (the discriminator and the generator were checked before any work)
+        for p in discriminator.parameters():
+            p.requires_grad = True
+        why = (f"{main.shape[1]} classes exceed the fused kernels' 32" if main.shape[1] > 32 else
+               "the heads share no resize geometry (the segmentation loss took the unfused path)")
+        raise RuntimeError(f"rtsds_amd.da_step: d_input={d_input!r} runs on the fused path only, and {why}; "
+                           "there is no unfused form")
     loss_seg.backward(_one(loss_seg))
     with torch.no_grad():
         source_features = _full(main.detach(), geo)
@@ -257,13 +280,17 @@ def da_step(generator, discriminator, generator_optimizer, discriminator_optimiz
 
 
 def _da_step_fused(generator, discriminator, generator_optimizer, discriminator_optimizer,
-                   discriminator_loss, main, geo, target_image, lambda_, iterations, loss_seg, correct):
+                   discriminator_loss, main, geo, target_image, lambda_, iterations, loss_seg, correct,
+                   d_input="softmax"):
     """da_step's discriminator phases with the full-resolution resize and softmax of each
     head fused into one pass that writes the discriminator's padded input
     (functional.upsample_softmax): identical values to softmax(interpolate(head)) -- the
     reference's D(softmax(G(x))) at train.py:225,245,256 -- without the full-resolution logits,
     the separate softmax pass or the conv's channel-pad pass.  softmax(target_feature.detach())
-    (train.py:256) equals the G-phase target probabilities, so they are computed once."""
+    (train.py:256) equals the G-phase target probabilities, so they are computed once.  With
+    ``d_input="self_information"`` the same three passes write AdvEnt's self-information maps
+    instead (functional.upsample_self_information); nothing else differs."""
+    d_in = getattr(F, D_INPUTS[d_input])
     amb = torch.cuda.current_stream(main.device)
     overlap = DA_OVERLAP and dp_world() <= 1 and branches_enabled()
     if overlap:
@@ -283,7 +310,7 @@ def _da_step_fused(generator, discriminator, generator_optimizer, discriminator_
     split = dp_world() > 1 and hasattr(generator_optimizer, "start_grad_allreduce")
     with ctx, (branches_serial() if overlap else contextlib.nullcontext()), collect_cuts(split) as cuts:
         (t_low, t_geo), = generator.forward_lowres(target_image, main_only=True)
-        target_probs = F.upsample_softmax(t_low, t_geo)
+        target_probs = d_in(t_low, t_geo)
         pred_t = discriminator(target_probs)
         ones = torch.ones(pred_t.size(), device=pred_t.device)
         loss_adv = lambda_ * discriminator_loss(pred_t, ones) / iterations
@@ -293,7 +320,7 @@ def _da_step_fused(generator, discriminator, generator_optimizer, discriminator_
         for t in (target_probs, loss_adv):
             t.record_stream(amb)
     with torch.no_grad():
-        source_probs = F.upsample_softmax(main.detach(), geo)
+        source_probs = d_in(main.detach(), geo)
     if overlap:
         # D's source phase needs only source_probs and D's (unchanged) weights, and writes only
         # D's gradients, which the adversarial backward (through the frozen D into G) never
@@ -376,8 +403,9 @@ def adversarial_train(iterations: int, epochs: int, generator: torch.nn.Module,
                       discriminator_loss: torch.nn.Module, lambda_: float, gen_init_lr: float,
                       gen_power: float, dis_power: float, dis_init_lr: float, lr_decay_iter: float,
                       num_classes: int, class_names: list, val_loader, do_validation: int = 1,
-                      device: str = "cuda", when_print: int = 10, callbacks: list = []):
-    """AdaptSegNet-style output-space adversarial training (train.py:130-318)."""
+                      device: str = "cuda", when_print: int = 10, callbacks: list = [], d_input: str = "softmax"):
+    """AdaptSegNet-style output-space adversarial training (train.py:130-318); with
+    ``d_input="self_information"`` AdvEnt's form of it (da_step)."""
     gen_lr = None
     for epoch in range(epochs):
         for cb in callbacks:
@@ -402,7 +430,7 @@ def adversarial_train(iterations: int, epochs: int, generator: torch.nn.Module,
             target_image = target_image.to(device)
             *losses, corr = da_step(generator, discriminator, generator_optimizer,
                                     discriminator_optimizer, generator_loss, discriminator_loss,
-                                    source_image, source_label, target_image, lambda_, iterations)
+                                    source_image, source_label, target_image, lambda_, iterations, d_input)
             vals = _host_values(list(losses) + [corr[0]])
             for k in range(4):
                 run[k] += vals[k]
