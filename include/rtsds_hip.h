@@ -446,6 +446,32 @@ int rtsds_adam_step_dev(float* param, const void* grad, float* exp_avg, float* e
                         void* bf16_shadow, long n, const float* hyper, float beta1, float beta2,
                         float eps, float weight_decay, float grad_scale, int grad_dtype, void* stream);
 
+/* rtsds_adam_step_dev over a run [0, n) of the arena, fused with the pending split-K reductions
+ * of the weight gradients inside it (rtsds_conv2d_wgrad_deferred): ONE launch.  descs: n_descs
+ * pending reductions, ascending in dw, whose ranges [dw, dw + 4 nv) are disjoint, 16-B aligned
+ * and inside [grad, grad + n).  For those ranges the slabs are summed exactly as
+ * rtsds_split_reduce_many sums them and the update is applied to the sum at once: the gradient
+ * is neither written to nor read from the arena.  desc.accumulate here is a set of flags: bit 0
+ * -- the arena holds an earlier contribution, read and added first (earlier + sum, as the reduce
+ * does); RTSDS_SLAB_KEEP_GRAD -- the gradient is also stored into the arena.  Every other element
+ * of the run gets the plain update, gradient from the arena; each element exactly once, no
+ * atomics.  Bit for bit rtsds_split_reduce_many followed by rtsds_adam_step_dev (a clean range
+ * skips the reduce's 0 + sum, which differs only for sum = -0 and gives the same p, m, v).
+ * max_descs: 0, or a lower cap on n_descs (tests).  RTSDS_ERR_UNSUPPORTED, nothing launched:
+ * n_descs above the cap (56 -- the tables travel as kernel arguments), grad_dtype other than
+ * RTSDS_F32, a base pointer not 16-B aligned (shadow: 8-B), n >= 2^31 - 4096; RTSDS_ERR_SHAPE:
+ * a malformed, unsorted, overlapping or out-of-run descriptor.  The caller then reduces with
+ * rtsds_split_reduce_many and calls rtsds_adam_step_dev.                                     */
+#define RTSDS_SLAB_KEEP_GRAD 2
+int rtsds_adam_step_slabs(float* param, float* grad, float* exp_avg, float* exp_avg_sq, void* bf16_shadow,
+                          long n, const float* hyper, float beta1, float beta2, float eps,
+                          float weight_decay, float grad_scale, int grad_dtype, int n_descs,
+                          const rtsds_split_reduce_desc* descs, int max_descs, void* stream);
+/* buf[lo[i] .. hi[i]) = 0 for count ranges (host arrays, floats), one launch per 128 ranges:
+ * the optimizer's zero_grad over the gradient ranges written since the last one.
+ * RTSDS_ERR_SHAPE: a NULL pointer with count > 0, lo < 0, hi < lo or a range of 2^31 floats. */
+int rtsds_zero_ranges(float* buf, int count, const long* lo, const long* hi, void* stream);
+
 /* torch.optim.SGD step (main.py:118-120) over a flat fp32 arena: d = grad*grad_scale
  * (+ weight_decay*param); with momentum, buf = d on the first step (first != 0), else
  * buf = momentum*buf + (1-dampening)*d; d = nesterov ? d + momentum*buf : buf;
@@ -971,7 +997,7 @@ int rtsds_label_stats(const int64_t* label, int n, int h, int w, int c, int igno
 /* ABI revision of this header (RTSDS_ABI_VERSION): bumped whenever an entry point's signature
  * changes.  The Python loader refuses a library whose revision differs (A/B variant libraries
  * built from older sources would otherwise be called with the wrong argument lists). */
-#define RTSDS_ABI_VERSION 28
+#define RTSDS_ABI_VERSION 29
 int rtsds_abi_version(void);
 
 #ifdef __cplusplus

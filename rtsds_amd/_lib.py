@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTSDS_LIB: alternative in-tree build of the same ABI (kernel-variant A/B measurements)
 DEFAULT_LIB_PATH = os.path.join(_HERE, "librtsds_hip.so")
-ABI_VERSION = 28  # include/rtsds_hip.h RTSDS_ABI_VERSION
+ABI_VERSION = 29  # include/rtsds_hip.h RTSDS_ABI_VERSION
 LIB_PATH = os.environ.get("RTSDS_LIB") or DEFAULT_LIB_PATH
 
 F32, BF16 = 0, 1
@@ -151,6 +151,9 @@ SIGNATURES = {
     "rtsds_bce_fwd": (c_int, [P, P, P, c_int, P]),
     "rtsds_bce_bwd": (c_int, [P, P, P, P, c_int, P]),
     "rtsds_adam_step_dev": (c_int, [P, P, P, P, P, c_long, P, c_float, c_float, c_float, c_float, c_float, c_int, P]),
+    "rtsds_adam_step_slabs": (c_int, [P, P, P, P, P, c_long, P, c_float, c_float, c_float, c_float, c_float, c_int, c_int,
+                                      ctypes.POINTER(SplitReduceDesc), c_int, P]),
+    "rtsds_zero_ranges": (c_int, [P, c_int, ctypes.POINTER(c_long), ctypes.POINTER(c_long), P]),
     "rtsds_upsoftmax_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, P]),
     "rtsds_upsoftmax_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "rtsds_upsoftmax_bwd": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,

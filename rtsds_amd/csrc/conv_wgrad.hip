@@ -3,6 +3,7 @@
 // in conv_gemm_wgrad.hip), the workspace plan, and the helper kernels: split-K reductions, bias
 // column sums, the narrow pointwise gradient, the superpixel dW unpack.
 #include "conv_host.h"
+#include "split_reduce_dev.h"
 
 // dw[co][tap][ci] = sum_s part[s][co][tap][ci_p]   (split-K reduce + channel unpad).
 // V consecutive input channels per thread (16-byte slab reads when c % 4 == 0), splits
@@ -277,34 +278,12 @@ __global__ void __launch_bounds__(256) split_reduce_many_kernel(const ReduceBatc
   const rtsds_split_reduce_desc& q = b.d[si];
   const int lane = threadIdx.x & 63, sg = threadIdx.x >> 6;
   const int i = ((int)blockIdx.x - b.blk0[si]) * 64 + lane;
-  const bool ok = i < q.nv;
-  const int rt = (ok ? i : 0) / q.cv;  // co * taps + tap
-  const long src = (long)rt * q.cp + (long)((ok ? i : 0) - rt * q.cv) * 4;
-  float s[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int g = sg; ok && g < q.splits; g += 32) {
-    float t[8][4];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const f32x4 v = *(const f32x4*)(q.slab + (long)min(g + 4 * u, q.splits - 1) * q.slab_stride + src);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) t[u][e] = v[e];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (g + 4 * u < q.splits)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[e] += t[u][e];
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) red[sg][lane][e] = s[e];
-  __syncthreads();
-  if (sg == 0 && ok) {
+  float t[4];
+  split_reduce_block(q, i, red, t);  // (split_reduce_dev.h: shared with the fused Adam step)
+  if (sg == 0 && i < q.nv) {
     float* o = q.dw + (long)i * 4;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float t = (red[0][lane][e] + red[1][lane][e]) + (red[2][lane][e] + red[3][lane][e]);
-      o[e] = q.accumulate ? o[e] + t : t;
-    }
+    for (int e = 0; e < 4; ++e) o[e] = q.accumulate ? o[e] + t[e] : t[e];
   }
 }
 extern "C" int rtsds_split_reduce_many(int n, const rtsds_split_reduce_desc* descs, void* stream) {

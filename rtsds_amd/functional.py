@@ -216,23 +216,28 @@ def _join_add(join, g):
 # backward() returns) instead of one small launch per conv (~27 per BiSeNet step).  Same sums,
 # same order.  Off while bench.py event-times each conv (CONV_PROFILE).
 DEFER_WGRAD_REDUCE = True
-_deferred = []  # [(SplitReduceDesc, workspace tensor holding the slabs, stream of the wgrad)]
+# [(SplitReduceDesc, workspace tensor holding the slabs, stream of the wgrad, the weight, keep)]
+# keep: the gradient must stay readable in .grad after the optimizer step (the image convs)
+_deferred = []
+# The optimizer step sums the slabs itself (optim.Adam, rtsds_adam_step_slabs): the reductions of a
+# backward pass whose optimizer has opted in (fuse_wgrad_reduce_into; train.seg_step) are handed to
+# it instead of launched, and the weight gradients never reach the arena.  False: always reduce
+# at the end of the backward (A/B runs and tests).
+FUSE_REDUCE_ADAM = True
+_fuse_into = [None]  # the optimizer that opted in for the backward pass now running
 
 
-def flush_wgrad_reduce():
-    """Run the pending split-K reductions (every deferral also queues this as an end-of-backward
-    callback; the first one of a backward pass does the work, optim.step() calls it too)."""
-    global _deferred
-    items, _deferred = _deferred, []
-    if not items:
-        return
-    cur = torch.cuda.current_stream(items[0][1].device)
-    for st in {it[2] for it in items}:  # wgrads issued on branch streams
-        if st != cur:
-            cur.wait_stream(st)
-    # one launch per run of distinct targets (a parameter reduced twice keeps its order)
+def fuse_wgrad_reduce_into(optimizer):
+    """Opt in for the next backward pass only: its deferred reductions onto ``optimizer``'s
+    parameters go to optimizer.take_wgrad_reduces() at the end of the pass (None: opt out)."""
+    _fuse_into[0] = optimizer if FUSE_REDUCE_ADAM and DEFER_WGRAD_REDUCE else None
+
+
+def reduce_wgrads_now(items, cur):
+    """rtsds_split_reduce_many over pending items on stream ``cur``: one launch per run of distinct
+    targets (a parameter reduced twice keeps its order); the targets now hold their gradients."""
     batch, seen = [], set()
-    for desc, _ws, _st in items + [(None, None, None)]:
+    for desc, *_ in list(items) + [(None,)]:
         if desc is None or desc.dw in seen or len(batch) == 16:
             if batch:
                 arr = (SplitReduceDesc * len(batch))(*batch)
@@ -241,12 +246,45 @@ def flush_wgrad_reduce():
         if desc is not None:
             batch.append(desc)
             seen.add(desc.dw)
-    for _desc, ws, st in items:
+    for _desc, _ws, _st, weight, _keep in items:
+        arena, i = weight._rt_arena
+        arena.dirty[i] = True
+
+
+def flush_wgrad_reduce():
+    """Run the pending split-K reductions (every deferral also queues this as an end-of-backward
+    callback; the first one of a backward pass does the work, optim.step() calls it too) -- or
+    hand them to the optimizer that opted in for this pass."""
+    global _deferred
+    items, _deferred = _deferred, []
+    owner, _fuse_into[0] = _fuse_into[0], None
+    if not items:
+        return
+    cur = torch.cuda.current_stream(items[0][1].device)
+    for st in {it[2] for it in items}:  # wgrads issued on branch streams
+        if st != cur:
+            cur.wait_stream(st)
+    mine = []
+    if owner is not None and FUSE_REDUCE_ADAM:
+        own = owner.arenas()
+        mine = [it for it in items if any(it[3]._rt_arena[0] is a for a in own)]
+        owner.take_wgrad_reduces(mine)
+    reduce_wgrads_now([it for it in items if not any(it is m for m in mine)], cur)
+    for _desc, ws, st, *_ in items:
         if st != cur:
             ws.record_stream(cur)
 
 
-def _wgrad_into_arena(d, x, g, sinks, xflag, ws):
+def _defer(pend, ws, weight, keep=False):
+    """Queue a pending reduction onto ``weight``'s arena gradient: the sink handed out for it has
+    not been written."""
+    arena, i = weight._rt_arena
+    arena.sink_unwritten(i)
+    _deferred.append((pend, ws, torch.cuda.current_stream(ws.device), weight, keep))
+    torch.autograd.Variable._execution_engine.queue_callback(flush_wgrad_reduce)
+
+
+def _wgrad_into_arena(d, x, g, sinks, xflag, ws, weight):
     """Weight gradient accumulated into the optimizer arena; its split-K reduction deferred to
     the end of the backward pass when allowed."""
     if DEFER_WGRAD_REDUCE and CONV_PROFILE is None and x.dtype == torch.bfloat16:
@@ -254,8 +292,7 @@ def _wgrad_into_arena(d, x, g, sinks, xflag, ws):
         lib.rtsds_conv2d_wgrad_deferred(ctypes.byref(d), _P(x), _P(g), _P(sinks[0]), _P(sinks[1]), 1 | xflag,
                                         _P(ws), ws.numel(), ctypes.byref(pend), stream())
         if pend.nv > 0:
-            _deferred.append((pend, ws, torch.cuda.current_stream(ws.device)))
-            torch.autograd.Variable._execution_engine.queue_callback(flush_wgrad_reduce)
+            _defer(pend, ws, weight)
         return
     with _Timed(d, "wgrad"):
         lib.rtsds_conv2d_wgrad(ctypes.byref(d), _P(x), _P(g), _P(sinks[0]), _P(sinks[1]), 1 | xflag,
@@ -372,7 +409,7 @@ class ConvFn(torch.autograd.Function):
             sinks = _sinks(weight, bias if ctx.needs_input_grad[2] else None) if ctx.needs_input_grad[1] else None
             ws = workspace(lib.rtsds_conv2d_wgrad_workspace(ctypes.byref(d)), x.device)
             if sinks is not None:
-                _wgrad_into_arena(d, x, g, sinks, ctx.xflag, ws)
+                _wgrad_into_arena(d, x, g, sinks, ctx.xflag, ws, weight)
                 dw = None
                 db = None
             else:
@@ -396,8 +433,9 @@ def _img_bn_wgrad(d, x, g, bx, coef, act, weight, xflag):
         pend = SplitReduceDesc()
         lib.rtsds_imgconv_bn_wgrad_deferred(ctypes.byref(d), _P(x), _P(g), _P(bx), _P(coef), act, _P(sinks[0]),
                                             1 | xflag, _P(ws), ws.numel(), ctypes.byref(pend), stream())
-        _deferred.append((pend, ws, torch.cuda.current_stream(ws.device)))
-        torch.autograd.Variable._execution_engine.queue_callback(flush_wgrad_reduce)
+        # keep: the image convs' gradients stay readable after the step (11 k floats; the fused
+        # BatchNorm form is checked against them at model level)
+        _defer(pend, ws, weight, keep=True)
         return None
     dw = sinks[0] if sinks is not None else torch.empty((d.k, d.c, d.kh, d.kw), dtype=torch.float32,
                                                          device=x.device, memory_format=CL)

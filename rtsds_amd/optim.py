@@ -25,7 +25,7 @@ import warnings
 import torch
 import torch.distributed as dist
 
-from ._lib import ConvDesc, lib
+from ._lib import ERRORS, ConvDesc, SplitReduceDesc, lib, load
 from .runtime import bump_params_epoch, collective, dp_world, stream
 
 
@@ -44,6 +44,7 @@ def set_allreduce_dtype(dtype):
 
 
 _DCODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+SLAB_KEEP_GRAD = 2  # include/rtsds_hip.h RTSDS_SLAB_KEEP_GRAD
 
 
 def wire_active():
@@ -133,6 +134,38 @@ def allreduce_start(buffers, wires=None):
     return finish
 
 
+def zero_plan(offsets, total, need):
+    """Arena ranges [lo, hi) (floats) zero_grad fills: the segments (a parameter and the padding
+    behind it, up to the next offset) of the parameters flagged in ``need``, neighbours merged."""
+    out = []
+    for i, off in enumerate(offsets):
+        if not need[i]:
+            continue
+        end = offsets[i + 1] if i + 1 < len(offsets) else total
+        if out and out[-1][1] == off:
+            out[-1] = (out[-1][0], end)
+        else:
+            out.append((off, end))
+    return out
+
+
+def slab_plan(lo, hi, targets):
+    """The fused step's plan for the arena run [lo, hi): ``targets`` = [(offset, floats)] of the
+    pending reductions' gradient ranges.  Returns (order, holes): the targets' indices ascending
+    in offset and the ranges [start, end) the slab blocks cover (the plain blocks take the rest) --
+    or None when the fused launch cannot take them: a range reduced twice or overlapping another,
+    outside the run, empty or not a whole number of 16-B vectors."""
+    order = sorted(range(len(targets)), key=lambda k: targets[k][0])
+    holes, at = [], lo
+    for k in order:
+        off, n = targets[k]
+        if n <= 0 or n % 4 or off % 4 or off < at or off + n > hi:
+            return None
+        holes.append((off, off + n))
+        at = off + n
+    return order, holes
+
+
 class _Arena:
     """One parameter group's flat fp32 buffers: parameters, gradients, first moment (Adam's
     exp_avg / SGD's momentum buffer), second moment (Adam only) and the bf16 shadow."""
@@ -158,6 +191,12 @@ class _Arena:
         self.gwire = None  # reduced-precision all-reduce wire: the summed gradients (wire())
         self.steps = [0] * len(params)
         self.touched = [False] * len(params)
+        # per parameter: its gradient range may be non-zero (written since the last zero_grad);
+        # a clean range is all zeros.  lazy: its sink of this step was handed out for a deferred
+        # split-K reduction and has not been written (functional._defer)
+        self.dirty = [False] * len(params)
+        self.lazy = [False] * len(params)
+        self._was_dirty = [False] * len(params)
         self.gen = [0] * len(params)  # generation of the last gradient write (_GEN)
         # per parameter: its gradient's all-reduce has been started (optimizer.start_grad_allreduce
         # with partial=True); a later gradient write would be missing from the reduced sum
@@ -170,6 +209,7 @@ class _Arena:
                 view.copy_(p.data)
                 p.data = view
                 p.grad = self.gflat[off:off + n].as_strided(p.shape, p.stride())
+        self._gver = self.gflat._version  # gflat's version counter at the last look (_hook)
         lib.rtsds_cast(self.flat.data_ptr(), 0, self.shadow.data_ptr(), 1, total, stream())
         for i, p in enumerate(params):
             off, n = self.offsets[i], p.numel()
@@ -196,6 +236,11 @@ class _Arena:
         def mark(_p):
             self._check_open(i)
             self.touched[i] = True
+            # (the hook also fires when the Function returned None because a kernel took the sink:
+            # only an AccumulateGrad that really added into the view bumps the buffer's version)
+            if self.gflat._version != self._gver:
+                self._gver = self.gflat._version
+                self.dirty[i] = True
             self.gen[i] = _GEN[0]
         return mark
 
@@ -226,8 +271,15 @@ class _Arena:
             return None
         self._check_open(i)
         self.touched[i] = True
+        self._was_dirty[i], self.dirty[i] = self.dirty[i], True
         self.gen[i] = _GEN[0]
         return self.params[i].grad
+
+    def sink_unwritten(self, i):
+        """The sink just handed out for parameter i was not written: its gradient waits in
+        split-K slabs (functional._defer) and dirties the range only when it is reduced into it."""
+        self.dirty[i] = self._was_dirty[i]
+        self.lazy[i] = True
 
     def grad_ptr_ok(self, i):
         p = self.params[i]
@@ -240,6 +292,7 @@ class _Arena:
         view = self.gflat[off:off + n].as_strided(p.shape, p.stride())
         if p.grad is not None:
             view.copy_(p.grad)
+            self.dirty[i] = True
         p.grad = view
 
 
@@ -266,6 +319,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._ring_pos = 0
         self._finish = []        # pending early gradient all-reduces (start_grad_allreduce)
         self._reduced = None     # per arena: parameters whose all-reduce has been started
+        # split-K reductions of this step's weight gradients handed over by functional.
+        # flush_wgrad_reduce instead of launched (take_wgrad_reduces): functional._deferred's items,
+        # their slab workspaces kept referenced until the step has consumed them
+        self._pending = []
 
     # ------------------------------------------------------------------ arena
     def _ensure(self):
@@ -330,13 +387,64 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self._import_state()
 
     def zero_grad(self, set_to_none=True):
+        """Zero the gradient ranges written since the last zero_grad (one launch per arena; the
+        whole arena as one fill when every parameter was written).  A range whose gradient was
+        consumed from the split-K slabs by the fused step was never written and stays zero."""
+        self._pending = []  # reductions never run: those gradients go with the rest
         for a in self._ensure():
-            a.gflat.zero_()
-            for i in range(len(a.params)):
-                a.touched[i] = False
+            n = len(a.params)
+            for i in range(n):
                 if not a.grad_ptr_ok(i):
                     a.rebind_grad(i)
-                    a.gflat[a.offsets[i]:a.offsets[i] + a.params[i].numel()].zero_()
+            need = [a.dirty[i] or (a.touched[i] and not a.lazy[i]) for i in range(n)]
+            rng = zero_plan(a.offsets, a.total, need)
+            if rng == [(0, a.total)]:
+                a.gflat.zero_()
+            elif rng:
+                lo = (ctypes.c_long * len(rng))(*[r[0] for r in rng])
+                hi = (ctypes.c_long * len(rng))(*[r[1] for r in rng])
+                lib.rtsds_zero_ranges(a.gflat.data_ptr(), len(rng), lo, hi, stream())
+            for i in range(n):
+                a.touched[i] = a.dirty[i] = a.lazy[i] = False
+            a._gver = a.gflat._version
+
+    # ------------------------------------------------------------------ fused split-K reduce
+    fuses_wgrad_reduce = False  # the step can sum split-K slabs itself (train.seg_step opts in)
+    SLAB_MAX_DESCS = 0          # lower cap on the reductions per fused launch (0: the kernel's own; tests)
+
+    def take_wgrad_reduces(self, items):
+        """The reductions of the backward pass just finished (functional.flush_wgrad_reduce): kept
+        for step(), which sums the slabs inside the update launch.  Until then the targets' .grad
+        does not hold these gradients -- materialize_grads() puts them there."""
+        self._pending = self._pending + list(items)
+
+    @torch.no_grad()
+    def materialize_grads(self):
+        """Run the reductions taken over now (rtsds_split_reduce_many, as without the fusion), so
+        that every .grad is complete; step() then runs the plain update.  For whoever reads
+        gradients between backward and step."""
+        items, self._pending = self._pending, []
+        if items:
+            from .functional import reduce_wgrads_now
+            reduce_wgrads_now(items, torch.cuda.current_stream(items[0][1].device))
+
+    def _can_fuse(self, arenas, gscale):
+        """The pending reductions can go into the update launches: a plain fp32 single-device
+        step, every target still in its arena, touched, and reduced once."""
+        if not self.fuses_wgrad_reduce or dp_world() > 1 or wire_active() or gscale != 1.0:
+            return False
+        seen = set()
+        for desc, _ws, _st, weight, _keep in self._pending:
+            a, i = weight._rt_arena
+            if desc.dw in seen or not a.touched[i] or not a.grad_ptr_ok(i) or not any(a is b for b in arenas):
+                return False
+            seen.add(desc.dw)
+        return True
+
+    def _launch_slabs(self, g, a, lo, hi, hyper, gscale, items):
+        """The update of arena run [lo, hi) fused with the pending reductions ``items`` inside it;
+        False (nothing launched): not taken, the caller reduces and runs the plain update."""
+        return False
 
     # ------------------------------------------------------------------ step
     def _fix_grads(self, arenas):
@@ -372,6 +480,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         if not _OVERLAP["on"] or dp_world() <= 1 or not (dist.is_available() and dist.is_initialized()):
             return
         arenas = self._ensure()
+        self.materialize_grads()  # (the all-reduce reads the arena)
         self._fix_grads(arenas)
         if self._reduced is None:
             self._reduced = [[False] * len(a.params) for a in arenas]
@@ -423,21 +532,32 @@ class _FlatOptimizer(torch.optim.Optimizer):
                     j += 1
                 runs.append((gi, i, j))
                 i = j + 1
+        pend = self._pending
+        if pend and not self._can_fuse(arenas, gscale):
+            self.materialize_grads()
+            pend = []
         if self._capturing:
             if runs != self._runs or self._hyper is None:
                 raise RuntimeError(f"rtsds_amd.{self._NAME}: step structure changed under graph capture")
         else:
             self._runs = runs
-            if self._graph:
+            if self._graph or pend:  # (the fused launch reads its hyperparameters from the device)
                 self.stage_hyper()
         for r, (gi, i, j) in enumerate(runs):
             g, a = self.param_groups[gi], arenas[gi]
             lo = a.offsets[i]
             hi = a.offsets[j] + a.params[j].numel()
-            hyper = self._hyper.data_ptr() + 12 * r if self._graph else None
-            self._launch(g, a, lo, hi, a.steps[i] + 1, hyper, gscale)
+            mine = [it for it in pend if it[3]._rt_arena[0] is a and i <= it[3]._rt_arena[1] <= j]
+            if mine and not self._launch_slabs(g, a, lo, hi, self._hyper.data_ptr() + 12 * r, gscale, mine):
+                from .functional import reduce_wgrads_now
+                reduce_wgrads_now(mine, torch.cuda.current_stream(a.flat.device))
+                mine = []
+            if not mine:
+                hyper = self._hyper.data_ptr() + 12 * r if self._graph else None
+                self._launch(g, a, lo, hi, a.steps[i] + 1, hyper, gscale)
             for k in range(i, j + 1):
                 a.steps[k] += 1
+        self._pending = []
         for a in arenas:
             if a.shadow is not None:
                 a.repack()
@@ -523,6 +643,33 @@ class Adam(_FlatOptimizer):
         else:
             lib.rtsds_adam_step(*ptrs, float(g["lr"]), float(b1), float(b2), float(g["eps"]),
                                 float(g["weight_decay"]), t, gscale, gd, stream())
+
+    fuses_wgrad_reduce = True
+
+    def _launch_slabs(self, g, a, lo, hi, hyper, gscale, items):
+        base = a.gflat.data_ptr()
+        plan = slab_plan(lo, hi, [((it[0].dw - base) // 4, 4 * it[0].nv) for it in items])
+        if plan is None:
+            return False
+        descs = (SplitReduceDesc * len(items))()
+        for k, src in enumerate(plan[0]):
+            desc, _ws, _st, weight, keep = items[src]
+            i = weight._rt_arena[1]
+            ctypes.memmove(ctypes.byref(descs[k]), ctypes.byref(desc), ctypes.sizeof(SplitReduceDesc))
+            # bit 0: the range already holds a gradient written this step, added first
+            descs[k].accumulate = (1 if a.dirty[i] else 0) | (SLAB_KEEP_GRAD if keep else 0)
+        b1, b2 = g["betas"]
+        rc = load().rtsds_adam_step_slabs(*_ptrs(a, lo, hi, "flat", "gflat", "m", "v"), a.shadow.data_ptr() + 2 * lo, hi - lo,
+                                          hyper, float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), gscale, 0,
+                                          len(items), descs, int(self.SLAB_MAX_DESCS), stream())
+        if rc == 2:  # RTSDS_ERR_UNSUPPORTED, nothing launched (more reductions than one launch takes)
+            return False
+        if rc != 0:
+            raise RuntimeError(f"rtsds_amd: rtsds_adam_step_slabs failed: {ERRORS.get(rc, rc)}")
+        for _desc, _ws, _st, weight, keep in items:
+            if keep:
+                a.dirty[weight._rt_arena[1]] = True
+        return True
 
     def _hyper3(self, g, t):
         # betas rounded to fp32 first, exactly as rtsds_adam_step receives them (eager and

@@ -86,6 +86,15 @@ def _backward(loss, optimizer, cuts, since=None):
             torch.autograd.backward([x], [xd.grad])
 
 
+def _fuse_reduce(optimizer):
+    """The step about to run has exactly one backward pass: let a single-device flat Adam sum that
+    pass's split-K weight-gradient slabs inside its update launch (functional.FUSE_REDUCE_ADAM).
+    Not for data parallelism (the all-reduce needs the gradients in the arena), SGD, or steps
+    whose backward passes accumulate (da_step)."""
+    ok = dp_world() == 1 and getattr(optimizer, "fuses_wgrad_reduce", False)
+    F.fuse_wgrad_reduce_into(optimizer if ok else None)
+
+
 def seg_step(model, criterion, optimizer, inputs, targets):
     """One train.train iteration body: zero_grad, forward, CE(main)+CE(aux1)+CE(aux2),
     backward, optimizer step, device-side pixel-accuracy count.  Returns device tensors
@@ -105,6 +114,7 @@ def seg_step(model, criterion, optimizer, inputs, targets):
         correct = torch.empty(1, dtype=torch.int64, device=fused[0][0].device)  # (overwritten)
         loss = F.upsample_cross_entropy(fused[0], targets, fused[1], criterion.ignore_index, correct, set_correct=True,
                                         weight=criterion.weight)
+        _fuse_reduce(optimizer)
         _backward(loss, optimizer, cuts)
         optimizer.step()
         return loss.detach(), correct
@@ -118,6 +128,7 @@ def seg_step(model, criterion, optimizer, inputs, targets):
         loss = loss + criterion(aux1, targets)
     if aux2 is not None:
         loss = loss + criterion(aux2, targets)
+    _fuse_reduce(optimizer)
     _backward(loss, optimizer, cuts)
     optimizer.step()
     correct = torch.zeros(1, dtype=torch.int64, device=main_output.device)
